@@ -9,10 +9,18 @@ step, inputs resident in HBM.  One process per GPU; with N > 1 every rank runs i
 no collective in the loop -- SURVEY.md 8e), `value` = total steps / max-over-ranks time.
 
     python bench.py --gpus 1 --steps 200 --warmup 10
+    python bench.py --gpus 1 --steps 200 --warmup 10 --full
+    python bench.py --gpus 1 --steps 200 --warmup 10 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Per-kernel durations come from two sources, both printed:
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, `config`).  `--full` adds everything else: the per-kernel trace, the roofline / floor / K1
+objects, the end-to-end `pipe(...)` calls, the fp8 and batch-1 variants, the training legs and the CPU baseline.
+`--dump-outputs DIR` writes the latents of the last timed step (what DenoiseEngine.run hands its caller), NCHW float32, to
+DIR/latents.npy (DIR/latents_rank<r>.npy per rank when N > 1); the inputs are seeded, so two builds can be compared.
+
+Per-kernel durations (--full) come from two sources, both printed:
   * `trace`  -- the device-side begin/end timestamps of every kernel of the REPLAYED graph (torch.profiler = roctracer in
                 process; the same timestamps `rocprofv3 --kernel-trace` reports -- profiles/r02*_kernel_trace_summary.txt is
                 that command's summary).  `roofline.achieved` and `k1` are computed from these.
@@ -493,73 +501,12 @@ TRAIN_DTYPE = ("bf16 activations and activation gradients, fp32 accumulation / s
 TRAIN_TOL = "flat LoRA gradient vs fp32 autograd: rel. L2 <= 6e-2 (tests/test_gpu_train_fullsize.py); AdamW vs torch.optim.AdamW 2e-6"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--batch", type=int, default=4)
-    ap.add_argument("--rank", type=int, default=4)
-    ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--chains", type=int, default=None, help="independent sub-batch chains captured as parallel graph branches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the LoRA-training and end-to-end pipeline legs")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr")
-    ap.add_argument("--fine", action="store_true", help="print the per-kernel-per-shape table to stderr")
-    ap.add_argument("--no-trace", action="store_true", help="skip the in-process kernel tracer (use under rocprofv3: one tracer at a time)")
-    ap.add_argument("--fp8-attention", action="store_true", help="BASELINE config 5: fp8 (e4m3) Q/K/V/P attention operands")
-    args = ap.parse_args()
-
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X: the product path has no CPU fallback")
-    torch.cuda.set_device(local)
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-
-    from audioldm_with_lora_amd.engine import DenoiseEngine
-    from audioldm_with_lora_amd.scheduler import DDIMScheduler
-
-    H, W, NSTEPS, G = 250, 16, 200, 2.5
-    unet, _ = build_unet(args.rank)
-    unet.attention_fp8 = args.fp8_attention
-    eng = DenoiseEngine(unet, DDIMScheduler(), args.batch, H, W, NSTEPS, G, use_graph=not args.no_graph, chains=args.chains)
-    lat, pe, ne = synth_inputs(args.batch, H, W, seed_off=100 * rank)
-    eng.set_condition(pe, ne)
-    eng.set_latents(lat)
-    eng.capture()
-
-    def barrier():
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    for _ in range(args.warmup):
-        eng.step()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        eng.step()
-    torch.cuda.synchronize()
-    if dist is not None:
-        dist.barrier()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    if dist is not None:
-        tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        dt = float(tmax.item())
-    assert torch.isfinite(eng.x).all(), "latents diverged"
-
-    # ---- per-kernel measurement on rank 0 (after the timed region: the tracer must not perturb `value`) ----
+def full_legs(args, eng, unet, dt, world, rank, H, W, NSTEPS, G):
+    """--full: everything after the headline, run once the timed region is over (the tracer must not perturb `value`).  Called
+    on every rank (the training legs hold collectives); returns the extra objects of the JSON line on rank 0, None elsewhere."""
+    # ---- per-kernel measurement on rank 0 ----
     rows = kernels = span_us = None
     if rank == 0:
-        print(f"[bench] {args.steps} steps in {dt:.3f} s -> {dt / args.steps * 1e3:.3f} ms/step", file=sys.stderr, flush=True)
         if eng.graph is not None and not args.no_trace:
             kernels, span_us = trace_replays(eng)
         ev_rows = launch_rows(eng)
@@ -626,14 +573,6 @@ def main():
                     "whole_step_tflops": round(8 * 101.2e9 * (args.batch / 4) / (dt / args.steps) / 1e12, 1)}
         floor = floor_model(rows, dt / args.steps * 1e3, boundary_us, small_us)
         out = {
-            "metric": "unet_denoise_steps_per_sec", "value": round(world * args.steps / dt, 3), "unit": "denoise_steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16" if not args.fp8_attention else "bf16 (fp8 e4m3 attention operands)", "data": "synthetic",
-            "config": {"workload": "audioldm-s-full-v2 UNet + rank-%d LoRA (q,k,v,out), DDIM 200-step schedule, "
-                                   "batch %d x 10 s clips (latent 250x16), CFG 2.5 (UNet batch %d), bf16" % (args.rank, args.batch, 2 * args.batch),
-                       "per_gpu_batch": args.batch, "parallelism": f"prompt-sharded x{world}", "hip_graph": not args.no_graph, "graph_chains": eng.chains,
-                       "sample_steps_per_sec": round(world * args.steps * args.batch / dt, 2)},
             "roofline": roofline,
             "floor": floor,
             "k1": {"what": "fused-LoRA attention module = QKV GEMM + LoRA (Q|K, V^T) -> flash attention -> out-proj + LoRA + residual; "
@@ -669,6 +608,108 @@ def main():
             out["train_loop_body"] = body_leg
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.batch, H, W, args.rank)
+        return out
+    return None
+
+
+def dump_outputs(dirname, eng, world, rank, cap_bytes=64 << 20):
+    """The latents after the last timed step, as DenoiseEngine.run hands them to its caller (laid out NCHW, as the pipeline passes
+    them on to the VAE): [B, 8, 250, 16] float32, 0.5 MB per rank at batch 4.  Above 64 MB over all ranks only the first samples
+    of the batch are kept."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    lat = eng.x.detach().cpu().permute(0, 3, 1, 2).contiguous().numpy().astype(np.float32)
+    per_sample = lat[0].nbytes
+    lat = lat[:max(1, cap_bytes // world // per_sample)]
+    name = "latents" if world == 1 else f"latents_rank{rank}"
+    np.save(os.path.join(dirname, name + ".npy"), lat)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--rank", type=int, default=4)
+    ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--chains", type=int, default=None, help="independent sub-batch chains captured as parallel graph branches")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: per-kernel trace, roofline / floor / K1, end-to-end, fp8, batch-1, training and CPU-baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's latents (NCHW float32) to DIR/latents.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-train", action="store_true", help="(--full) skip the LoRA-training and end-to-end pipeline legs")
+    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr (implies --full)")
+    ap.add_argument("--fine", action="store_true", help="print the per-kernel-per-shape table to stderr (implies --full)")
+    ap.add_argument("--no-trace", action="store_true", help="(--full) skip the in-process kernel tracer (use under rocprofv3: one tracer at a time)")
+    ap.add_argument("--fp8-attention", action="store_true", help="BASELINE config 5: fp8 (e4m3) Q/K/V/P attention operands")
+    args = ap.parse_args()
+    full = args.full or args.breakdown or args.fine
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs an MI355X: the product path has no CPU fallback")
+    torch.cuda.set_device(local)
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+
+    from audioldm_with_lora_amd.engine import DenoiseEngine
+    from audioldm_with_lora_amd.scheduler import DDIMScheduler
+
+    H, W, NSTEPS, G = 250, 16, 200, 2.5
+    unet, _ = build_unet(args.rank)
+    unet.attention_fp8 = args.fp8_attention
+    eng = DenoiseEngine(unet, DDIMScheduler(), args.batch, H, W, NSTEPS, G, use_graph=not args.no_graph, chains=args.chains)
+    lat, pe, ne = synth_inputs(args.batch, H, W, seed_off=100 * rank)
+    eng.set_condition(pe, ne)
+    eng.set_latents(lat)
+    eng.capture()
+
+    def barrier():
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    for _ in range(args.warmup):
+        eng.step()
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        eng.step()
+    torch.cuda.synchronize()
+    if dist is not None:
+        dist.barrier()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if dist is not None:
+        tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        dt = float(tmax.item())
+    assert torch.isfinite(eng.x).all(), "latents diverged"
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, world, rank)      # before --full steps the engine any further
+    if rank == 0:
+        print(f"[bench] {args.steps} steps in {dt:.3f} s -> {dt / args.steps * 1e3:.3f} ms/step", file=sys.stderr, flush=True)
+    extra = full_legs(args, eng, unet, dt, world, rank, H, W, NSTEPS, G) if full else None
+    if rank == 0:
+        out = {
+            "metric": "unet_denoise_steps_per_sec", "value": round(world * args.steps / dt, 3), "unit": "denoise_steps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "bf16" if not args.fp8_attention else "bf16 (fp8 e4m3 attention operands)", "data": "synthetic",
+            "config": {"workload": "audioldm-s-full-v2 UNet + rank-%d LoRA (q,k,v,out), DDIM 200-step schedule, "
+                                   "batch %d x 10 s clips (latent 250x16), CFG 2.5 (UNet batch %d), bf16" % (args.rank, args.batch, 2 * args.batch),
+                       "per_gpu_batch": args.batch, "parallelism": f"prompt-sharded x{world}", "hip_graph": not args.no_graph, "graph_chains": eng.chains,
+                       "sample_steps_per_sec": round(world * args.steps * args.batch / dt, 2)},
+        }
+        out.update(extra or {})
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

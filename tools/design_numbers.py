@@ -1,4 +1,4 @@
-"""Rewrites the two tables of DESIGN.md section 5.1 (between the `<!-- 5.1 tables -->` markers) from a bench.py JSON line.
+"""Rewrites the two tables of DESIGN.md section 5.1 (between the `<!-- 5.1 tables -->` markers) from a `bench.py --full` JSON line.
 usage: python tools/design_numbers.py gpurun_out/<tag>_bench.json"""
 import json, re, sys
 

@@ -6,7 +6,7 @@ set -e
 TAG=${1:-r02x}
 OUT=$PWD/gpurun_out
 export TMPDIR=/tmp
-BENCH="bench.py --no-cpu-baseline --no-train --no-trace --steps 50 --warmup 5"
+BENCH="bench.py --full --no-cpu-baseline --no-train --no-trace --steps 50 --warmup 5"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG} -o inf -- python3 $BENCH > $OUT/prof_${TAG}.log 2>&1
 python3 tools/prof_summary.py $OUT/prof_${TAG}/inf_kernel_trace.csv --top 70 > $OUT/${TAG}_kernel_trace_summary.txt
 python3 tools/prof_summary.py $OUT/prof_${TAG}/inf_kernel_trace.csv --top 90 --by-grid > $OUT/${TAG}_kernel_trace_by_grid.txt
@@ -16,7 +16,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_train -
 python3 tools/prof_summary.py $OUT/prof_${TAG}_train/trn_kernel_trace.csv --top 70 > $OUT/${TAG}_train_kernel_trace_summary.txt
 cp $OUT/prof_${TAG}_train/trn_kernel_stats.csv $OUT/${TAG}_train_kernel_stats.csv
 echo "[profile] training trace done"
-PB="bench.py --no-cpu-baseline --no-train --no-trace --steps 3 --warmup 1"
+PB="bench.py --full --no-cpu-baseline --no-train --no-trace --steps 3 --warmup 1"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/prof_${TAG}_fetch -o f -- python3 $PB > $OUT/prof_${TAG}_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/prof_${TAG}_write -o w -- python3 $PB > $OUT/prof_${TAG}_write.log 2>&1
 python3 tools/pmc_traffic.py $OUT/prof_${TAG}_fetch/f_counter_collection.csv $OUT/prof_${TAG}_write/w_counter_collection.csv > $OUT/${TAG}_pmc_traffic.json
