@@ -1,5 +1,5 @@
 // Small fused elementwise kernels of the denoise loop and the training step (gfx950, HBM/latency-bound):
-// timestep embedding, SiLU, layout/precision boundary conversions, the fused CFG + DDIM update with a
+// timestep embedding, SiLU, layout/precision boundary conversions, the fused CFG + DDIM (or DPM-Solver multistep) update with a
 // device-side step counter (so one captured hipGraph replays all 200 steps), and flat AdamW.
 // [REF script/inference/generate_audio.py:47-52] (AudioLDMPipeline.__call__ loop body)
 // [REF script/train/train_audioldm_lora.py:396-403,563-565] (torch.optim.AdamW on the LoRA parameters)
@@ -129,6 +129,77 @@ __global__ __launch_bounds__(256) void ddim_step_fused_kernel(const float* __res
     // the last workgroup's stores below after every other workgroup's ticket -- by the memory model, not by an incidental s_waitcnt
     const unsigned done = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     if (done == gridDim.x - 1) {                              // last workgroup: nobody will read step_idx[0] again in this launch
+      ticket[0] = 0;
+      step_idx[0] = nxt;
+      t_out[0] = timesteps[nxt];
+    }
+  }
+}
+
+// guidance + DPM-Solver(++) multistep update of one element from a coefficient row {alpha_s, sig_s, A, B, C, convert, reads_hist, -}
+// (scheduler.py DPMSolverMultistepScheduler.coefficient_table), every fused multiply-add spelled out as in ddim_update:
+//   m0 = convert ? (x - sig_s e) / alpha_s : e ;  x' = A x + B m0 + C (m0 - m1)      (m1 = hist; C == 0 and m1 unread on first-order rows)
+__device__ __forceinline__ float dpm_model_output(float eu, float et, float xv, int cfg, float g, float alpha_s, float sig_s, bool convert) {
+  const float e = cfg ? fmaf(g, et - eu, eu) : eu;
+  return convert ? fmaf(-sig_s, e, xv) / alpha_s : e;
+}
+
+__device__ __forceinline__ float dpm_update(float m0, float m1, float xv, float A, float Bc, float Cc) {
+  return fmaf(A, xv, fmaf(Bc, m0, Cc * (m0 - m1)));
+}
+
+// The DPM-Solver multistep counterpart of ddim_step_fused_kernel: guidance, model-output conversion, the first- or second-order
+// update (history `hist` [B][n] fp32: the previous step's converted output, read only on rows that ask for it, then overwritten
+// with this step's), the bf16 next UNet input, the next step's time-embedding row and the counter advance, as ONE launch.  The
+// counter protocol (every workgroup reads step_idx[0] when it starts, the last one by the agent-scope ticket moves it) is
+// ddim_step_fused_kernel's unchanged.  ticket == NULL: the counter is left alone (eager scheduler.step; table is NULL there too).
+template <int VEC>
+__global__ __launch_bounds__(256) void dpm_step_fused_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
+                                                             float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                             bf16* __restrict__ x_in, float* __restrict__ hist, const float* __restrict__ table,
+                                                             long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                             int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket) {
+  typedef float fvec __attribute__((ext_vector_type(VEC)));
+  typedef bf16 bvec __attribute__((ext_vector_type(VEC)));
+  const int cur = step_idx[0];
+  int nxt = cur + 1;
+  if (nxt >= n_steps) nxt = 0;                                // wrap: a replayed graph may run past the schedule (benchmarks)
+  const long long tix = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long idx = tix * VEC;
+  const long long total = (long long)B * n;
+  if (idx < total) {
+    fvec eu = *reinterpret_cast<const fvec*>(eps + idx), et = eu;
+    if (cfg) et = *reinterpret_cast<const fvec*>(eps + total + idx);
+    const fvec xv = *reinterpret_cast<const fvec*>(x + idx);
+    const float* cf = coef + 8 * cur;
+    const float alpha_s = cf[0], sig_s = cf[1], A = cf[2], Bc = cf[3], Cc = cf[4];
+    const bool convert = cf[5] != 0.f, second = cf[6] != 0.f;
+    fvec m1 = (fvec)0.f;
+    if (second) m1 = *reinterpret_cast<const fvec*>(hist + idx);   // a first-order row (row 0 among them) never loads the history
+    fvec xn, m0;
+    bvec xb;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      m0[k] = dpm_model_output(eu[k], et[k], xv[k], cfg, g, alpha_s, sig_s, convert);
+      const float r = dpm_update(m0[k], second ? m1[k] : m0[k], xv[k], A, Bc, Cc);
+      xn[k] = r;
+      xb[k] = (bf16)r;
+    }
+    *reinterpret_cast<fvec*>(x + idx) = xn;
+    *reinterpret_cast<fvec*>(hist + idx) = m0;
+    if (x_in) {
+      *reinterpret_cast<bvec*>(x_in + idx) = xb;
+      if (cfg) *reinterpret_cast<bvec*>(x_in + total + idx) = xb;
+    }
+  }
+  if (table && tix * 4 < row_elems)
+    *reinterpret_cast<f32x4*>(rowbias + tix * 4) = *reinterpret_cast<const f32x4*>(table + (long long)nxt * row_elems + tix * 4);
+  if (!ticket) return;                                        // (uniform over the grid)
+  __syncthreads();                                            // every thread of this workgroup has read the counter
+  if (threadIdx.x == 0) {
+    // acq_rel at agent scope, as in ddim_step_fused_kernel
+    const unsigned done = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (done == gridDim.x - 1) {
       ticket[0] = 0;
       step_idx[0] = nxt;
       t_out[0] = timesteps[nxt];
@@ -268,6 +339,27 @@ extern "C" int aldm_ddim_step_fused(const float* eps, float* x, int B, long long
     hipLaunchKernelGGL(ddim_step_fused_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample, cfg,
                        guidance, coef, step_idx, (bf16*)x_in_bf16, table, table ? row_elems : 0, rowbias, timesteps, n_steps, t_out, ticket);
   return aldm_launch_status("ddim_step_fused");
+}
+
+extern "C" int aldm_dpm_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                   int* step_idx, void* x_in_bf16, float* hist, const float* table, long long row_elems, float* rowbias,
+                                   const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream) {
+  ALDM_CHECK_ARG(eps && x && coef && step_idx && hist && B > 0 && n_per_sample > 0 && n_steps > 0, "dpm_step_fused: bad args");
+  ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "dpm_step_fused: the counter advance needs timesteps and t_out");
+  ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
+                 "dpm_step_fused: table needs ticket, rowbias and row_elems %% 4 == 0");
+  if (!table) row_elems = 0;
+  const long long total = (long long)B * n_per_sample;
+  const bool v4 = total % 4 == 0;                       // (torch allocations are 16-byte aligned; CFG's second half starts at `total`)
+  const long long items = v4 ? total / 4 : total;
+  const long long work = items > row_elems / 4 ? items : row_elems / 4;
+  if (v4)
+    hipLaunchKernelGGL(dpm_step_fused_kernel<4>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample, cfg,
+                       guidance, coef, step_idx, (bf16*)x_in_bf16, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket);
+  else
+    hipLaunchKernelGGL(dpm_step_fused_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample, cfg,
+                       guidance, coef, step_idx, (bf16*)x_in_bf16, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket);
+  return aldm_launch_status("dpm_step_fused");
 }
 
 extern "C" int aldm_add_noise(const float* x, const float* noise, const float* coef, int B, long long n_per_sample,

@@ -7,11 +7,13 @@ One step is ~450 kernel launches of a few microseconds each, so the loop is laun
 the host.  Everything that changes between steps lives in DEVICE memory -- the latent x, the CFG-doubled
 bf16 UNet input, the timestep scalar and a step counter that indexes the precomputed DDIM coefficient
 table -- so ONE captured graph of a single step replays unchanged for all N steps with no host work
-in between.
+in between.  With a DPMSolverMultistepScheduler the update is the multistep solver's (ops.dpm_step_fused): its coefficient rows
+come from the scheduler in the same way, and the previous step's model output lives in one more device buffer.
 """
 import torch
 
 from . import ops
+from .scheduler import DPMSolverMultistepScheduler
 
 
 class DenoiseEngine:
@@ -22,11 +24,12 @@ class DenoiseEngine:
         self.C = unet.cfg["in_channels"]
         self.cfg = guidance_scale > 1.0
         self.g = float(guidance_scale)
-        self.n_steps = num_inference_steps
         self.use_graph = use_graph
         dev = torch.device(device)
         self.dev = dev
         scheduler.set_timesteps(num_inference_steps)
+        self.n_steps = len(scheduler.timesteps)
+        self.dpm = isinstance(scheduler, DPMSolverMultistepScheduler)
         self.timesteps_f32 = scheduler.timesteps.to(torch.float32).to(dev)
         self.coef = scheduler.coefficient_table().contiguous().to(dev)
         # Optional: independent sub-batches ("chains") captured as parallel branches of the graph (each owns a contiguous
@@ -35,14 +38,18 @@ class DenoiseEngine:
         # default stays a single chain.
         if chains is None:
             chains = 1
+        if chains > 1 and self.dpm:
+            raise NotImplementedError("chains > 1 runs the DDIM update only")
         assert batch % chains == 0
         self.chains, self.bc = chains, batch // chains
         nbc = 2 * self.bc if self.cfg else self.bc
         self.x = torch.zeros(batch, height, width, self.C, dtype=torch.float32, device=dev)       # latents, NHWC fp32
         self.x_in = [torch.zeros(nbc, height, width, self.C, dtype=torch.bfloat16, device=dev) for _ in range(chains)]
+        # DPM-Solver: the previous step's converted model output (read by second-order rows, never by row 0)
+        self.hist = torch.zeros_like(self.x) if self.dpm else None
         self.t_buf = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)      # aldm_ddim_step_fused's last-workgroup ticket (rests at 0)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)      # the fused step's last-workgroup ticket (rests at 0)
         self.cls = None
         self.temb = None             # [chains][n_steps, nbc, temb_total] fp32: time-embedding projections of every step
         self.rowbias = None          # [chains][nbc, temb_total] fp32: the current step's row (gathered on the device)
@@ -104,6 +111,8 @@ class DenoiseEngine:
                 self.x_in[i][self.bc:].copy_(xb[sl])
         self.step_idx.zero_()
         self.t_buf.copy_(self.timesteps_f32[:1])
+        if self.hist is not None:
+            self.hist.zero_()
         self._prime()
 
     def _prime(self):
@@ -122,8 +131,12 @@ class DenoiseEngine:
 
     def _one_step(self):
         if self.chains == 1:
-            # one chain: guidance + DDIM update, the next step's time-embedding row and the step counter in ONE launch behind the UNet
+            # one chain: guidance + the scheduler's update, the next step's time-embedding row and the step counter in ONE launch behind the UNet
             eps = self.unet.forward_nhwc(self.x_in[0], self.t_buf, self.cls[0], rowbias=self.rowbias[0])
+            if self.dpm:
+                ops.dpm_step_fused(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.hist, self.temb[0],
+                                   self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket)
+                return
             ops.ddim_step_fused(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.temb[0], self.rowbias[0],
                                 self.timesteps_f32, self.t_buf, self.ticket)
             return
@@ -146,6 +159,7 @@ class DenoiseEngine:
         self.graph = None
         self._plan_ref, self.plan_version = self.unet.plan(), self.unet.plan_version
         saved = (self.x.clone(), [t.clone() for t in self.x_in], self.step_idx.clone(), self.t_buf.clone())
+        saved_hist = self.hist.clone() if self.hist is not None else None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -159,6 +173,8 @@ class DenoiseEngine:
                 self._one_step()
         for dst, src in zip([self.x] + self.x_in + [self.step_idx, self.t_buf], [saved[0]] + saved[1] + [saved[2], saved[3]]):
             dst.copy_(src)
+        if saved_hist is not None:
+            self.hist.copy_(saved_hist)
         self._prime()
         torch.cuda.synchronize()
 

@@ -1142,6 +1142,26 @@ def ddim_step_fused(eps, x, cfg, guidance, coef, step_idx, x_in, table, rowbias,
                                                            _stream())), "aldm_ddim_step_fused")
 
 
+def dpm_step_fused(eps, x, cfg, guidance, coef, step_idx, x_in, hist, table=None, rowbias=None, timesteps_f32=None, t_out=None,
+                   ticket=None):
+    """CFG + DPM-Solver(++) multistep update (+ gather_row(next step) + advance_step when `ticket` is given) as one launch
+    (aldm_dpm_step_fused).  coef fp32 [n_steps, 8] (DPMSolverMultistepScheduler.coefficient_table); hist fp32, x's shape: the
+    previous step's converted model output, read by second-order rows and overwritten.  ticket None: eager, the counter stays."""
+    _require_gpu(x)
+    B = x.shape[0]
+    n = x.numel() // B
+    row = table[0].numel() if table is not None else 0
+    assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.shape[1] == 8 and step_idx.dtype == torch.int32
+    assert hist.dtype == torch.float32 and hist.numel() == x.numel() and eps.numel() == x.numel() * (2 if cfg else 1)
+    assert ticket is None or (ticket.dtype == torch.int32 and timesteps_f32 is not None and t_out is not None)
+    n_steps = timesteps_f32.numel() if timesteps_f32 is not None else coef.shape[0]
+    # bytes: eps (1 or 2 halves) + x read/write + hist read/write (upper bound: second-order rows) + bf16 UNet input (1 or 2 halves)
+    check(_launch("dpm_step_fused", 10.0 * x.numel(), (4.0 * (2 if cfg else 1) + 8.0 + 8.0 + 2.0 * (2 if cfg else 1)) * x.numel() + 8.0 * row,
+                  lambda: _lib.load().aldm_dpm_step_fused(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in), _p(hist),
+                                                          _p(table), row, _p(rowbias), _p(timesteps_f32), n_steps, _p(t_out), _p(ticket),
+                                                          _stream())), "aldm_dpm_step_fused")
+
+
 def add_noise(x, noise, coef):
     _require_gpu(x)
     B = x.shape[0]

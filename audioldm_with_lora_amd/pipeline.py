@@ -25,6 +25,13 @@ class AudioPipelineOutput(SimpleNamespace):
     pass
 
 
+def _frozen_config(scheduler):
+    """the scheduler's configuration as a hashable, sorted tuple (lists become tuples)"""
+    cfg = scheduler.config
+    items = cfg.items() if isinstance(cfg, dict) else vars(cfg).items()
+    return tuple(sorted((k, tuple(v) if isinstance(v, list) else v) for k, v in items))
+
+
 class AudioLDMPipeline:
     def __init__(self, vae, text_encoder, tokenizer, unet, scheduler, vocoder):
         self.vae, self.text_encoder, self.tokenizer = vae, text_encoder, tokenizer
@@ -90,10 +97,11 @@ class AudioLDMPipeline:
         return height, n_samples
 
     def engine(self, batch, h, w, steps, guidance):
-        key = (batch, h, w, steps, float(guidance))
+        # the scheduler is part of the key: a graph captured with one scheduler's update and coefficients must never replay for another
+        key = (batch, h, w, steps, float(guidance), type(self.scheduler).__name__, _frozen_config(self.scheduler))
         eng = self._engines.get(key)
-        if eng is not None and (eng.unet is not self._unet or eng.stale()):
-            eng = None                                  # weights / adapter changed since the capture: never replay the old graph
+        if eng is not None and (eng.unet is not self._unet or eng.scheduler is not self.scheduler or eng.stale()):
+            eng = None                                  # weights / adapter / scheduler changed since the capture: never replay the old graph
         if eng is None:
             eng = self._engines[key] = DenoiseEngine(self._unet, self.scheduler, batch, h, w, steps, guidance, device=self.device)
         return eng

@@ -1,10 +1,12 @@
-"""DDIMScheduler for the HIP path (host-side integer logic + device step kernel).
+"""DDIMScheduler and DPMSolverMultistepScheduler for the HIP path (host-side integer logic + device step kernels).
 
 Same surface the reference touches: `from_pretrained(id, subfolder="scheduler")`, `.config.num_train_timesteps`,
 `.add_noise` [REF script/train/train_audioldm_lora.py:367,503-504] and, through the pipeline,
 `set_timesteps / timesteps / step / init_noise_sigma / scale_model_input` [REF script/inference/generate_audio.py:47-52].
 Arithmetic spec: SURVEY.md Appendix B.1 (diffusers 0.32.2).  Timestep indices are int64 and computed exactly as
 diffusers does ("leading" spacing, steps_offset); the fp32 alpha-bar table uses the same torch ops as diffusers.
+DPMSolverMultistepScheduler is diffusers 0.32.2's deterministic multistep solver, swapped in the way diffusers
+users do it: `pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)`.
 """
 import json
 import os
@@ -15,6 +17,21 @@ import torch
 
 from . import ops
 from .configs import SCHEDULER
+
+
+def _read_config(path, subfolder):
+    d = os.path.join(path, subfolder) if subfolder else path
+    f = os.path.join(d, "scheduler_config.json")
+    if not os.path.isfile(f):
+        raise FileNotFoundError(f"{f} not found: hub downloads are unavailable, pass a local directory")
+    with open(f) as fh:
+        return json.load(fh)
+
+
+def _config_dict(config, over):
+    d = dict(config) if isinstance(config, dict) else dict(vars(config))
+    d.update(over)
+    return d
 
 
 class DDIMScheduler:
@@ -36,11 +53,12 @@ class DDIMScheduler:
 
     @classmethod
     def from_pretrained(cls, path, subfolder=None, **kw):
-        d = os.path.join(path, subfolder) if subfolder else path
-        f = os.path.join(d, "scheduler_config.json")
-        if not os.path.isfile(f):
-            raise FileNotFoundError(f"{f} not found: hub downloads are unavailable, pass a local directory")
-        return cls(**json.load(open(f)))
+        return cls(**_read_config(path, subfolder))
+
+    @classmethod
+    def from_config(cls, config, **over):
+        """dict or SimpleNamespace (e.g. another scheduler's `.config`); keys this class does not know are ignored."""
+        return cls(**_config_dict(config, over))
 
     def scale_model_input(self, sample, timestep=None):
         return sample
@@ -86,3 +104,205 @@ class DDIMScheduler:
         if ac is None:
             ac = self._dev[("ac", dev)] = self.alphas_cumprod.to(dev, torch.float32).contiguous()
         return ops.add_noise_t(original_samples, noise, ac, timesteps.to(dev, torch.int64).reshape(-1))
+
+
+# diffusers 0.32.2 DPMSolverMultistepScheduler defaults for the solver keys; the keys it shares with DDIMScheduler default to the
+# AudioLDM scheduler configuration, as DDIMScheduler's do here
+DPM_CONFIG = dict(
+    num_train_timesteps=SCHEDULER["num_train_timesteps"], beta_start=SCHEDULER["beta_start"], beta_end=SCHEDULER["beta_end"],
+    beta_schedule=SCHEDULER["beta_schedule"], trained_betas=None, solver_order=2, prediction_type=SCHEDULER["prediction_type"],
+    thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0, algorithm_type="dpmsolver++", solver_type="midpoint",
+    lower_order_final=True, euler_at_final=False, use_karras_sigmas=False, use_exponential_sigmas=False, use_beta_sigmas=False,
+    use_lu_lambdas=False, final_sigmas_type="zero", lambda_min_clipped=-float("inf"), variance_type=None,
+    timestep_spacing=SCHEDULER["timestep_spacing"], steps_offset=SCHEDULER["steps_offset"], rescale_betas_zero_snr=False,
+)
+
+
+class DPMSolverMultistepScheduler:
+    """DPM-Solver / DPM-Solver++ (first or second order, deterministic), diffusers 0.32.2 arithmetic restated.
+
+    `coefficient_table()` turns the whole schedule into fp32 rows {alpha_s, sig_s, A, B, C, convert, reads_hist, 0}; the device
+    update (aldm_dpm_step_fused) is then  m0 = convert ? (x - sig_s e) / alpha_s : e ;  x' = A x + B m0 + C (m0 - m1),  with m1 the
+    previous step's m0 (the history buffer) and 1 / r0 folded into C.  First-order rows have C = 0 and never read the history."""
+
+    def __init__(self, **over):
+        cfg = dict(DPM_CONFIG)
+        cfg.update({k: v for k, v in over.items() if k in DPM_CONFIG})
+        self.config = SimpleNamespace(**cfg)
+        self._check(cfg)
+        n = cfg["num_train_timesteps"]
+        self.betas = torch.linspace(cfg["beta_start"] ** 0.5, cfg["beta_end"] ** 0.5, n, dtype=torch.float32) ** 2
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.alpha_t = torch.sqrt(self.alphas_cumprod)
+        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+        self.sigmas = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
+        self.init_noise_sigma = 1.0
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.linspace(0, n - 1, n, dtype=np.float32)[::-1].copy().astype(np.int64))
+        self._step_index = None
+        self._lower_order_nums = 0
+        self._hist = {}
+        self._dev = {}
+
+    @staticmethod
+    def _check(cfg):
+        alg = cfg["algorithm_type"]
+        if alg in ("sde-dpmsolver", "sde-dpmsolver++"):
+            raise NotImplementedError(f"algorithm_type={alg!r}: the SDE variants draw noise inside every step (not in the captured graph)")
+        if alg not in ("dpmsolver++", "dpmsolver"):
+            raise NotImplementedError(f"algorithm_type={alg!r}")
+        if cfg["solver_order"] not in (1, 2):
+            raise NotImplementedError(f"solver_order={cfg['solver_order']}: only first and second order are implemented")
+        if cfg["solver_type"] not in ("midpoint", "heun"):
+            raise NotImplementedError(f"solver_type={cfg['solver_type']!r}")
+        for k in ("thresholding", "use_karras_sigmas", "use_exponential_sigmas", "use_beta_sigmas", "use_lu_lambdas",
+                  "rescale_betas_zero_snr"):
+            if cfg[k]:
+                raise NotImplementedError(f"{k}=True")
+        if cfg["prediction_type"] != "epsilon":
+            raise NotImplementedError(f"prediction_type={cfg['prediction_type']!r}: only epsilon prediction is implemented")
+        if cfg["beta_schedule"] != "scaled_linear" or cfg["trained_betas"] is not None:
+            raise NotImplementedError(f"beta_schedule={cfg['beta_schedule']!r} / trained_betas: only scaled_linear is implemented")
+        if cfg["variance_type"] is not None:
+            raise NotImplementedError(f"variance_type={cfg['variance_type']!r}")
+        if cfg["lambda_min_clipped"] != -float("inf"):
+            raise NotImplementedError(f"lambda_min_clipped={cfg['lambda_min_clipped']}")
+        if cfg["timestep_spacing"] not in ("leading", "linspace", "trailing"):
+            raise NotImplementedError(f"timestep_spacing={cfg['timestep_spacing']!r}")
+        if cfg["final_sigmas_type"] not in ("zero", "sigma_min"):
+            raise NotImplementedError(f"final_sigmas_type={cfg['final_sigmas_type']!r}")
+        if alg == "dpmsolver" and cfg["final_sigmas_type"] == "zero":
+            raise ValueError(f"`final_sigmas_type` {cfg['final_sigmas_type']} is not supported for `algorithm_type` {alg}. "
+                             "Please choose `sigma_min` instead.")
+
+    @classmethod
+    def from_pretrained(cls, path, subfolder=None, **kw):
+        return cls(**_read_config(path, subfolder))
+
+    @classmethod
+    def from_config(cls, config, **over):
+        """dict or SimpleNamespace (e.g. DDIMScheduler's `.config`); keys this class does not know (clip_sample, ...) are ignored."""
+        return cls(**_config_dict(config, over))
+
+    def scale_model_input(self, sample, *args, **kw):
+        return sample
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        cfg = self.config
+        n = cfg.num_train_timesteps
+        if not 0 < num_inference_steps <= n:
+            raise ValueError("need 0 < num_inference_steps <= num_train_timesteps")
+        last = n                                      # lambda_min_clipped = -inf clips nothing
+        N = num_inference_steps
+        if cfg.timestep_spacing == "linspace":
+            ts = np.linspace(0, last - 1, N + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif cfg.timestep_spacing == "leading":
+            ratio = last // (N + 1)
+            ts = (np.arange(0, N + 1) * ratio).round()[::-1][:-1].copy().astype(np.int64)
+            ts += cfg.steps_offset
+        else:                                         # trailing
+            ts = np.arange(last, 0, -n / N).round().copy().astype(np.int64)
+            ts -= 1
+        sig = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        sig = np.interp(ts, np.arange(0, len(sig)), sig)
+        if cfg.final_sigmas_type == "sigma_min":
+            sigma_last = float(((1 - self.alphas_cumprod[0]) / self.alphas_cumprod[0]) ** 0.5)
+        else:
+            sigma_last = 0.0
+        self.sigmas = torch.from_numpy(np.concatenate([sig, [sigma_last]]).astype(np.float32))
+        self.timesteps = torch.from_numpy(ts).to(dtype=torch.int64)
+        if device is not None:
+            self.timesteps = self.timesteps.to(device)
+        self.num_inference_steps = len(ts)
+        self._step_index = None
+        self._lower_order_nums = 0
+        self._hist = {}
+
+    @staticmethod
+    def _alpha_sigma(sigma):
+        alpha_t = 1 / ((sigma ** 2 + 1) ** 0.5)
+        return alpha_t, sigma * alpha_t
+
+    def row_order(self, i):
+        """Solver order of step i of the schedule (diffusers' step(): the first step and, under the final-step rules, the last one
+        are first order)."""
+        cfg, N = self.config, len(self.timesteps)
+        if cfg.solver_order == 1 or i == 0:
+            return 1
+        if i == N - 1 and (cfg.euler_at_final or (cfg.lower_order_final and N < 15) or cfg.final_sigmas_type == "zero"):
+            return 1
+        return 2
+
+    def step_coefficients(self, i, order=None):
+        """fp32 row {alpha_s, sig_s, A, B, C, convert, reads_hist, 0} of step i, from diffusers' fp32 scalar torch ops."""
+        order = self.row_order(i) if order is None else order
+        pp = self.config.algorithm_type == "dpmsolver++"
+        alpha_t, sigma_t = self._alpha_sigma(self.sigmas[i + 1])
+        alpha_s0, sigma_s0 = self._alpha_sigma(self.sigmas[i])
+        lambda_t = torch.log(alpha_t) - torch.log(sigma_t)
+        lambda_s0 = torch.log(alpha_s0) - torch.log(sigma_s0)
+        h = lambda_t - lambda_s0
+        if pp:
+            A, Bc = sigma_t / sigma_s0, -(alpha_t * (torch.exp(-h) - 1.0))
+        else:
+            A, Bc = alpha_t / alpha_s0, -(sigma_t * (torch.exp(h) - 1.0))
+        Cc = torch.zeros((), dtype=torch.float32)     # exactly 0 on first-order rows (h is +inf on a final sigma-0 row)
+        if order == 2:
+            alpha_s1, sigma_s1 = self._alpha_sigma(self.sigmas[i - 1])
+            lambda_s1 = torch.log(alpha_s1) - torch.log(sigma_s1)
+            r0 = (lambda_s0 - lambda_s1) / h
+            inv_r0 = 1.0 / r0
+            midpoint = self.config.solver_type == "midpoint"
+            if pp:
+                Cc = (-(0.5 * (alpha_t * (torch.exp(-h) - 1.0))) if midpoint else alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0)) * inv_r0
+            else:
+                Cc = (-(0.5 * (sigma_t * (torch.exp(h) - 1.0))) if midpoint else -(sigma_t * ((torch.exp(h) - 1.0) / h - 1.0))) * inv_r0
+        one, zero = torch.ones((), dtype=torch.float32), torch.zeros((), dtype=torch.float32)
+        return torch.stack([alpha_s0, sigma_s0, A, Bc, Cc, one if pp else zero, one if order == 2 else zero, zero]).float()
+
+    def coefficient_table(self):
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() first")
+        return torch.stack([self.step_coefficients(i) for i in range(len(self.timesteps))])
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def _init_step_index(self, timestep):
+        t = int(timestep)
+        cand = (self.timesteps.cpu() == t).nonzero()
+        if len(cand) == 0:
+            self._step_index = len(self.timesteps) - 1
+        else:
+            self._step_index = int(cand[1 if len(cand) > 1 else 0])
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, **kw):
+        """x at the next timestep from eps via the device kernel (aldm_dpm_step_fused, eager mode); fp32 tensors of any layout.
+        The previous step's converted output stays on the device, one history tensor per sample shape."""
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() first")
+        dev = sample.device
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        i = self._step_index
+        order = self.row_order(i) if self._lower_order_nums >= 1 else 1
+        x = sample.detach().float().contiguous().clone()
+        key = (tuple(x.shape), dev)
+        hist = self._hist.get(key)
+        if hist is None:
+            if order == 2:
+                raise ValueError(f"step(): no previous model output for a sample of shape {tuple(x.shape)}")
+            hist = self._hist[key] = torch.empty_like(x)
+        coef = self.step_coefficients(i, order).view(1, 8).to(dev)
+        idx = self._dev.setdefault(("zero", dev), torch.zeros(1, dtype=torch.int32, device=dev))
+        ops.dpm_step_fused(model_output.detach().float().contiguous(), x, False, 0.0, coef, idx, None, hist)
+        if self._lower_order_nums < self.config.solver_order:
+            self._lower_order_nums += 1
+        self._step_index += 1
+        prev = x.to(sample.dtype)
+        if not return_dict:
+            return (prev,)
+        return SimpleNamespace(prev_sample=prev)

@@ -6,6 +6,7 @@ names (`base_model.model.<path>.lora_{A,B}.default.weight`, strict=False as in t
 writes a wav.  LoRA stays un-merged and is applied inside the fused projection GEMMs (reference quirk Q4).
 Defaults follow the script: r=2, 50 DDIM steps, 10 s, guidance 5.0; alpha defaults to the TRAINED value 2 rather than the
 script's inconsistent 4 (quirk Q3) -- pass --lora-alpha 4 to reproduce the script literally.
+`--scheduler dpmsolver++ --steps 25` swaps in DPMSolverMultistepScheduler (from the checkpoint's scheduler config) instead of DDIM.
 """
 import argparse
 import os
@@ -15,6 +16,7 @@ import torch
 
 from ..lora import LoraConfig, get_peft_model
 from ..pipeline import AudioLDMPipeline
+from ..scheduler import DPMSolverMultistepScheduler
 from ..unet import UNet2DConditionModel
 
 
@@ -28,6 +30,10 @@ def main(argv=None):
     ap.add_argument("--target-modules", default="to_q,to_v")
     ap.add_argument("--prompt", default="An instrumental hip-hop track in the subgenre of boom bap")
     ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--scheduler", choices=["ddim", "dpmsolver++", "dpmsolver"], default="ddim",
+                    help="sampler: the reference's DDIM (default) or diffusers' DPMSolverMultistepScheduler from the same config "
+                         "(dpmsolver uses final_sigmas_type='sigma_min')")
+    ap.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="DPM-Solver order (ignored with --scheduler ddim)")
     ap.add_argument("--audio-length", type=float, default=10.0)
     ap.add_argument("--guidance-scale", type=float, default=5.0)
     ap.add_argument("--output", default="./generated_audio_LoRA/ex.wav")
@@ -43,6 +49,10 @@ def main(argv=None):
             from safetensors.torch import load_file
             unet_lora.load_state_dict(load_file(args.lora_weights), strict=False)
     pipe = AudioLDMPipeline.from_pretrained(args.model_dir, unet=unet).to(device)
+    if args.scheduler != "ddim":
+        extra = {"final_sigmas_type": "sigma_min"} if args.scheduler == "dpmsolver" else {}
+        pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, algorithm_type=args.scheduler,
+                                                                 solver_order=args.solver_order, **extra)
     generator = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
     audio = pipe(prompt=args.prompt, num_inference_steps=args.steps, audio_length_in_s=args.audio_length,
                  guidance_scale=args.guidance_scale, generator=generator).audios[0]

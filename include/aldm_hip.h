@@ -372,6 +372,17 @@ int aldm_cfg_ddim_step(const float* eps, float* x, int B, long long n_per_sample
 int aldm_ddim_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
                          int* step_idx, void* x_in_bf16, const float* table, long long row_elems, float* rowbias,
                          const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream);
+/* classifier-free guidance + DPM-Solver / DPM-Solver++ multistep update (first or second order), the loop body of
+   AudioLDMPipeline.__call__ with diffusers' DPMSolverMultistepScheduler swapped in, elementwise over channels-last fp32 latents:
+     e  = eps_u + g (eps_t - eps_u)                        (cfg != 0; eps holds [uncond | text] halves)
+     m0 = convert ? (x - sig_s e) / alpha_s : e            (dpmsolver++: the x0 prediction; dpmsolver: eps)
+     x' = A x + B m0 + C (m0 - m1) ;  m1 = hist (read only where reads_hist != 0) ;  hist = m0
+   coef: device fp32 table [n_steps][8] = {alpha_s, sig_s, A, B, C, convert, reads_hist, 0}, the row selected ON DEVICE by
+   step_idx[0].  hist fp32 [B][n] is read (second-order rows) and then overwritten with m0.  Counter, next time-embedding row
+   and ticket as in aldm_ddim_step_fused; ticket == NULL leaves step_idx alone (eager step: table NULL, timesteps/t_out unused). */
+int aldm_dpm_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                        int* step_idx, void* x_in_bf16, float* hist, const float* table, long long row_elems, float* rowbias,
+                        const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream);
 /* measurement aid: keeps `stream` busy for ~us microseconds so that later launches queue up behind it (bench.py) */
 int aldm_sleep_us(int us, void* stream);
 /* device-side loop counter for graph replay: step_idx[0] = (step_idx[0] + 1) mod n_steps ; t_out[0] = timesteps[step_idx[0]] */

@@ -1,0 +1,79 @@
+"""Times one real `pipe(...)` call per sampler at config 2 (4 prompts x 10 s, CFG 2.5, rank-4 LoRA, random-init weights), built the
+way bench.py's end-to-end leg builds it: DDIM-200 (the reference app's call), DDIM-25 and DPM-Solver++-25 (second order,
+DPMSolverMultistepScheduler.from_config of the DDIM config).  One pipeline object; the scheduler is swapped between variants.
+
+    python tools/bench_solvers.py [--repeats 3]
+
+Per variant: one warm-up call (engine build + graph capture), then `repeats` timed calls (median) with device synchronisation
+around the host clock; `ms_per_step` times the engine's graph replays alone (DenoiseEngine.run after set_latents), divided by N.
+Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from bench import build_unet, synth_inputs  # noqa: E402
+
+
+def timed(fn, repeats):
+    out = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    out.sort()
+    return out[len(out) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=3)
+    args = ap.parse_args()
+    from audioldm_with_lora_amd.pipeline import AudioLDMPipeline
+    from audioldm_with_lora_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler
+    from audioldm_with_lora_amd.vae import AutoencoderKL
+    from audioldm_with_lora_amd.vocoder import SpeechT5HifiGan
+    batch, seconds, guidance = 4, 10.0, 2.5
+    unet, _ = build_unet(4)
+    torch.manual_seed(99)
+    pipe = AudioLDMPipeline(AutoencoderKL(), None, None, unet, DDIMScheduler(), SpeechT5HifiGan())
+    pipe.device = torch.device("cuda")
+    pipe.vae.cuda(); pipe.vocoder.cuda()                 # (the UNet is already on the device: keep its packed plan)
+    h = int(seconds * 100) // 4
+    lat, pe, ne = synth_inputs(batch, h, 16)
+    ddim_cfg = pipe.scheduler.config
+    variants = [("ddim_200", DDIMScheduler.from_config(ddim_cfg), 200),
+                ("ddim_25", DDIMScheduler.from_config(ddim_cfg), 25),
+                ("dpmsolver++_25", DPMSolverMultistepScheduler.from_config(ddim_cfg), 25)]
+    res = {}
+    for name, sched, n in variants:
+        pipe.scheduler = sched
+        call = dict(prompt_embeds=pe, negative_prompt_embeds=ne, audio_length_in_s=seconds, num_inference_steps=n,
+                    guidance_scale=guidance)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        audio = pipe(latents=lat.clone(), **call).audios
+        torch.cuda.synchronize()
+        first = (time.perf_counter() - t0) * 1e3
+        assert audio.shape == (batch, int(seconds * 16000)) and bool((audio == audio).all())
+        call_ms = timed(lambda: pipe(latents=lat.clone(), **call), args.repeats)
+        eng = pipe.engine(batch, h, 16, n, guidance)
+        eng.set_latents(lat.cuda())
+        run_ms = timed(eng.run, args.repeats)
+        res[name] = {"steps": n, "ms_per_call": round(call_ms, 1), "ms_per_step": round(run_ms / n, 4),
+                     "first_call_ms_incl_capture": round(first, 1)}
+    print(json.dumps({"what": "AudioLDMPipeline.__call__ at config 2 (4 x 10 s, CFG 2.5, rank-4 LoRA, random-init weights) per sampler; "
+                              "ms_per_step = graph replays only",
+                      "variants": res}))
+
+
+if __name__ == "__main__":
+    main()
