@@ -1,0 +1,65 @@
+"""CLAP score + KAD of a folder of generated clips against a folder of reference clips -- what the reference's
+script/inference/inference.py sets out to do (the shipped file does not parse).
+
+Reads every *.wav of --gen-dir / --ref-dir with scipy.io.wavfile (the 16 kHz float32 files script/inference.py writes;
+int PCM is scaled to [-1, 1], stereo is mono-mixed), embeds them with the CLAP model of --clap-dir on the HIP kernels, and
+prints one JSON line: the CLAP score of every generated file against --prompt, their mean, and KAD in the inference.py
+variant (bandwidth 1, no scale).  Clips must be at most 10 s long.
+
+    python -m audioldm_with_lora_amd.script.evaluate --clap-dir clap-htsat-fused --gen-dir out/gen --ref-dir data/ref \
+        --prompt "a calm piano melody"
+"""
+import argparse
+import json
+import os
+
+import numpy as np
+
+
+def load_wav_16k(path):
+    from scipy.io import wavfile
+    sr, x = wavfile.read(path)
+    if sr != 16000:
+        raise ValueError(f"{path}: {sr} Hz (16 kHz files expected)")
+    if np.issubdtype(x.dtype, np.integer):
+        x = x.astype(np.float32) / float(np.iinfo(x.dtype).max + 1)
+    x = np.asarray(x, dtype=np.float32)
+    return x.mean(axis=1) if x.ndim == 2 else x
+
+
+def load_dir(d):
+    names = sorted(f for f in os.listdir(d) if f.lower().endswith(".wav"))
+    if len(names) < 2:
+        raise ValueError(f"{d}: KAD needs at least two .wav files, found {len(names)}")
+    return names, [load_wav_16k(os.path.join(d, n)) for n in names]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clap-dir", required=True, help="local laion/clap-htsat-* directory (config.json, model.safetensors)")
+    ap.add_argument("--gen-dir", required=True)
+    ap.add_argument("--ref-dir", required=True)
+    ap.add_argument("--prompt", required=True, help="text, or comma-separated token ids when the directory has no tokenizer")
+    ap.add_argument("--batch", type=int, default=8)
+    args = ap.parse_args(argv)
+    import torch
+    from ..clap_audio import ClapModel
+    from ..metrics import embed_audio, embed_text, kernel_audio_distance
+    clap = ClapModel.from_pretrained(args.clap_dir).to("cuda")
+    gen_names, gen = load_dir(args.gen_dir)
+    _, ref = load_dir(args.ref_dir)
+    text = args.prompt
+    if clap.tokenizer is None:
+        text = torch.tensor([int(t) for t in args.prompt.split(",")])
+    g = embed_audio(gen, clap, batch=args.batch)
+    r = embed_audio(ref, clap, batch=args.batch)
+    t = embed_text(text, clap)
+    scores = (g @ t[0] + 1.0) / 2.0
+    res = {"clap_score": {n: float(s) for n, s in zip(gen_names, scores)}, "clap_score_mean": float(scores.mean()),
+           "kad": kernel_audio_distance(g, r, bandwidth=1.0), "n_gen": len(gen), "n_ref": len(ref)}
+    print(json.dumps(res))
+    return res
+
+
+if __name__ == "__main__":
+    main()

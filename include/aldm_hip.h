@@ -462,6 +462,47 @@ int aldm_adamw_flat(float* p, const float* g, float* m, float* v, long long n, f
 int aldm_log_mel(const float* wav, int B, int T, int n_fft, int hop, const float* window, const float* mel_basis,
                  const int* mel_range, int n_mels, int target_frames, float clamp_min, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CLAP audio tower (transformers' ClapAudioModelWithProjection, HTSAT-Swin) and its front end
+ * (ClapFeatureExtractor), for the CLAP score / KAD of the reference's log_validation and
+ * inference.py [REF script/train/train_audioldm_lora.py:97-321].  fp32 arithmetic, bf16 rows.
+ * ------------------------------------------------------------------------------------------ */
+/* y[b][n] = sum_j x[b][j] taps[n + (ntaps-1)/2 - 3j] for n < 3 lens[b], else 0 (scipy.signal.resample_poly(x, 3, 1) with
+   its 61 taps: the 16 kHz -> 48 kHz step the reference does with librosa.resample).  x fp32 [B][T_in], y fp32 [B][T_out]. */
+int aldm_resample_up3(const float* x, const int* lens, int B, int T_in, const float* taps, int ntaps, float* y, int T_out,
+                      void* stream);
+/* ClapFeatureExtractor._np_extract_fbank_features over the repeatpad'ed clip: wav fp32 [B][T] holding lens[b] <= max_len
+   samples; np.tile to (max_len / len) copies, zeros to max_len, reflect padding n_fft/2, periodic Hann `window`, |rfft|^2,
+   mel_basis fp32 [n_mels][n_fft/2+1] (non-zero ranges mel_range), 10 log10(max(., 1e-10)).
+   out fp32 [B][1 + max_len/hop][n_mels].  n_fft other than 1024: ALDM_E_UNSUPPORTED. */
+int aldm_clap_log_mel(const float* wav, const int* lens, int B, int T, int max_len, int n_fft, int hop, const float* window,
+                      const float* mel_basis, const int* mel_range, int n_mels, float* out, void* stream);
+/* ClapAudioEncoder input stage: eval batch_norm over the mel bins (bn_scale / bn_shift fp32 [n_mels]) + bicubic align_corners
+   resize of T frames to 1024 + reshape_mel2img, as the im2col rows of the patch embedding:
+   g bf16 [B][64][64][16] from channel 0 (patch_embed.proj, 4 x 4 / stride 4, K = kh*4 + kw),
+   l bf16 [B][64][64][48] from channels 1..3 (mel_conv2d 4 x 12 / stride (4,12); token column c*21 + j, column 63 zero), or NULL.
+   mel fp32 [B][C][T][n_mels] with element strides b_stride / c_stride (c_stride 0: one channel broadcast).
+   n_mels != 64 or T outside 2..1024: ALDM_E_UNSUPPORTED. */
+int aldm_clap_input(const float* mel, long long b_stride, long long c_stride, int B, int T, int n_mels, const float* bn_scale,
+                    const float* bn_shift, void* g, void* l, void* stream);
+/* ClapAudioAFFBlock, non-GEMM parts, over [B][4096][C] bf16 (64 x 64 tokens; the local branch's token column 63 reads as 0):
+   aff_sum_pool: a = h + r and pooled bf16 [B][C] = its token mean;
+   aff_combine:  out = longer[b] ? 2 h f + 2 r (1 - f), f = sigmoid(loc + glob[b]) : h   (loc fp32 [B][4096][C], glob fp32 [B][C]) */
+int aldm_aff_sum_pool(const void* h, const void* r, int B, int C, void* a, void* pooled, void* stream);
+int aldm_aff_combine(const void* h, const void* r, const float* loc, const float* glob, const int* longer, int B, int C, void* out,
+                     void* stream);
+/* Swin (shifted-)window self-attention.  qkv bf16 [B][H][W][ld] token-major (Q | K | V, each heads*head_dim wide); the
+   cyclic roll by -shift, window partition, window reverse and roll by +shift are folded into the addressing.  Scores
+   scale * q.k + bias[head][i][j] (fp32 [heads][64][64]) + transformers' -100 where the shift regions differ; fp32 softmax;
+   out bf16 [B][H][W][ld_out] token-major, column head*head_dim + d.
+   head_dim != 24, window != 8, H or W not multiples of 8: ALDM_E_UNSUPPORTED. */
+int aldm_window_attention(const void* qkv, int ld, int B, int H, int W, int heads, int head_dim, int window, int shift,
+                          const float* bias, float scale, void* out, int ld_out, void* stream);
+/* ClapAudioPatchMerging gather: x bf16 [B][H][W][C] -> out bf16 [B][H/2][W/2][4C] = [x(2i,2j) | x(2i+1,2j) | x(2i,2j+1) | x(2i+1,2j+1)] */
+int aldm_patch_merge_gather(const void* x, int B, int H, int W, int C, void* out, void* stream);
+/* mean over the N tokens of x bf16 [B][N][C] -> out_f32 fp32 [B][C] and out_bf16 bf16 [B][C] */
+int aldm_token_mean(const void* x, int B, int N, int C, float* out_f32, void* out_bf16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,97 @@
+"""Deterministic weights and test audio for the CLAP audio tower tests (no transformers import).
+
+`audio_state_dict(cfg, seed)` fills every entry of a transformers-named ClapAudioModelWithProjection state dict from one
+numpy RandomState: linear / conv weights ~ N(0, 1 / fan_in), biases ~ N(0, 0.02), LayerNorm gains ~ 1 + N(0, 0.1),
+BatchNorms with sane running statistics (the input BatchNorm is centred on a log-mel in dB), relative-position tables
+~ N(0, 0.5).  The key list comes from the product's own parameter containers, so a fixture regenerated from the seed and
+the module under test agree name for name; tests/golden/make_golden_clap_audio.py loads the same dict into transformers
+with strict=True, which pins the names against the real implementation.
+"""
+import numpy as np
+import torch
+
+FUSED = dict(enable_fusion=True, fusion_type="aff_2d")
+UNFUSED = dict(enable_fusion=False, fusion_type=None)
+NARROW = dict(enable_fusion=True, fusion_type="aff_2d", patch_embeds_hidden_size=48, num_attention_heads=[2, 4, 8, 16],
+              hidden_size=384)
+CONFIGS = {"fused": FUSED, "unfused": UNFUSED, "narrow": NARROW}
+TEXT = dict(vocab_size=200, hidden_size=64, num_hidden_layers=2, num_attention_heads=4, intermediate_size=128,
+            max_position_embeddings=40, type_vocab_size=1, pad_token_id=1, layer_norm_eps=1e-12, projection_dim=512)
+PROMPT_IDS = [0, 17, 45, 99, 3, 150, 2]
+CLIP_SECONDS = [4.0, 10.0, 2.5, 7.0]
+SEEDS = {"fused": 11, "unfused": 12, "narrow": 13, "text": 14}
+
+
+def _fill(template, seed, bn_input=None):
+    rng = np.random.RandomState(seed)
+    bn = {k[:-len("running_mean")] for k in template if k.endswith("running_mean")}
+    out = {}
+    for k in sorted(template):
+        t = template[k]
+        shape = tuple(t.shape)
+        pre = k[:k.rfind(".") + 1]
+        if k.endswith("relative_position_index") or k.endswith("position_ids") or k.endswith("token_type_ids"):
+            out[k] = t.clone()
+        elif k.endswith("num_batches_tracked"):
+            out[k] = torch.zeros((), dtype=torch.long)
+        elif pre in bn:
+            is_in = pre == bn_input
+            if k.endswith("running_mean"):
+                v = (-35.0 + 5.0 * rng.randn(*shape)) if is_in else 0.1 * rng.randn(*shape)
+            elif k.endswith("running_var"):
+                v = (100.0 if is_in else 1.0) * rng.uniform(0.5, 1.5, shape)
+            elif k.endswith("weight"):
+                v = 1.0 + 0.1 * rng.randn(*shape)
+            else:
+                v = 0.05 * rng.randn(*shape)
+            out[k] = torch.tensor(v, dtype=torch.float32)
+        elif k.endswith("relative_position_bias_table"):
+            out[k] = torch.tensor(0.5 * rng.randn(*shape), dtype=torch.float32)
+        elif k.endswith("logit_scale_a") or k.endswith("logit_scale_t"):
+            out[k] = torch.tensor(np.log(1 / 0.07), dtype=torch.float32)
+        elif len(shape) == 1 and k.endswith("weight"):                     # LayerNorm gain
+            out[k] = torch.tensor(1.0 + 0.1 * rng.randn(*shape), dtype=torch.float32)
+        elif k.endswith("bias"):
+            out[k] = torch.tensor(0.02 * rng.randn(*shape), dtype=torch.float32)
+        elif "embeddings" in k:
+            out[k] = torch.tensor(rng.randn(*shape), dtype=torch.float32)
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            out[k] = torch.tensor(rng.randn(*shape) / np.sqrt(fan_in), dtype=torch.float32)
+    return out
+
+
+def audio_config(name):
+    return dict(CONFIGS[name])
+
+
+def audio_state_dict(name):
+    """transformers-named state dict (audio_model.* / audio_projection.*) of config `name`, from SEEDS[name]."""
+    from audioldm_with_lora_amd.clap_audio import ClapAudioModelWithProjection
+    tmpl = ClapAudioModelWithProjection(**CONFIGS[name]).state_dict()
+    return _fill(tmpl, SEEDS[name], bn_input="audio_model.audio_encoder.batch_norm.")
+
+
+def text_state_dict():
+    """transformers-named ClapTextModelWithProjection state dict of TEXT (position_ids / token_type_ids buffers included)."""
+    from audioldm_with_lora_amd.clap_text import ClapTextModelWithProjection
+    tmpl = dict(ClapTextModelWithProjection(**TEXT).state_dict())
+    n = TEXT["max_position_embeddings"]
+    tmpl["text_model.embeddings.position_ids"] = torch.arange(n)[None]
+    tmpl["text_model.embeddings.token_type_ids"] = torch.zeros(1, n, dtype=torch.long)
+    return _fill(tmpl, SEEDS["text"])
+
+
+def wave16k(seconds, seed):
+    """Seeded test clip at 16 kHz: three sines (110 - 3000 Hz, amplitude 0.05 - 0.3) plus N(0, 0.02) noise, float32."""
+    rng = np.random.RandomState(1000 + seed)
+    n = int(round(seconds * 16000))
+    t = np.arange(n) / 16000.0
+    x = 0.02 * rng.randn(n)
+    for _ in range(3):
+        x += rng.uniform(0.05, 0.3) * np.sin(2 * np.pi * rng.uniform(110, 3000) * t + rng.uniform(0, 2 * np.pi))
+    return x.astype(np.float32)
+
+
+def clips16k():
+    return [wave16k(s, i) for i, s in enumerate(CLIP_SECONDS)]
