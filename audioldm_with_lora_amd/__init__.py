@@ -2,6 +2,14 @@
 
 Drop-in surface for the reference's entry points:
 AudioLDMPipeline / UNet2DConditionModel / AutoencoderKL / SpeechT5HifiGan / DDIMScheduler / DPMSolverMultistepScheduler
-(both in scheduler.py) and the peft-shaped LoraConfig / get_peft_model helpers.  No CPU fallback: ops raise if libaldm_hip.so is missing.
+(both in scheduler.py) and the peft-shaped LoraConfig / get_peft_model helpers; AudioLDMAudioToAudioPipeline (audio2audio.py,
+exported here on first use) starts from a recording.  No CPU fallback: ops raise if libaldm_hip.so is missing.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    if name == "AudioLDMAudioToAudioPipeline":
+        from .audio2audio import AudioLDMAudioToAudioPipeline
+        return AudioLDMAudioToAudioPipeline
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,169 @@
+"""Text-guided audio-to-audio on the MI355X HIP path: style transfer, inpainting and band regeneration.
+
+`AudioLDMAudioToAudioPipeline.from_pipe(pipe)(prompt, audio=wav, strength=0.5)` partly noises the encoded clip and denoises it
+toward the prompt over the suffix timesteps[begin:] of the schedule (diffusers' get_timesteps rule).  With `mask=` the loop is
+diffusers' legacy inpaint loop: after every step the known latents, noised to the next timestep, are blended back in where the mask
+keeps them, inside the fused step launch (aldm_{ddim,dpm}_step_fused_masked), so the loop stays one captured graph.
+
+    x0 = scaling_factor * vae.encode(log_mel(audio)).latent_dist.sample()
+    x  = a_begin x0 + s_begin eps                         (x = eps exactly at strength 1)
+    for k, t in enumerate(timesteps[begin:]):  x = step(unet(x, t), t, x);  x = (1 - m) (a_k x0 + s_k eps) + m x
+"""
+import numpy as np
+import torch
+
+from . import ops
+from .engine import DenoiseEngine
+from .mel import LogMelFrontEnd
+from .pipeline import AudioLDMPipeline, AudioPipelineOutput, _frozen_config
+
+HOP_SECONDS = 0.01        # one mel frame per 160 samples at 16 kHz
+
+
+def regeneration_mask(height, n_mel, seconds=None, bands=None):
+    """Rectangular mask [height, n_mel] fp32 at mel resolution, 1 = regenerate.  `seconds=(t0, t1)` marks the frames that overlap
+    [t0, t1) at a 10 ms hop (all frames when None); `bands=(f0, f1)` marks the mel bins that overlap the fraction [f0, f1) of the bins
+    (all bins when None), so bands=(0.5, 1.0) regenerates the upper half (band-limited super-resolution)."""
+    m = torch.zeros(height, n_mel, dtype=torch.float32)
+    r0, r1 = 0, height
+    if seconds is not None:
+        t0, t1 = (float(v) for v in seconds)
+        if not 0.0 <= t0 < t1:
+            raise ValueError(f"seconds=(t0, t1) needs 0 <= t0 < t1, got {seconds}")
+        r0 = min(int(np.floor(t0 / HOP_SECONDS + 1e-6)), height)
+        r1 = min(int(np.ceil(t1 / HOP_SECONDS - 1e-6)), height)
+    c0, c1 = 0, n_mel
+    if bands is not None:
+        f0, f1 = (float(v) for v in bands)
+        if not 0.0 <= f0 < f1 <= 1.0:
+            raise ValueError(f"bands=(f0, f1) needs 0 <= f0 < f1 <= 1, got {bands}")
+        c0 = int(np.floor(f0 * n_mel + 1e-6))
+        c1 = int(np.ceil(f1 * n_mel - 1e-6))
+    m[r0:r1, c0:c1] = 1.0
+    return m
+
+
+def reduce_mask(mask, factor):
+    """[B, H, W] mel-resolution mask -> [B, H / factor, W / factor] latent-resolution mask: the max over each factor x factor cell, so
+    every latent pixel that touches a regenerated mel cell is regenerated.  Host-side (a few kB, once per call)."""
+    mask = torch.as_tensor(mask, dtype=torch.float32).cpu()
+    if mask.dim() != 3 or mask.shape[1] % factor or mask.shape[2] % factor:
+        raise ValueError(f"mask [B, H, W] with H, W multiples of {factor} expected, got {tuple(mask.shape)}")
+    return torch.nn.functional.max_pool2d(mask[:, None], factor)[:, 0].contiguous()
+
+
+class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
+    """AudioLDMPipeline that starts from a recording: style transfer (`strength`), inpainting / band regeneration (`mask`)."""
+
+    @classmethod
+    def from_pipe(cls, pipe):
+        """shares pipe's modules (and its device); keeps an engine cache of its own"""
+        new = cls(pipe.vae, pipe.text_encoder, pipe.tokenizer, pipe.unet, pipe.scheduler, pipe.vocoder)
+        new.device = pipe.device
+        return new
+
+    def engine(self, batch, h, w, steps, guidance, begin_index=0, masked=False):
+        key = (batch, h, w, steps, float(guidance), type(self.scheduler).__name__, _frozen_config(self.scheduler), int(begin_index),
+               bool(masked))
+        eng = self._engines.get(key)
+        if eng is not None and (eng.unet is not self._unet or eng.scheduler is not self.scheduler or eng.stale()):
+            eng = None
+        if eng is None:
+            eng = self._engines[key] = DenoiseEngine(self._unet, self.scheduler, batch, h, w, steps, guidance, device=self.device,
+                                                     begin_index=begin_index, masked=masked)
+        return eng
+
+    def _audio_batch(self, audio, batch, per_prompt):
+        a = torch.as_tensor(np.asarray(audio, dtype=np.float32)) if not torch.is_tensor(audio) else audio.detach().float()
+        if a.dim() == 1:
+            a = a[None].expand(batch, -1)
+        elif a.dim() == 2:
+            if a.shape[0] * per_prompt == batch and per_prompt > 1:
+                a = a.repeat_interleave(per_prompt, dim=0)
+            elif a.shape[0] != batch:
+                raise ValueError(f"audio batch {a.shape[0]} does not match {batch // per_prompt} prompt(s)")
+        else:
+            raise ValueError(f"audio must be [T] or [B, T], got {tuple(a.shape)}")
+        if a.shape[-1] == 0:
+            raise ValueError("empty audio")
+        return a.contiguous()
+
+    def _latent_mask(self, mask, batch, per_prompt, height, n_mel):
+        """the batching rule of _audio_batch: [frames, n_mel] is shared by every sample, [prompts, frames, n_mel] is repeated for
+        each of a prompt's num_waveforms_per_prompt samples, [batch, frames, n_mel] is taken as is"""
+        m = torch.as_tensor(mask, dtype=torch.float32).cpu()
+        if m.dim() not in (2, 3) or tuple(m.shape[-2:]) != (height, n_mel):
+            raise ValueError(f"mask must be [{height}, {n_mel}] or [B, {height}, {n_mel}] at mel resolution, got {tuple(m.shape)}")
+        if m.dim() == 2:
+            m = m[None].expand(batch, -1, -1)
+        elif m.shape[0] * per_prompt == batch and per_prompt > 1:
+            m = m.repeat_interleave(per_prompt, dim=0)
+        elif m.shape[0] != batch:
+            raise ValueError(f"mask batch {m.shape[0]} does not match {batch // per_prompt} prompt(s)")
+        return reduce_mask(m.contiguous(), self.vae_scale_factor)
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, audio=None, sampling_rate=16000, strength=0.5, mask=None, audio_length_in_s=None,
+                 num_inference_steps=50, guidance_scale=2.5, negative_prompt=None, num_waveforms_per_prompt=1, generator=None,
+                 latents=None, prompt_embeds=None, negative_prompt_embeds=None, return_dict=True, output_type="np"):
+        if self.device.type != "cuda":
+            raise ops._lib.AldmError("AudioLDMAudioToAudioPipeline runs on the MI355X only: call .to('cuda') (no CPU fallback)")
+        if audio is None:
+            raise ValueError("pass audio= (the recording to start from)")
+        if output_type not in ("np", "pt", "latent"):
+            raise ValueError(f"output_type must be 'np', 'pt' or 'latent', got {output_type!r}")
+        vc = self.vocoder.config
+        if int(sampling_rate) != int(vc.sampling_rate):
+            raise ValueError(f"audio at {sampling_rate} Hz: the vocoder runs at {vc.sampling_rate} Hz and there is no resampler here")
+        _, begin = self.scheduler.get_timesteps(num_inference_steps, strength)    # raises on a strength that leaves no step
+        prompt_embeds, negative_prompt_embeds = self._prompt_embeds(prompt, prompt_embeds, negative_prompt, negative_prompt_embeds,
+                                                                    guidance_scale, num_waveforms_per_prompt)
+        batch = prompt_embeds.shape[0]
+        wav = self._audio_batch(audio, batch, num_waveforms_per_prompt)
+        if audio_length_in_s is None:
+            audio_length_in_s = wav.shape[-1] / float(vc.sampling_rate)
+        height, n_samples = self.geometry(audio_length_in_s)
+        n_mel = vc.model_in_dim
+        h, w = height // self.vae_scale_factor, n_mel // self.vae_scale_factor
+        shape = (batch, self._unet.cfg["in_channels"], h, w)
+        m_lat = self._latent_mask(mask, batch, num_waveforms_per_prompt, height, n_mel) if mask is not None else None
+        if latents is not None and tuple(latents.shape) != shape:
+            raise ValueError(f"Unexpected latents shape, got {tuple(latents.shape)}, expected {shape}")
+
+        # encode: log-mel front end (pads / crops to `height` frames) -> VAE moments -> posterior sample
+        mel = LogMelFrontEnd(device=self.device, target_length=height, n_mel=n_mel)(wav.to(self.device))
+        dist = self.vae.encode(mel).latent_dist
+        if tuple(dist.mean.shape) != shape:
+            raise ValueError(f"the VAE encodes to {tuple(dist.mean.shape)}, the UNet expects {shape}")
+        # random draws, in this order, on the generator's device: the posterior noise, then eps (unless latents= gives it)
+        gdev = generator.device if generator is not None else torch.device("cpu")
+        post = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32)
+        if latents is None:
+            latents = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32)
+        eps = latents.to(self.device, torch.float32).contiguous()
+        x0 = ops.gaussian_sample(dist.parameters.float(), post.to(self.device)) * self.vae.config.scaling_factor
+        if float(strength) == 1.0:
+            x = eps                                                   # diffusers' is_strength_max: pure noise, not a * x0 + s * eps
+        else:
+            a, s = self.scheduler.add_noise_coefficients(begin)
+            coef = torch.tensor([float(a), float(s)], dtype=torch.float32).repeat(batch).to(self.device)
+            x = ops.add_noise(x0, eps, coef)
+
+        eng = self.engine(batch, h, w, num_inference_steps, guidance_scale, begin_index=begin, masked=m_lat is not None)
+        eng.set_condition(prompt_embeds, negative_prompt_embeds)
+        eng.set_latents(x)
+        if m_lat is not None:
+            eng.set_inpaint(x0, eps, m_lat)
+        if eng.graph is None and eng.use_graph:
+            eng.capture()
+        eng.run()
+        if output_type == "latent":
+            out = eng.latents_nchw()
+        else:
+            wav_out, _ = self.decode_latents_nhwc(eng.x)
+            out = wav_out[:, :n_samples]
+            if output_type == "np":
+                out = out.float().cpu().numpy()
+        if not return_dict:
+            return (out,)
+        return AudioPipelineOutput(audios=out)

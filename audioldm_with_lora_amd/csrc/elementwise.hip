@@ -80,24 +80,45 @@ __global__ void cfg_ddim_step_kernel(const float* __restrict__ eps, float* __res
   }
 }
 
+// Inpainting / audio-to-audio blend of the masked step kernels (diffusers' legacy inpaint loop): after the scheduler update xn, the
+// known latents are noised to the level of the NEXT timestep with the row (a, s) = blend[step_idx[0]] and put back where the mask
+// keeps them:   known = a x0 + s noise ;  x' = (1 - m) known + m xn      (m = mask[pixel], broadcast over channels; 1 = regenerate)
+// Exact at the ends: m == 1 gives xn, m == 0 gives known, and the last row (1, 0) gives known == x0 (each term is an exact product
+// or an exact zero added once).
+struct Inpaint {
+  const float* x0;       // [B][h][w][C] fp32: the encoded clip times scaling_factor
+  const float* noise;    // [B][h][w][C] fp32: the eps the loop started from
+  const float* mask;     // [B][h][w] fp32
+  const float* blend;    // [n_steps][2] fp32 rows (a, s)
+  int C;
+};
+
+__device__ __forceinline__ float inpaint_blend(float xn, float x0, float nz, float m, float a, float s) {
+  const float known = fmaf(s, nz, a * x0);
+  return fmaf(m, xn, (1.f - m) * known);
+}
+
 // The whole per-step bookkeeping of the replayed DDIM loop as ONE launch behind the UNet: classifier-free guidance + DDIM update
 // (as cfg_ddim_step_kernel), the NEXT step's row of the precomputed time-embedding table gathered into `rowbias`, and the
 // device-side step counter advanced.  Every workgroup reads the counter when it starts; the one that finishes LAST (an
 // agent-scope ticket) writes the new value, so no workgroup can see the counter move under it -- three launches become one.
 // VEC elements per thread (4 when B * n % 4 == 0): a quarter of the workgroups means a quarter of the same-address ticket atomics,
 // which were most of this launch's 8.4 us (500 workgroups at one thread per element).
-template <int VEC>
-__global__ __launch_bounds__(256) void ddim_step_fused_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
-                                                              float g, const float* __restrict__ coef, int* __restrict__ step_idx,
-                                                              bf16* __restrict__ x_in, const float* __restrict__ table, long long row_elems,
-                                                              float* __restrict__ rowbias, const float* __restrict__ timesteps, int n_steps,
-                                                              float* __restrict__ t_out, unsigned* __restrict__ ticket) {
+// The body is shared with ddim_step_fused_masked_kernel (MASKED = true: the inpainting blend after the update, see inpaint_blend);
+// this kernel instantiates MASKED = false and keeps its own parameter list and arithmetic: its results are what they were before the
+// blend (bench.py's dumped latents are bit-identical).  The disassembly is not identical: one scalar load and one wait are in a
+// different order, and the operands of one (commutative) multiply are swapped.
+template <int VEC, bool MASKED>
+__device__ __forceinline__ void ddim_step_fused_body(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg, float g,
+                                                     const float* __restrict__ coef, int* __restrict__ step_idx, bf16* __restrict__ x_in,
+                                                     const float* __restrict__ table, long long row_elems, float* __restrict__ rowbias,
+                                                     const float* __restrict__ timesteps, int n_steps, float* __restrict__ t_out,
+                                                     unsigned* __restrict__ ticket, long long tix, const Inpaint& ip) {
   typedef float fvec __attribute__((ext_vector_type(VEC)));
   typedef bf16 bvec __attribute__((ext_vector_type(VEC)));
   const int cur = step_idx[0];
   int nxt = cur + 1;
   if (nxt >= n_steps) nxt = 0;                                // wrap: a replayed graph may run past the schedule (benchmarks)
-  const long long tix = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long idx = tix * VEC;
   const long long total = (long long)B * n;
   if (idx < total) {
@@ -105,13 +126,20 @@ __global__ __launch_bounds__(256) void ddim_step_fused_kernel(const float* __res
     fvec eu = *reinterpret_cast<const fvec*>(eps + idx), et = eu;
     if (cfg) et = *reinterpret_cast<const fvec*>(eps + total + idx);
     const fvec xv = *reinterpret_cast<const fvec*>(x + idx);
+    fvec kx0, knz;
+    if constexpr (MASKED) {
+      kx0 = *reinterpret_cast<const fvec*>(ip.x0 + idx);
+      knz = *reinterpret_cast<const fvec*>(ip.noise + idx);
+    }
     const float* cf = coef + 4 * cur;
     const float sa = cf[0], sb = cf[1], sap = cf[2], sbp = cf[3];
     fvec xn;
     bvec xb;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-      const float r = ddim_update(eu[k], et[k], xv[k], cfg, g, sa, sb, sap, sbp);
+      float r = ddim_update(eu[k], et[k], xv[k], cfg, g, sa, sb, sap, sbp);
+      if constexpr (MASKED)
+        r = inpaint_blend(r, kx0[k], knz[k], ip.mask[(unsigned)(idx + k) / (unsigned)ip.C], ip.blend[2 * cur], ip.blend[2 * cur + 1]);
       xn[k] = r;
       xb[k] = (bf16)r;
     }
@@ -136,6 +164,28 @@ __global__ __launch_bounds__(256) void ddim_step_fused_kernel(const float* __res
   }
 }
 
+template <int VEC>
+__global__ __launch_bounds__(256) void ddim_step_fused_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
+                                                              float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                              bf16* __restrict__ x_in, const float* __restrict__ table, long long row_elems,
+                                                              float* __restrict__ rowbias, const float* __restrict__ timesteps, int n_steps,
+                                                              float* __restrict__ t_out, unsigned* __restrict__ ticket) {
+  ddim_step_fused_body<VEC, false>(eps, x, B, n, cfg, g, coef, step_idx, x_in, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                                   (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void ddim_step_fused_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                     int cfg, float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                                     bf16* __restrict__ x_in, const float* __restrict__ table, long long row_elems,
+                                                                     float* __restrict__ rowbias, const float* __restrict__ timesteps, int n_steps,
+                                                                     float* __restrict__ t_out, unsigned* __restrict__ ticket,
+                                                                     const float* __restrict__ x0, const float* __restrict__ noise,
+                                                                     const float* __restrict__ mask, const float* __restrict__ blend, int C) {
+  ddim_step_fused_body<VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                                  (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
+}
+
 // guidance + DPM-Solver(++) multistep update of one element from a coefficient row {alpha_s, sig_s, A, B, C, convert, reads_hist, -}
 // (scheduler.py DPMSolverMultistepScheduler.coefficient_table), every fused multiply-add spelled out as in ddim_update:
 //   m0 = convert ? (x - sig_s e) / alpha_s : e ;  x' = A x + B m0 + C (m0 - m1)      (m1 = hist; C == 0 and m1 unread on first-order rows)
@@ -153,24 +203,29 @@ __device__ __forceinline__ float dpm_update(float m0, float m1, float xv, float 
 // with this step's), the bf16 next UNet input, the next step's time-embedding row and the counter advance, as ONE launch.  The
 // counter protocol (every workgroup reads step_idx[0] when it starts, the last one by the agent-scope ticket moves it) is
 // ddim_step_fused_kernel's unchanged.  ticket == NULL: the counter is left alone (eager scheduler.step; table is NULL there too).
-template <int VEC>
-__global__ __launch_bounds__(256) void dpm_step_fused_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
+// The body is shared with dpm_step_fused_masked_kernel in the same way as the DDIM body.
+template <int VEC, bool MASKED>
+__device__ __forceinline__ void dpm_step_fused_body(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
                                                              float g, const float* __restrict__ coef, int* __restrict__ step_idx,
                                                              bf16* __restrict__ x_in, float* __restrict__ hist, const float* __restrict__ table,
                                                              long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
-                                                             int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket) {
+                                                             int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket, long long tix, const Inpaint& ip) {
   typedef float fvec __attribute__((ext_vector_type(VEC)));
   typedef bf16 bvec __attribute__((ext_vector_type(VEC)));
   const int cur = step_idx[0];
   int nxt = cur + 1;
   if (nxt >= n_steps) nxt = 0;                                // wrap: a replayed graph may run past the schedule (benchmarks)
-  const long long tix = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long idx = tix * VEC;
   const long long total = (long long)B * n;
   if (idx < total) {
     fvec eu = *reinterpret_cast<const fvec*>(eps + idx), et = eu;
     if (cfg) et = *reinterpret_cast<const fvec*>(eps + total + idx);
     const fvec xv = *reinterpret_cast<const fvec*>(x + idx);
+    fvec kx0, knz;
+    if constexpr (MASKED) {
+      kx0 = *reinterpret_cast<const fvec*>(ip.x0 + idx);
+      knz = *reinterpret_cast<const fvec*>(ip.noise + idx);
+    }
     const float* cf = coef + 8 * cur;
     const float alpha_s = cf[0], sig_s = cf[1], A = cf[2], Bc = cf[3], Cc = cf[4];
     const bool convert = cf[5] != 0.f, second = cf[6] != 0.f;
@@ -181,7 +236,10 @@ __global__ __launch_bounds__(256) void dpm_step_fused_kernel(const float* __rest
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
       m0[k] = dpm_model_output(eu[k], et[k], xv[k], cfg, g, alpha_s, sig_s, convert);
-      const float r = dpm_update(m0[k], second ? m1[k] : m0[k], xv[k], A, Bc, Cc);
+      float r = dpm_update(m0[k], second ? m1[k] : m0[k], xv[k], A, Bc, Cc);
+      // (the history keeps the unblended m0, as diffusers stores the model output before the caller blends)
+      if constexpr (MASKED)
+        r = inpaint_blend(r, kx0[k], knz[k], ip.mask[(unsigned)(idx + k) / (unsigned)ip.C], ip.blend[2 * cur], ip.blend[2 * cur + 1]);
       xn[k] = r;
       xb[k] = (bf16)r;
     }
@@ -205,6 +263,29 @@ __global__ __launch_bounds__(256) void dpm_step_fused_kernel(const float* __rest
       t_out[0] = timesteps[nxt];
     }
   }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void dpm_step_fused_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
+                                                             float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                             bf16* __restrict__ x_in, float* __restrict__ hist, const float* __restrict__ table,
+                                                             long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                             int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket) {
+  dpm_step_fused_body<VEC, false>(eps, x, B, n, cfg, g, coef, step_idx, x_in, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                                  (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void dpm_step_fused_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                    int cfg, float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                                    bf16* __restrict__ x_in, float* __restrict__ hist, const float* __restrict__ table,
+                                                                    long long row_elems, float* __restrict__ rowbias,
+                                                                    const float* __restrict__ timesteps, int n_steps, float* __restrict__ t_out,
+                                                                    unsigned* __restrict__ ticket, const float* __restrict__ x0,
+                                                                    const float* __restrict__ noise, const float* __restrict__ mask,
+                                                                    const float* __restrict__ blend, int C) {
+  dpm_step_fused_body<VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                                 (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
 }
 
 __global__ void advance_step_kernel(int* step_idx, const float* __restrict__ timesteps, int n_steps, float* t_out) {
@@ -360,6 +441,59 @@ extern "C" int aldm_dpm_step_fused(const float* eps, float* x, int B, long long 
     hipLaunchKernelGGL(dpm_step_fused_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample, cfg,
                        guidance, coef, step_idx, (bf16*)x_in_bf16, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket);
   return aldm_launch_status("dpm_step_fused");
+}
+
+// the masked launches: the same arguments as their unmasked counterparts, then the inpainting operands (Inpaint above).  The mask is
+// indexed by element / C in 32 bits, so B * n_per_sample must stay below 2^31.
+extern "C" int aldm_ddim_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                           int* step_idx, void* x_in_bf16, const float* table, long long row_elems, float* rowbias,
+                                           const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0,
+                                           const float* noise, const float* mask, const float* blend, int channels, void* stream) {
+  ALDM_CHECK_ARG(eps && x && coef && step_idx && timesteps && t_out && ticket && B > 0 && n_per_sample > 0 && n_steps > 0,
+                 "ddim_step_fused_masked: bad args");
+  ALDM_CHECK_ARG(!table || (rowbias && row_elems > 0 && row_elems % 4 == 0), "ddim_step_fused_masked: table needs rowbias and row_elems %% 4 == 0");
+  ALDM_CHECK_ARG(x0 && noise && mask && blend && channels > 0 && n_per_sample % channels == 0 && (long long)B * n_per_sample < (1ll << 31),
+                 "ddim_step_fused_masked: bad inpainting args");
+  if (!table) row_elems = 0;
+  const long long total = (long long)B * n_per_sample;
+  const bool v4 = total % 4 == 0;
+  const long long items = v4 ? total / 4 : total;
+  const long long work = items > row_elems / 4 ? items : row_elems / 4;
+  if (v4)
+    hipLaunchKernelGGL(ddim_step_fused_masked_kernel<4>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
+                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                       x0, noise, mask, blend, channels);
+  else
+    hipLaunchKernelGGL(ddim_step_fused_masked_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
+                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                       x0, noise, mask, blend, channels);
+  return aldm_launch_status("ddim_step_fused_masked");
+}
+
+extern "C" int aldm_dpm_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                          int* step_idx, void* x_in_bf16, float* hist, const float* table, long long row_elems, float* rowbias,
+                                          const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0,
+                                          const float* noise, const float* mask, const float* blend, int channels, void* stream) {
+  ALDM_CHECK_ARG(eps && x && coef && step_idx && hist && B > 0 && n_per_sample > 0 && n_steps > 0, "dpm_step_fused_masked: bad args");
+  ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "dpm_step_fused_masked: the counter advance needs timesteps and t_out");
+  ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
+                 "dpm_step_fused_masked: table needs ticket, rowbias and row_elems %% 4 == 0");
+  ALDM_CHECK_ARG(x0 && noise && mask && blend && channels > 0 && n_per_sample % channels == 0 && (long long)B * n_per_sample < (1ll << 31),
+                 "dpm_step_fused_masked: bad inpainting args");
+  if (!table) row_elems = 0;
+  const long long total = (long long)B * n_per_sample;
+  const bool v4 = total % 4 == 0;
+  const long long items = v4 ? total / 4 : total;
+  const long long work = items > row_elems / 4 ? items : row_elems / 4;
+  if (v4)
+    hipLaunchKernelGGL(dpm_step_fused_masked_kernel<4>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
+                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                       x0, noise, mask, blend, channels);
+  else
+    hipLaunchKernelGGL(dpm_step_fused_masked_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
+                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                       x0, noise, mask, blend, channels);
+  return aldm_launch_status("dpm_step_fused_masked");
 }
 
 extern "C" int aldm_add_noise(const float* x, const float* noise, const float* coef, int B, long long n_per_sample,

@@ -9,6 +9,9 @@ bf16 UNet input, the timestep scalar and a step counter that indexes the precomp
 table -- so ONE captured graph of a single step replays unchanged for all N steps with no host work
 in between.  With a DPMSolverMultistepScheduler the update is the multistep solver's (ops.dpm_step_fused): its coefficient rows
 come from the scheduler in the same way, and the previous step's model output lives in one more device buffer.
+Audio-to-audio and inpainting: `begin_index` runs the suffix timesteps[begin:] of the schedule, and `masked`
+swaps in the masked fused steps, which blend the known latents back in after every update (x0, noise, mask and the blend rows in
+four more device buffers, filled by set_inpaint) -- still one launch behind the UNet, so the loop stays one captured graph.
 """
 import torch
 
@@ -18,7 +21,7 @@ from .scheduler import DPMSolverMultistepScheduler
 
 class DenoiseEngine:
     def __init__(self, unet, scheduler, batch, height, width, num_inference_steps, guidance_scale=2.5,
-                 device="cuda", use_graph=True, chains=None):
+                 device="cuda", use_graph=True, chains=None, begin_index=0, masked=False):
         self.unet, self.scheduler = unet, scheduler
         self.B, self.H, self.W = batch, height, width
         self.C = unet.cfg["in_channels"]
@@ -28,10 +31,16 @@ class DenoiseEngine:
         dev = torch.device(device)
         self.dev = dev
         scheduler.set_timesteps(num_inference_steps)
-        self.n_steps = len(scheduler.timesteps)
         self.dpm = isinstance(scheduler, DPMSolverMultistepScheduler)
-        self.timesteps_f32 = scheduler.timesteps.to(torch.float32).to(dev)
-        self.coef = scheduler.coefficient_table().contiguous().to(dev)
+        self.begin_index, self.masked = int(begin_index), bool(masked)
+        if not 0 <= self.begin_index < len(scheduler.timesteps):
+            raise ValueError(f"begin_index {begin_index} outside the schedule of {len(scheduler.timesteps)} steps")
+        # (the defaults keep the full schedule and the scheduler's own table call, launch for launch)
+        ts = scheduler.timesteps[self.begin_index:] if self.begin_index else scheduler.timesteps
+        self.n_steps = len(ts)
+        self.timesteps_f32 = ts.to(torch.float32).to(dev)
+        coef = scheduler.coefficient_table(begin_index=self.begin_index) if self.begin_index else scheduler.coefficient_table()
+        self.coef = coef.contiguous().to(dev)
         # Optional: independent sub-batches ("chains") captured as parallel branches of the graph (each owns a contiguous
         # slice of the latents and its own CFG-doubled input block [uncond_i | cond_i]).  Measured on MI355X / ROCm 7.2 at
         # batch 4: 1 chain 4.83 ms/step, 2 chains 4.81, 4 chains 5.90 -- the branches do not overlap usefully, so the
@@ -40,6 +49,8 @@ class DenoiseEngine:
             chains = 1
         if chains > 1 and self.dpm:
             raise NotImplementedError("chains > 1 runs the DDIM update only")
+        if chains > 1 and self.masked:
+            raise NotImplementedError("chains > 1 runs the unmasked update only")
         assert batch % chains == 0
         self.chains, self.bc = chains, batch // chains
         nbc = 2 * self.bc if self.cfg else self.bc
@@ -47,6 +58,13 @@ class DenoiseEngine:
         self.x_in = [torch.zeros(nbc, height, width, self.C, dtype=torch.bfloat16, device=dev) for _ in range(chains)]
         # DPM-Solver: the previous step's converted model output (read by second-order rows, never by row 0)
         self.hist = torch.zeros_like(self.x) if self.dpm else None
+        # masked: the known latents (x0 * scaling_factor), the eps the loop started from (both NHWC fp32), the mask [B, h, w] fp32
+        # (1 = regenerate) and the blend rows (a, s) of the suffix [n_steps, 2] -- set_inpaint fills the first three
+        self.x0 = self.noise = self.mask = self.blend = None
+        if self.masked:
+            self.x0, self.noise = torch.zeros_like(self.x), torch.zeros_like(self.x)
+            self.mask = torch.ones(batch, height, width, dtype=torch.float32, device=dev)
+            self.blend = scheduler.blend_table(self.begin_index).contiguous().to(dev)
         self.t_buf = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)      # the fused step's last-workgroup ticket (rests at 0)
@@ -115,6 +133,18 @@ class DenoiseEngine:
             self.hist.zero_()
         self._prime()
 
+    def set_inpaint(self, x0_nchw, noise_nchw, mask):
+        """masked engines: x0 [B, C, H, W] fp32 (the encoded clip times scaling_factor), noise [B, C, H, W] fp32 (the eps the loop
+        started from), mask [B, H, W] (1 = regenerate, 0 = keep; fractional values blend).  Copied into the engine's own buffers, so a
+        captured graph replays with the new values."""
+        if not self.masked:
+            raise ValueError("set_inpaint needs an engine built with masked=True")
+        if tuple(mask.shape) != tuple(self.mask.shape):
+            raise ValueError(f"mask shape {tuple(mask.shape)}, expected {tuple(self.mask.shape)}")
+        self.x0.copy_(ops.nchw_to_nhwc(x0_nchw.to(self.dev, torch.float32).contiguous(), out_f32=True))
+        self.noise.copy_(ops.nchw_to_nhwc(noise_nchw.to(self.dev, torch.float32).contiguous(), out_f32=True))
+        self.mask.copy_(mask.to(self.dev, torch.float32))
+
     def _prime(self):
         """The single-chain step gathers the NEXT step's time-embedding row at its end (ops.ddim_step_fused); the row of the
         step the counter stands at is put in place here, whenever the counter or the table changes outside the graph.  The fused
@@ -133,6 +163,15 @@ class DenoiseEngine:
         if self.chains == 1:
             # one chain: guidance + the scheduler's update, the next step's time-embedding row and the step counter in ONE launch behind the UNet
             eps = self.unet.forward_nhwc(self.x_in[0], self.t_buf, self.cls[0], rowbias=self.rowbias[0])
+            if self.masked:
+                ip = (self.x0, self.noise, self.mask, self.blend)
+                if self.dpm:
+                    ops.dpm_step_fused_masked(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.hist, self.temb[0],
+                                              self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket, *ip)
+                else:
+                    ops.ddim_step_fused_masked(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.temb[0],
+                                               self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket, *ip)
+                return
             if self.dpm:
                 ops.dpm_step_fused(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.hist, self.temb[0],
                                    self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket)

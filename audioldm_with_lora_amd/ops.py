@@ -1162,6 +1162,55 @@ def dpm_step_fused(eps, x, cfg, guidance, coef, step_idx, x_in, hist, table=None
                                                           _stream())), "aldm_dpm_step_fused")
 
 
+def _inpaint_args(x, x0, noise, mask, blend, n_steps):
+    """checks the masked steps' extra operands; returns the channel count (x is channels-last [B, h, w, C])"""
+    C = x.shape[-1]
+    for t in (x0, noise, mask, blend):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device
+    assert x0.numel() == x.numel() and noise.numel() == x.numel() and mask.numel() * C == x.numel(), "x0 / noise / mask geometry"
+    assert blend.dim() == 2 and blend.shape == (n_steps, 2), "blend rows [n_steps, 2]"
+    return C
+
+
+def ddim_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, table, rowbias, timesteps_f32, t_out, ticket, x0, noise, mask, blend):
+    """ddim_step_fused followed by the inpainting blend (aldm_ddim_step_fused_masked): x' = (1 - m) (a x0 + s noise) + m x_ddim with
+    (a, s) = blend[step_idx].  x, x0, noise fp32 [B, h, w, C]; mask fp32 [B, h, w] (1 = regenerate); blend fp32 [n_steps, 2]."""
+    _require_gpu(x)
+    B = x.shape[0]
+    n = x.numel() // B
+    row = table[0].numel() if table is not None else 0
+    assert ticket.dtype == torch.int32 and step_idx.dtype == torch.int32
+    C = _inpaint_args(x, x0, noise, mask, blend, timesteps_f32.numel())
+    # bytes: the unmasked step's, plus x0 and noise (4 B each) and the mask (4 B per pixel)
+    check(_launch("ddim_step_fused_masked", 10.0 * x.numel(),
+                  (4.0 * (2 if cfg else 1) + 8.0 + 8.0 + 4.0 / C + 2.0 * (2 if cfg else 1)) * x.numel() + 8.0 * row,
+                  lambda: _lib.load().aldm_ddim_step_fused_masked(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in),
+                                                                  _p(table), row, _p(rowbias), _p(timesteps_f32), timesteps_f32.numel(), _p(t_out),
+                                                                  _p(ticket), _p(x0), _p(noise), _p(mask), _p(blend), C, _stream())),
+          "aldm_ddim_step_fused_masked")
+
+
+def dpm_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, hist, table, rowbias, timesteps_f32, t_out, ticket, x0, noise, mask,
+                          blend):
+    """dpm_step_fused followed by the inpainting blend (aldm_dpm_step_fused_masked); operands as ddim_step_fused_masked.  hist
+    receives the unblended converted model output.  ticket None: eager, the counter stays (table must be None then)."""
+    _require_gpu(x)
+    B = x.shape[0]
+    n = x.numel() // B
+    row = table[0].numel() if table is not None else 0
+    assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.shape[1] == 8 and step_idx.dtype == torch.int32
+    assert hist.dtype == torch.float32 and hist.numel() == x.numel() and eps.numel() == x.numel() * (2 if cfg else 1)
+    assert ticket is None or (ticket.dtype == torch.int32 and timesteps_f32 is not None and t_out is not None)
+    n_steps = timesteps_f32.numel() if timesteps_f32 is not None else coef.shape[0]
+    C = _inpaint_args(x, x0, noise, mask, blend, n_steps)
+    check(_launch("dpm_step_fused_masked", 14.0 * x.numel(),
+                  (4.0 * (2 if cfg else 1) + 16.0 + 8.0 + 4.0 / C + 2.0 * (2 if cfg else 1)) * x.numel() + 8.0 * row,
+                  lambda: _lib.load().aldm_dpm_step_fused_masked(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in),
+                                                                 _p(hist), _p(table), row, _p(rowbias), _p(timesteps_f32), n_steps, _p(t_out),
+                                                                 _p(ticket), _p(x0), _p(noise), _p(mask), _p(blend), C, _stream())),
+          "aldm_dpm_step_fused_masked")
+
+
 def add_noise(x, noise, coef):
     _require_gpu(x)
     B = x.shape[0]

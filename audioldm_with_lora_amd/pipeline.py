@@ -87,6 +87,27 @@ class AudioLDMPipeline:
             emb = self.text_encoder(tok.input_ids.to(self.device), attention_mask=tok.attention_mask.to(self.device)).text_embeds
         return torch.nn.functional.normalize(emb.float(), dim=-1)
 
+    def _prompt_embeds(self, prompt, prompt_embeds, negative_prompt, negative_prompt_embeds, guidance_scale, num_waveforms_per_prompt):
+        """step 2 with CFG's negative half and num_waveforms_per_prompt: (prompt_embeds, negative_prompt_embeds or None)"""
+        if prompt_embeds is None:
+            if prompt is None:
+                raise ValueError("pass prompt or prompt_embeds")
+            prompts = [prompt] if isinstance(prompt, str) else list(prompt)
+            prompt_embeds = self._encode_prompt(prompts, len(prompts))
+        batch = prompt_embeds.shape[0]
+        cfg = guidance_scale > 1.0
+        if cfg and negative_prompt_embeds is None:
+            if self.text_encoder is not None:
+                neg = [""] * batch if negative_prompt is None else ([negative_prompt] * batch if isinstance(negative_prompt, str) else list(negative_prompt))
+                negative_prompt_embeds = self._encode_prompt(neg, batch)
+            else:
+                negative_prompt_embeds = torch.zeros_like(prompt_embeds)
+        if num_waveforms_per_prompt > 1:
+            prompt_embeds = prompt_embeds.repeat_interleave(num_waveforms_per_prompt, dim=0)
+            if negative_prompt_embeds is not None:
+                negative_prompt_embeds = negative_prompt_embeds.repeat_interleave(num_waveforms_per_prompt, dim=0)
+        return prompt_embeds, negative_prompt_embeds
+
     def geometry(self, audio_length_in_s):
         vc = self.vocoder.config
         up = float(np.prod(vc.upsample_rates)) / vc.sampling_rate
@@ -128,24 +149,9 @@ class AudioLDMPipeline:
             inner = getattr(getattr(self.unet, "base_model", None), "model", self.unet)          # a PeftModel wraps the UNet
             audio_length_in_s = inner.config.sample_size * self.vae_scale_factor * float(np.prod(vc.upsample_rates)) / vc.sampling_rate
         height, n_samples = self.geometry(audio_length_in_s)
-        if prompt_embeds is None:
-            if prompt is None:
-                raise ValueError("pass prompt or prompt_embeds")
-            prompts = [prompt] if isinstance(prompt, str) else list(prompt)
-            prompt_embeds = self._encode_prompt(prompts, len(prompts))
+        prompt_embeds, negative_prompt_embeds = self._prompt_embeds(prompt, prompt_embeds, negative_prompt, negative_prompt_embeds,
+                                                                    guidance_scale, num_waveforms_per_prompt)
         batch = prompt_embeds.shape[0]
-        cfg = guidance_scale > 1.0
-        if cfg and negative_prompt_embeds is None:
-            if self.text_encoder is not None:
-                neg = [""] * batch if negative_prompt is None else ([negative_prompt] * batch if isinstance(negative_prompt, str) else list(negative_prompt))
-                negative_prompt_embeds = self._encode_prompt(neg, batch)
-            else:
-                negative_prompt_embeds = torch.zeros_like(prompt_embeds)
-        if num_waveforms_per_prompt > 1:
-            prompt_embeds = prompt_embeds.repeat_interleave(num_waveforms_per_prompt, dim=0)
-            if negative_prompt_embeds is not None:
-                negative_prompt_embeds = negative_prompt_embeds.repeat_interleave(num_waveforms_per_prompt, dim=0)
-            batch = prompt_embeds.shape[0]
         h, w = height // self.vae_scale_factor, vc.model_in_dim // self.vae_scale_factor
         shape = (batch, self._unet.cfg["in_channels"], h, w)
         if latents is None:

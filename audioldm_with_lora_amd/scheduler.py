@@ -34,7 +34,42 @@ def _config_dict(config, over):
     return d
 
 
-class DDIMScheduler:
+def strength_begin_index(num_inference_steps, strength):
+    """Index of the first step an audio-to-audio / inpainting loop runs at `strength` (diffusers' pipelines' get_timesteps):
+    init = min(int(N * strength), N), begin = max(N - init, 0); the loop runs timesteps[begin:].  Host-only."""
+    N = int(num_inference_steps)
+    if N <= 0:
+        raise ValueError(f"num_inference_steps must be positive, got {num_inference_steps}")
+    if not 0.0 <= float(strength) <= 1.0:
+        raise ValueError(f"The value of strength should be in [0.0, 1.0] but is {strength}")
+    init = min(int(N * strength), N)
+    if init == 0:
+        raise ValueError(f"strength {strength} with {N} inference steps leaves no step to run (int(N * strength) == 0)")
+    return max(N - init, 0)
+
+
+class _SuffixMixin:
+    """The audio-to-audio pieces both schedulers share (host-only: no device, no shared library).  After set_timesteps(N):
+    `get_timesteps(N, strength)` -> (timesteps[begin:], begin); `blend_table(begin)` -> fp32 [N - begin, 2], row k the
+    add_noise_coefficients of schedule index begin + k + 1 and the last row exactly (1, 0) -- diffusers' legacy inpaint loop noises
+    the known latents to timesteps[i + 1] after step i and uses them clean after the last step."""
+
+    def get_timesteps(self, num_inference_steps, strength):
+        begin = strength_begin_index(num_inference_steps, strength)
+        self.set_timesteps(num_inference_steps)
+        return self.timesteps[begin:], begin
+
+    def blend_table(self, begin_index=0):
+        N = len(self.timesteps)
+        if not 0 <= begin_index < N:
+            raise ValueError(f"begin_index {begin_index} outside the schedule of {N} steps")
+        rows = [torch.stack([torch.as_tensor(v, dtype=torch.float32) for v in self.add_noise_coefficients(i)])
+                for i in range(begin_index + 1, N)]
+        rows.append(torch.tensor([1.0, 0.0], dtype=torch.float32))
+        return torch.stack(rows).float().contiguous()
+
+
+class DDIMScheduler(_SuffixMixin):
     def __init__(self, **over):
         cfg = dict(SCHEDULER)
         cfg.update({k: v for k, v in over.items() if k in SCHEDULER})
@@ -84,8 +119,14 @@ class DDIMScheduler:
         a_p = self.alphas_cumprod[p] if p >= 0 else self.final_alpha_cumprod
         return torch.stack([a_t ** 0.5, (1 - a_t) ** 0.5, a_p ** 0.5, (1 - a_p) ** 0.5]).float()
 
-    def coefficient_table(self):
-        return torch.stack([self.step_coefficients(t) for t in self.timesteps.tolist()])
+    def coefficient_table(self, begin_index=0):
+        """rows of timesteps[begin_index:] (a begun DDIM schedule needs no other change: each row depends on its own t only)"""
+        return torch.stack([self.step_coefficients(t) for t in self.timesteps.tolist()[begin_index:]])
+
+    def add_noise_coefficients(self, i):
+        """fp32 (sqrt(abar[t_i]), sqrt(1 - abar[t_i])): what add_noise applies at schedule index i."""
+        a = self.alphas_cumprod[int(self.timesteps[i])]
+        return a ** 0.5, (1 - a) ** 0.5
 
     def step(self, model_output, timestep, sample, eta=0.0, **kw):
         """x_{t-1} from eps (eta = 0) via the fused device kernel; fp32 tensors of any layout."""
@@ -118,7 +159,7 @@ DPM_CONFIG = dict(
 )
 
 
-class DPMSolverMultistepScheduler:
+class DPMSolverMultistepScheduler(_SuffixMixin):
     """DPM-Solver / DPM-Solver++ (first or second order, deterministic), diffusers 0.32.2 arithmetic restated.
 
     `coefficient_table()` turns the whole schedule into fp32 rows {alpha_s, sig_s, A, B, C, convert, reads_hist, 0}; the device
@@ -217,6 +258,7 @@ class DPMSolverMultistepScheduler:
             self.timesteps = self.timesteps.to(device)
         self.num_inference_steps = len(ts)
         self._step_index = None
+        self._begin_index = None
         self._lower_order_nums = 0
         self._hist = {}
 
@@ -262,22 +304,69 @@ class DPMSolverMultistepScheduler:
         one, zero = torch.ones((), dtype=torch.float32), torch.zeros((), dtype=torch.float32)
         return torch.stack([alpha_s0, sigma_s0, A, Bc, Cc, one if pp else zero, one if order == 2 else zero, zero]).float()
 
-    def coefficient_table(self):
+    def coefficient_table(self, begin_index=0):
+        """rows of the schedule from step begin_index on.  A begun schedule starts with an empty history (diffusers:
+        lower_order_nums = 0), so its first row is first order; the later rows and the final-step rule (judged on the full N) are
+        the full schedule's."""
         if self.num_inference_steps is None:
             raise ValueError("call set_timesteps() first")
-        return torch.stack([self.step_coefficients(i) for i in range(len(self.timesteps))])
+        N = len(self.timesteps)
+        if not 0 <= begin_index < N:
+            raise ValueError(f"begin_index {begin_index} outside the schedule of {N} steps")
+        return torch.stack([self.step_coefficients(i, 1 if i == begin_index else None) for i in range(begin_index, N)])
+
+    def add_noise_coefficients(self, i):
+        """fp32 (alpha, sigma) of sigmas[i]: what add_noise applies at schedule index i (diffusers' add_noise after set_begin_index(i))."""
+        return self._alpha_sigma(self.sigmas[i])
+
+    def set_begin_index(self, begin_index=0):
+        self._begin_index = begin_index
+
+    @property
+    def begin_index(self):
+        return getattr(self, "_begin_index", None)
+
+    def index_for_timestep(self, timestep):
+        """diffusers' index_for_timestep: the second match of `timestep` in the schedule when there are two, else the only one, else
+        the last index (a timestep outside the schedule)."""
+        cand = (self.timesteps.cpu() == int(timestep)).nonzero()
+        if len(cand) == 0:
+            return len(self.timesteps) - 1
+        return int(cand[1 if len(cand) > 1 else 0])
+
+    def add_noise_indices(self, timesteps):
+        """The schedule index add_noise uses for each timestep, in diffusers' order: with no begin index, index_for_timestep(t);
+        else, once a step has run, the current step index (add_noise after a step, the inpaint loop); else the begin index (the
+        initial latents of img2img).  Host-only."""
+        t = torch.as_tensor(timesteps).reshape(-1).cpu()
+        if self.begin_index is None:
+            return [self.index_for_timestep(tb) for tb in t.tolist()]
+        if self._step_index is not None:
+            return [self._step_index] * t.numel()
+        return [self.begin_index] * t.numel()
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' DPMSolverMultistepScheduler.add_noise: alpha_t x + sigma_t noise, with (alpha_t, sigma_t) the
+        add_noise_coefficients of add_noise_indices(timesteps) -- one timestep per sample, or one for the whole batch.
+        Coefficients on the host, the multiply-add on the device (aldm_add_noise)."""
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() first")
+        B = original_samples.shape[0]
+        idx = self.add_noise_indices(timesteps)
+        if len(idx) == 1:
+            idx = idx * B
+        if len(idx) != B:
+            raise ValueError(f"add_noise: {len(idx)} timesteps for a batch of {B}")
+        coef = torch.stack([torch.stack(self.add_noise_coefficients(i)) for i in idx]).float().contiguous()
+        return ops.add_noise(original_samples, noise, coef.to(original_samples.device))
 
     @property
     def step_index(self):
         return self._step_index
 
     def _init_step_index(self, timestep):
-        t = int(timestep)
-        cand = (self.timesteps.cpu() == t).nonzero()
-        if len(cand) == 0:
-            self._step_index = len(self.timesteps) - 1
-        else:
-            self._step_index = int(cand[1 if len(cand) > 1 else 0])
+        # diffusers: a schedule begun with set_begin_index starts there, else at the timestep's index
+        self._step_index = self.index_for_timestep(timestep) if self.begin_index is None else self.begin_index
 
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, **kw):
         """x at the next timestep from eps via the device kernel (aldm_dpm_step_fused, eager mode); fp32 tensors of any layout.

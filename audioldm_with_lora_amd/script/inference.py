@@ -7,6 +7,8 @@ writes a wav.  LoRA stays un-merged and is applied inside the fused projection G
 Defaults follow the script: r=2, 50 DDIM steps, 10 s, guidance 5.0; alpha defaults to the TRAINED value 2 rather than the
 script's inconsistent 4 (quirk Q3) -- pass --lora-alpha 4 to reproduce the script literally.
 `--scheduler dpmsolver++ --steps 25` swaps in DPMSolverMultistepScheduler (from the checkpoint's scheduler config) instead of DDIM.
+`--init-audio in.wav --strength 0.5` starts from a 16 kHz recording (AudioLDMAudioToAudioPipeline: style transfer toward the prompt);
+`--regenerate-seconds T0,T1` / `--regenerate-bands F0,F1` regenerate only that time span / fraction of the mel bins and keep the rest.
 """
 import argparse
 import os
@@ -15,6 +17,7 @@ import numpy as np
 import torch
 
 from ..lora import LoraConfig, get_peft_model
+from ..audio2audio import AudioLDMAudioToAudioPipeline, regeneration_mask
 from ..pipeline import AudioLDMPipeline
 from ..scheduler import DPMSolverMultistepScheduler
 from ..unet import UNet2DConditionModel
@@ -34,11 +37,17 @@ def main(argv=None):
                     help="sampler: the reference's DDIM (default) or diffusers' DPMSolverMultistepScheduler from the same config "
                          "(dpmsolver uses final_sigmas_type='sigma_min')")
     ap.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="DPM-Solver order (ignored with --scheduler ddim)")
-    ap.add_argument("--audio-length", type=float, default=10.0)
+    ap.add_argument("--audio-length", type=float, default=None, help="seconds (default 10, or the --init-audio clip's length)")
     ap.add_argument("--guidance-scale", type=float, default=5.0)
     ap.add_argument("--output", default="./generated_audio_LoRA/ex.wav")
     ap.add_argument("--seed", type=int, default=None, help="seed of the initial-noise generator (the reference seeds nothing, quirk Q5)")
+    ap.add_argument("--init-audio", default=None, help="16 kHz wav to start from (audio-to-audio); read with scipy")
+    ap.add_argument("--strength", type=float, default=0.5, help="with --init-audio: how much of the schedule to run (1 = from noise)")
+    ap.add_argument("--regenerate-seconds", default=None, help="with --init-audio: T0,T1 -- regenerate only this time span")
+    ap.add_argument("--regenerate-bands", default=None, help="with --init-audio: F0,F1 -- regenerate only this fraction of the mel bins")
     args = ap.parse_args(argv)
+    if args.init_audio is None and (args.regenerate_seconds or args.regenerate_bands):
+        ap.error("--regenerate-seconds / --regenerate-bands need --init-audio")
 
     device = "cuda"
     unet = UNet2DConditionModel.from_pretrained(args.model_dir, subfolder="unet")
@@ -54,12 +63,56 @@ def main(argv=None):
         pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, algorithm_type=args.scheduler,
                                                                  solver_order=args.solver_order, **extra)
     generator = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
-    audio = pipe(prompt=args.prompt, num_inference_steps=args.steps, audio_length_in_s=args.audio_length,
-                 guidance_scale=args.guidance_scale, generator=generator).audios[0]
+    if args.init_audio is None:
+        audio = pipe(prompt=args.prompt, num_inference_steps=args.steps,
+                     audio_length_in_s=10.0 if args.audio_length is None else args.audio_length,
+                     guidance_scale=args.guidance_scale, generator=generator).audios[0]
+    else:
+        audio = _audio_to_audio(pipe, args, generator)
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     from scipy.io import wavfile
     wavfile.write(args.output, 16000, np.asarray(audio, dtype=np.float32))
     print(f"Generated audio saved to: {args.output}")
+
+
+def _pair(text, name):
+    try:
+        a, b = (float(v) for v in text.split(","))
+    except ValueError:
+        raise SystemExit(f"{name} expects two comma-separated numbers, got {text!r}")
+    return a, b
+
+
+def read_wav(path):
+    """(rate, mono fp32 samples in [-1, 1]) of a wav file read with scipy: float data as stored, signed PCM divided by 2^(bits-1),
+    8-bit PCM (unsigned, centred at 128) shifted by 128 first; channels are averaged."""
+    from scipy.io import wavfile
+    sr, wav = wavfile.read(path)
+    wav = np.asarray(wav)
+    if wav.dtype == np.uint8:
+        wav = (wav.astype(np.float32) - 128.0) / 128.0
+    elif np.issubdtype(wav.dtype, np.signedinteger):
+        wav = wav.astype(np.float32) / float(-np.iinfo(wav.dtype).min)
+    elif not np.issubdtype(wav.dtype, np.floating):
+        raise ValueError(f"{path}: unsupported wav sample type {wav.dtype}")
+    wav = wav.astype(np.float32)
+    if wav.ndim == 2:
+        wav = wav.mean(axis=1)                                  # mono
+    return sr, wav
+
+
+def _audio_to_audio(pipe, args, generator):
+    sr, wav = read_wav(args.init_audio)
+    a2a = AudioLDMAudioToAudioPipeline.from_pipe(pipe)
+    seconds = wav.shape[0] / float(sr) if args.audio_length is None else args.audio_length
+    mask = None
+    if args.regenerate_seconds or args.regenerate_bands:
+        height, _ = a2a.geometry(seconds)
+        mask = regeneration_mask(height, a2a.vocoder.config.model_in_dim,
+                                 seconds=_pair(args.regenerate_seconds, "--regenerate-seconds") if args.regenerate_seconds else None,
+                                 bands=_pair(args.regenerate_bands, "--regenerate-bands") if args.regenerate_bands else None)
+    return a2a(prompt=args.prompt, audio=wav, sampling_rate=sr, strength=args.strength, mask=mask, audio_length_in_s=seconds,
+               num_inference_steps=args.steps, guidance_scale=args.guidance_scale, generator=generator).audios[0]
 
 
 if __name__ == "__main__":

@@ -383,6 +383,20 @@ int aldm_ddim_step_fused(const float* eps, float* x, int B, long long n_per_samp
 int aldm_dpm_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
                         int* step_idx, void* x_in_bf16, float* hist, const float* table, long long row_elems, float* rowbias,
                         const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream);
+/* the two fused steps with the inpainting / audio-to-audio blend (diffusers' legacy inpaint loop) after the scheduler update xn:
+     known = a x0 + s noise ;  x' = (1 - m) known + m xn ;  x and both CFG halves of x_in receive x'  (hist keeps the unblended m0)
+   x0, noise: fp32 [B][h][w][C] (channels-last like x; C = channels, n_per_sample % C == 0); mask fp32 [B][h][w], broadcast over C,
+   1 = regenerate, 0 = keep; blend fp32 [n_steps][2] rows (a, s), selected by step_idx[0] like the coefficient row.  Bitwise: m == 1
+   gives xn, m == 0 gives known, the row (1, 0) gives known == x0.  Everything else (counter, ticket, next time-embedding row) as in
+   the unmasked launches.  B * n_per_sample < 2^31. */
+int aldm_ddim_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                int* step_idx, void* x_in_bf16, const float* table, long long row_elems, float* rowbias,
+                                const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0, const float* noise,
+                                const float* mask, const float* blend, int channels, void* stream);
+int aldm_dpm_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                               int* step_idx, void* x_in_bf16, float* hist, const float* table, long long row_elems, float* rowbias,
+                               const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0, const float* noise,
+                               const float* mask, const float* blend, int channels, void* stream);
 /* measurement aid: keeps `stream` busy for ~us microseconds so that later launches queue up behind it (bench.py) */
 int aldm_sleep_us(int us, void* stream);
 /* device-side loop counter for graph replay: step_idx[0] = (step_idx[0] + 1) mod n_steps ; t_out[0] = timesteps[step_idx[0]] */
