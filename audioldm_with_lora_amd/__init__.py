@@ -1,8 +1,8 @@
 """MI355X-native AudioLDM + LoRA hot path (gfx950 HIP kernels behind a C-ABI).
 
 Drop-in surface for the reference's entry points:
-AudioLDMPipeline / UNet2DConditionModel / AutoencoderKL / SpeechT5HifiGan / DDIMScheduler / DPMSolverMultistepScheduler
-(both in scheduler.py) and the peft-shaped LoraConfig / get_peft_model helpers; AudioLDMAudioToAudioPipeline (audio2audio.py,
+AudioLDMPipeline / UNet2DConditionModel / AutoencoderKL / SpeechT5HifiGan / DDIMScheduler / DPMSolverMultistepScheduler /
+EulerAncestralDiscreteScheduler (all three in scheduler.py; the last one exported here on first use as well) and the peft-shaped LoraConfig / get_peft_model helpers; AudioLDMAudioToAudioPipeline (audio2audio.py,
 exported here on first use) starts from a recording.  No CPU fallback: ops raise if libaldm_hip.so is missing.
 """
 __version__ = "0.1.0"
@@ -12,4 +12,7 @@ def __getattr__(name):
     if name == "AudioLDMAudioToAudioPipeline":
         from .audio2audio import AudioLDMAudioToAudioPipeline
         return AudioLDMAudioToAudioPipeline
+    if name == "EulerAncestralDiscreteScheduler":
+        from .scheduler import EulerAncestralDiscreteScheduler
+        return EulerAncestralDiscreteScheduler
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

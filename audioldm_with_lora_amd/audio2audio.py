@@ -5,6 +5,9 @@ toward the prompt over the suffix timesteps[begin:] of the schedule (diffusers' 
 diffusers' legacy inpaint loop: after every step the known latents, noised to the next timestep, are blended back in where the mask
 keeps them, inside the fused step launch (aldm_{ddim,dpm}_step_fused_masked), so the loop stays one captured graph.
 
+With an EulerAncestralDiscreteScheduler every step re-draws part of the noise on the device (aldm_euler_a_step_fused[_masked]); the
+rows are then in sigma space, (a, s) = (1, sigma).
+
     x0 = scaling_factor * vae.encode(log_mel(audio)).latent_dist.sample()
     x  = a_begin x0 + s_begin eps                         (x = eps exactly at strength 1)
     for k, t in enumerate(timesteps[begin:]):  x = step(unet(x, t), t, x);  x = (1 - m) (a_k x0 + s_k eps) + m x
@@ -144,6 +147,8 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
         x0 = ops.gaussian_sample(dist.parameters.float(), post.to(self.device)) * self.vae.config.scaling_factor
         if float(strength) == 1.0:
             x = eps                                                   # diffusers' is_strength_max: pure noise, not a * x0 + s * eps
+            if self.scheduler.init_noise_sigma != 1.0:                # (sigma-space schedulers start at init_noise_sigma * noise)
+                x = x * self.scheduler.init_noise_sigma
         else:
             a, s = self.scheduler.add_noise_coefficients(begin)
             coef = torch.tensor([float(a), float(s)], dtype=torch.float32).repeat(batch).to(self.device)
@@ -151,6 +156,7 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
 
         eng = self.engine(batch, h, w, num_inference_steps, guidance_scale, begin_index=begin, masked=m_lat is not None)
         eng.set_condition(prompt_embeds, negative_prompt_embeds)
+        self._seed_engine(eng, generator)
         eng.set_latents(x)
         if m_lat is not None:
             eng.set_inpaint(x0, eps, m_lat)

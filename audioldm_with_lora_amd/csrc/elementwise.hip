@@ -4,6 +4,7 @@
 // [REF script/inference/generate_audio.py:47-52] (AudioLDMPipeline.__call__ loop body)
 // [REF script/train/train_audioldm_lora.py:396-403,563-565] (torch.optim.AdamW on the LoRA parameters)
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -288,6 +289,111 @@ __global__ __launch_bounds__(256) void dpm_step_fused_masked_kernel(const float*
                                  (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
 }
 
+// guidance + Euler-ancestral update of one element from a coefficient row {dt, sigma_up, in_scale_next, sigma_down}
+// (scheduler.py EulerAncestralDiscreteScheduler.coefficient_table; dt = sigma_down - sigma_from), every fused multiply-add spelled
+// out as in ddim_update:   x' = x + e dt + sigma_up z      (z ~ N(0, 1) from the Philox stream; sigma_up == 0 on the last row)
+__device__ __forceinline__ float euler_a_update(float eu, float et, float xv, int cfg, float g, float dt, float sigma_up, float z) {
+  const float e = cfg ? fmaf(g, et - eu, eu) : eu;
+  return fmaf(sigma_up, z, fmaf(e, dt, xv));
+}
+
+// The Euler-ancestral counterpart of ddim_step_fused_kernel: guidance, the update above with its noise generated HERE (element i of
+// the [B][n] latents is element i of the current draw of the Philox state, philox.h: no noise tensor in memory, and the same bits
+// as aldm_randn for the same state), the fp32 latents (sigma space: unscaled), the bf16 next UNet input x' * in_scale_next, the
+// next step's time-embedding row, and the counter advance -- which here moves the DRAW ORDINAL of the state as well, by the same
+// last-workgroup ticket: every workgroup reads state[2..3] when it starts, the last one stores ordinal + 1.  VEC = 4 maps one thread
+// to one Philox block; VEC = 1 evaluates the element's whole block and keeps its lane.  ticket == NULL: counter and ordinal stay.
+template <int VEC, bool MASKED>
+__device__ __forceinline__ void euler_a_step_fused_body(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
+                                                        float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                        bf16* __restrict__ x_in, uint32_t* __restrict__ rng, const float* __restrict__ table,
+                                                        long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                        int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket, long long tix,
+                                                        const Inpaint& ip) {
+  typedef float fvec __attribute__((ext_vector_type(VEC)));
+  typedef bf16 bvec __attribute__((ext_vector_type(VEC)));
+  const int cur = step_idx[0];
+  int nxt = cur + 1;
+  if (nxt >= n_steps) nxt = 0;                                // wrap: a replayed graph may run past the schedule (benchmarks)
+  const PhiloxState rs = philox_load(rng);
+  const long long idx = tix * VEC;
+  const long long total = (long long)B * n;
+  if (idx < total) {
+    fvec eu = *reinterpret_cast<const fvec*>(eps + idx), et = eu;
+    if (cfg) et = *reinterpret_cast<const fvec*>(eps + total + idx);
+    const fvec xv = *reinterpret_cast<const fvec*>(x + idx);
+    fvec kx0, knz;
+    if constexpr (MASKED) {
+      kx0 = *reinterpret_cast<const fvec*>(ip.x0 + idx);
+      knz = *reinterpret_cast<const fvec*>(ip.noise + idx);
+    }
+    const float* cf = coef + 4 * cur;
+    const float dt = cf[0], sigma_up = cf[1], in_scale = cf[2];
+    const f32x4 z4 = philox_normal4(rs, (unsigned long long)(idx >> 2));
+    fvec xn;
+    bvec xb;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      float z;
+      if constexpr (VEC == 4) {
+        z = z4[k];
+      } else {
+        const int lane = (int)(idx & 3);
+        z = lane == 0 ? z4[0] : lane == 1 ? z4[1] : lane == 2 ? z4[2] : z4[3];
+      }
+      float r = euler_a_update(eu[k], et[k], xv[k], cfg, g, dt, sigma_up, z);
+      if constexpr (MASKED)
+        r = inpaint_blend(r, kx0[k], knz[k], ip.mask[(unsigned)(idx + k) / (unsigned)ip.C], ip.blend[2 * cur], ip.blend[2 * cur + 1]);
+      xn[k] = r;
+      xb[k] = (bf16)(r * in_scale);
+    }
+    *reinterpret_cast<fvec*>(x + idx) = xn;
+    if (x_in) {
+      *reinterpret_cast<bvec*>(x_in + idx) = xb;
+      if (cfg) *reinterpret_cast<bvec*>(x_in + total + idx) = xb;
+    }
+  }
+  if (table && tix * 4 < row_elems)
+    *reinterpret_cast<f32x4*>(rowbias + tix * 4) = *reinterpret_cast<const f32x4*>(table + (long long)nxt * row_elems + tix * 4);
+  if (!ticket) return;                                        // (uniform over the grid)
+  __syncthreads();                                            // every thread of this workgroup has read the counter and the RNG state
+  if (threadIdx.x == 0) {
+    // acq_rel at agent scope, as in ddim_step_fused_kernel
+    const unsigned done = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (done == gridDim.x - 1) {
+      ticket[0] = 0;
+      step_idx[0] = nxt;
+      t_out[0] = timesteps[nxt];
+      philox_store_next(rng, rs);
+    }
+  }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void euler_a_step_fused_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
+                                                                 float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                                 bf16* __restrict__ x_in, uint32_t* __restrict__ rng,
+                                                                 const float* __restrict__ table, long long row_elems, float* __restrict__ rowbias,
+                                                                 const float* __restrict__ timesteps, int n_steps, float* __restrict__ t_out,
+                                                                 unsigned* __restrict__ ticket) {
+  euler_a_step_fused_body<VEC, false>(eps, x, B, n, cfg, g, coef, step_idx, x_in, rng, table, row_elems, rowbias, timesteps, n_steps, t_out,
+                                      ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void euler_a_step_fused_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                        int cfg, float g, const float* __restrict__ coef,
+                                                                        int* __restrict__ step_idx, bf16* __restrict__ x_in,
+                                                                        uint32_t* __restrict__ rng, const float* __restrict__ table,
+                                                                        long long row_elems, float* __restrict__ rowbias,
+                                                                        const float* __restrict__ timesteps, int n_steps, float* __restrict__ t_out,
+                                                                        unsigned* __restrict__ ticket, const float* __restrict__ x0,
+                                                                        const float* __restrict__ noise, const float* __restrict__ mask,
+                                                                        const float* __restrict__ blend, int C) {
+  euler_a_step_fused_body<VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, rng, table, row_elems, rowbias, timesteps, n_steps, t_out,
+                                     ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
+}
+
 __global__ void advance_step_kernel(int* step_idx, const float* __restrict__ timesteps, int n_steps, float* t_out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     int i = step_idx[0] + 1;
@@ -494,6 +600,56 @@ extern "C" int aldm_dpm_step_fused_masked(const float* eps, float* x, int B, lon
                        cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
                        x0, noise, mask, blend, channels);
   return aldm_launch_status("dpm_step_fused_masked");
+}
+
+// the Euler-ancestral fused steps: aldm_dpm_step_fused's argument list with the Philox state {seed_lo, seed_hi, draw_lo, draw_hi} in the
+// place of the history buffer
+extern "C" int aldm_euler_a_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                       int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table, long long row_elems,
+                                       float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream) {
+  ALDM_CHECK_ARG(eps && x && coef && step_idx && rng_state && B > 0 && n_per_sample > 0 && n_steps > 0, "euler_a_step_fused: bad args");
+  ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "euler_a_step_fused: the counter advance needs timesteps and t_out");
+  ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
+                 "euler_a_step_fused: table needs ticket, rowbias and row_elems %% 4 == 0");
+  if (!table) row_elems = 0;
+  const long long total = (long long)B * n_per_sample;
+  const bool v4 = total % 4 == 0;
+  const long long items = v4 ? total / 4 : total;
+  const long long work = items > row_elems / 4 ? items : row_elems / 4;
+  if (v4)
+    hipLaunchKernelGGL(euler_a_step_fused_kernel<4>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
+                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, rng_state, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket);
+  else
+    hipLaunchKernelGGL(euler_a_step_fused_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
+                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, rng_state, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket);
+  return aldm_launch_status("euler_a_step_fused");
+}
+
+extern "C" int aldm_euler_a_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                              const float* coef, int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table,
+                                              long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                              unsigned* ticket, const float* x0, const float* noise, const float* mask, const float* blend,
+                                              int channels, void* stream) {
+  ALDM_CHECK_ARG(eps && x && coef && step_idx && rng_state && B > 0 && n_per_sample > 0 && n_steps > 0, "euler_a_step_fused_masked: bad args");
+  ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "euler_a_step_fused_masked: the counter advance needs timesteps and t_out");
+  ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
+                 "euler_a_step_fused_masked: table needs ticket, rowbias and row_elems %% 4 == 0");
+  ALDM_CHECK_ARG(x0 && noise && mask && blend && channels > 0 && n_per_sample % channels == 0 && (long long)B * n_per_sample < (1ll << 31),
+                 "euler_a_step_fused_masked: bad inpainting args");
+  if (!table) row_elems = 0;
+  const long long total = (long long)B * n_per_sample;
+  const bool v4 = total % 4 == 0;
+  const long long items = v4 ? total / 4 : total;
+  const long long work = items > row_elems / 4 ? items : row_elems / 4;
+  if (v4)
+    hipLaunchKernelGGL(euler_a_step_fused_masked_kernel<4>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B,
+                       n_per_sample, cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, rng_state, table, row_elems, rowbias, timesteps, n_steps,
+                       t_out, ticket, x0, noise, mask, blend, channels);
+  else
+    hipLaunchKernelGGL(euler_a_step_fused_masked_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B,
+                       n_per_sample, cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, rng_state, table, row_elems, rowbias, timesteps, n_steps,
+                       t_out, ticket, x0, noise, mask, blend, channels);
+  return aldm_launch_status("euler_a_step_fused_masked");
 }
 
 extern "C" int aldm_add_noise(const float* x, const float* noise, const float* coef, int B, long long n_per_sample,

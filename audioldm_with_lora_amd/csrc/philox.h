@@ -1,0 +1,71 @@
+// Counter-based device RNG: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123
+// constants) and the Box-Muller transform to standard normals.  Shared by aldm_randn (rng.hip) and the fused ancestral step
+// (elementwise.hip), which must produce the same bits for the same state.
+//
+// Addressing (independent of the launch shape):  key = the 64-bit seed;  counter = (block_lo, block_hi, draw_lo, draw_hi) with
+// block = element_index / 4 and draw the 64-bit ordinal of the tensor-sized draw within the stream.  Element e of draw d is lane
+// e % 4 of block e / 4, so a one-element-per-thread kernel and a four-wide one read the same words.
+// The state is four 32-bit words in DEVICE memory: {seed_lo, seed_hi, draw_lo, draw_hi}.
+#pragma once
+#include "common.h"
+
+struct PhiloxState { uint32_t seed_lo, seed_hi, draw_lo, draw_hi; };
+
+__device__ __forceinline__ PhiloxState philox_load(const uint32_t* __restrict__ state) {
+  return PhiloxState{state[0], state[1], state[2], state[3]};
+}
+
+// {draw_lo, draw_hi} += 1 as one 64-bit ordinal: two ordinary global stores by the one thread that owns the advance
+__device__ __forceinline__ void philox_store_next(uint32_t* state, const PhiloxState& s) {
+  const uint32_t lo = s.draw_lo + 1u;
+  state[2] = lo;
+  state[3] = s.draw_hi + (lo == 0u ? 1u : 0u);
+}
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
+    const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+    k0 += W0;
+    k1 += W1;
+  }
+}
+
+// the four raw words of `block` of the state's current draw
+__device__ __forceinline__ void philox_block(const PhiloxState& s, unsigned long long block, uint32_t w[4]) {
+  w[0] = (uint32_t)block;
+  w[1] = (uint32_t)(block >> 32);
+  w[2] = s.draw_lo;
+  w[3] = s.draw_hi;
+  philox4x32_10(w, s.seed_lo, s.seed_hi);
+}
+
+// Box-Muller on one word pair, everything in fp32 with the precise library functions:
+//   u = w0 2^-32 + 2^-33 in (0, 1]   (the product is exact, so the sum rounds once; u may round to 1, then r = 0)
+//   v = w1 (2 pi 2^-32) in [0, 2 pi] ;  r = sqrt(-2 ln u) ;  (r cos v, r sin v)
+__device__ __forceinline__ void box_muller(uint32_t w0, uint32_t w1, float& z0, float& z1) {
+  const float u = fmaf((float)w0, 0x1p-32f, 0x1p-33f);
+  const float v = (float)w1 * (6.28318530717958647692f * 0x1p-32f);
+  const float r = sqrtf(-2.f * logf(u));
+  z0 = r * cosf(v);
+  z1 = r * sinf(v);
+}
+
+// the four standard normals of `block` of the state's current draw: lanes 0/1 from (w0, w1), lanes 2/3 from (w2, w3)
+__device__ __forceinline__ f32x4 philox_normal4(const PhiloxState& s, unsigned long long block) {
+  uint32_t w[4];
+  philox_block(s, block, w);
+  f32x4 z;
+  float a, b;
+  box_muller(w[0], w[1], a, b);
+  z[0] = a; z[1] = b;
+  box_muller(w[2], w[3], a, b);
+  z[2] = a; z[3] = b;
+  return z;
+}

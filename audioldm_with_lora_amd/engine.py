@@ -12,11 +12,15 @@ come from the scheduler in the same way, and the previous step's model output li
 Audio-to-audio and inpainting: `begin_index` runs the suffix timesteps[begin:] of the schedule, and `masked`
 swaps in the masked fused steps, which blend the known latents back in after every update (x0, noise, mask and the blend rows in
 four more device buffers, filled by set_inpaint) -- still one launch behind the UNet, so the loop stays one captured graph.
+With an EulerAncestralDiscreteScheduler the update is the ancestral Euler step (ops.euler_a_step_fused), which
+draws its noise inside the launch from a Philox stream whose state {seed, draw ordinal} is one more device buffer: the last workgroup
+moves the ordinal with the step counter, so every replay draws fresh noise.  In sigma space `x` is the unscaled sample and `x_in` holds
+x / sqrt(sigma^2 + 1).
 """
 import torch
 
 from . import ops
-from .scheduler import DPMSolverMultistepScheduler
+from .scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, _fresh_seed
 
 
 class DenoiseEngine:
@@ -32,6 +36,7 @@ class DenoiseEngine:
         self.dev = dev
         scheduler.set_timesteps(num_inference_steps)
         self.dpm = isinstance(scheduler, DPMSolverMultistepScheduler)
+        self.euler = isinstance(scheduler, EulerAncestralDiscreteScheduler)
         self.begin_index, self.masked = int(begin_index), bool(masked)
         if not 0 <= self.begin_index < len(scheduler.timesteps):
             raise ValueError(f"begin_index {begin_index} outside the schedule of {len(scheduler.timesteps)} steps")
@@ -47,7 +52,7 @@ class DenoiseEngine:
         # default stays a single chain.
         if chains is None:
             chains = 1
-        if chains > 1 and self.dpm:
+        if chains > 1 and (self.dpm or self.euler):
             raise NotImplementedError("chains > 1 runs the DDIM update only")
         if chains > 1 and self.masked:
             raise NotImplementedError("chains > 1 runs the unmasked update only")
@@ -58,6 +63,10 @@ class DenoiseEngine:
         self.x_in = [torch.zeros(nbc, height, width, self.C, dtype=torch.bfloat16, device=dev) for _ in range(chains)]
         # DPM-Solver: the previous step's converted model output (read by second-order rows, never by row 0)
         self.hist = torch.zeros_like(self.x) if self.dpm else None
+        # Euler-ancestral: the Philox state {seed_lo, seed_hi, draw_lo, draw_hi} of the in-loop noise (set_seed; set_latents puts the
+        # draw ordinal back to 0) and the input scale of the first row, which set_latents applies (the later rows' are in the table)
+        self.rng = ops.philox_state(_fresh_seed(), 0, dev) if self.euler else None
+        self.in_scale0 = float(scheduler.input_scale(self.begin_index)) if self.euler else 1.0
         # masked: the known latents (x0 * scaling_factor), the eps the loop started from (both NHWC fp32), the mask [B, h, w] fp32
         # (1 = regenerate) and the blend rows (a, s) of the suffix [n_steps, 2] -- set_inpaint fills the first three
         self.x0 = self.noise = self.mask = self.blend = None
@@ -117,11 +126,19 @@ class DenoiseEngine:
                 dst.copy_(src)
         self._prime()
 
+    def set_seed(self, seed):
+        """Euler-ancestral engines: the 64-bit seed of the in-loop noise stream, written into the device state (draw ordinal 0), so a
+        captured graph replays with the new stream.  Same seed + same latents = the same bits, replayed or eager."""
+        if not self.euler:
+            raise ValueError("set_seed needs an engine built with an EulerAncestralDiscreteScheduler (the other updates draw no noise)")
+        self.rng.copy_(ops.philox_state(seed, 0, self.dev))
+
     def set_latents(self, latents_nchw):
-        """latents [B, C, H, W] fp32 (already multiplied by init_noise_sigma = 1)."""
+        """latents [B, C, H, W] fp32, already multiplied by init_noise_sigma (1 for DDIM / DPM-Solver).  Euler-ancestral: the unscaled
+        sigma-space sample; the UNet input gets row 0's input scale here, and the noise stream's draw ordinal returns to 0."""
         x = ops.nchw_to_nhwc(latents_nchw.to(self.dev, torch.float32).contiguous(), out_f32=True)
         self.x.copy_(x)
-        xb = ops.f32_to_bf16(self.x)
+        xb = ops.f32_to_bf16(self.x, self.in_scale0) if self.euler else ops.f32_to_bf16(self.x)
         for i in range(self.chains):
             sl = slice(i * self.bc, (i + 1) * self.bc)
             self.x_in[i][: self.bc].copy_(xb[sl])
@@ -131,6 +148,8 @@ class DenoiseEngine:
         self.t_buf.copy_(self.timesteps_f32[:1])
         if self.hist is not None:
             self.hist.zero_()
+        if self.rng is not None:
+            self.rng[2:].zero_()
         self._prime()
 
     def set_inpaint(self, x0_nchw, noise_nchw, mask):
@@ -165,12 +184,19 @@ class DenoiseEngine:
             eps = self.unet.forward_nhwc(self.x_in[0], self.t_buf, self.cls[0], rowbias=self.rowbias[0])
             if self.masked:
                 ip = (self.x0, self.noise, self.mask, self.blend)
-                if self.dpm:
+                if self.euler:
+                    ops.euler_a_step_fused_masked(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.rng, self.temb[0],
+                                                  self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket, *ip)
+                elif self.dpm:
                     ops.dpm_step_fused_masked(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.hist, self.temb[0],
                                               self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket, *ip)
                 else:
                     ops.ddim_step_fused_masked(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.temb[0],
                                                self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket, *ip)
+                return
+            if self.euler:
+                ops.euler_a_step_fused(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.rng, self.temb[0],
+                                       self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket)
                 return
             if self.dpm:
                 ops.dpm_step_fused(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.hist, self.temb[0],
@@ -199,6 +225,7 @@ class DenoiseEngine:
         self._plan_ref, self.plan_version = self.unet.plan(), self.unet.plan_version
         saved = (self.x.clone(), [t.clone() for t in self.x_in], self.step_idx.clone(), self.t_buf.clone())
         saved_hist = self.hist.clone() if self.hist is not None else None
+        saved_rng = self.rng.clone() if self.rng is not None else None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -214,6 +241,8 @@ class DenoiseEngine:
             dst.copy_(src)
         if saved_hist is not None:
             self.hist.copy_(saved_hist)
+        if saved_rng is not None:
+            self.rng.copy_(saved_rng)
         self._prime()
         torch.cuda.synchronize()
 

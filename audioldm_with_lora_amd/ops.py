@@ -1211,6 +1211,95 @@ def dpm_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, hist, tab
           "aldm_dpm_step_fused_masked")
 
 
+# ---- on-device RNG (csrc/rng.hip, csrc/philox.h) -----------------------------------------------------------------------------
+def _u32_words(v):
+    """a 64-bit unsigned value as two int32 bit patterns (torch has no uint32 arithmetic; the kernels read the words as unsigned)"""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return [w - (1 << 32) if w >= (1 << 31) else w for w in (v & 0xFFFFFFFF, v >> 32)]
+
+
+def philox_state(seed, draw=0, device="cuda"):
+    """The Philox stream state the RNG kernels read: int32 [4] on the device holding the bit patterns {seed_lo, seed_hi, draw_lo,
+    draw_hi} -- a 64-bit seed (the key) and the 64-bit ordinal of the next tensor-sized draw."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.AldmError("the product path runs on the MI355X only (philox_state on a CPU device); there is no CPU fallback")
+    return torch.tensor(_u32_words(seed) + _u32_words(draw), dtype=torch.int32, device=dev)
+
+
+def philox_state_values(state):
+    """(seed, draw) of a philox_state as Python ints (synchronises; for tests and logs)"""
+    w = [int(v) & 0xFFFFFFFF for v in state.cpu().tolist()]
+    return w[0] | (w[1] << 32), w[2] | (w[3] << 32)
+
+
+def _check_state(state):
+    _require_gpu(state)
+    assert state.dtype == torch.int32 and state.numel() == 4 and state.is_contiguous(), "philox state: int32 [4] (ops.philox_state)"
+
+
+def philox_u32(n, state, first_block=0):
+    """n raw Philox4x32-10 words of the state's current draw, from block `first_block` (element 4 * first_block) on, as int32 bit
+    patterns [n] (aldm_philox_u32); the state stays."""
+    _check_state(state)
+    out = torch.empty(int(n), dtype=torch.int32, device=state.device)
+    check(_lib.load().aldm_philox_u32(_p(out), int(n), _p(state), int(first_block) & 0xFFFFFFFFFFFFFFFF, _stream()), "aldm_philox_u32")
+    return out
+
+
+def randn(shape, state, advance=True):
+    """fp32 standard normals of `shape` from the state's current draw (aldm_randn): element i of the flattened tensor is element i of
+    the draw, whatever the shape.  advance: the draw ordinal grows by 1 on the device, so the next call draws a new tensor."""
+    _check_state(state)
+    out = torch.empty(shape, dtype=torch.float32, device=state.device)
+    check(_lib.load().aldm_randn(_p(out), out.numel(), _p(state), int(bool(advance)), _stream()), "aldm_randn")
+    return out
+
+
+def euler_a_step_fused(eps, x, cfg, guidance, coef, step_idx, x_in, rng_state, table=None, rowbias=None, timesteps_f32=None, t_out=None,
+                       ticket=None):
+    """CFG + Euler-ancestral update with the noise drawn in the kernel from rng_state (+ gather_row(next step) + advance_step + the
+    draw ordinal's advance when `ticket` is given) as one launch (aldm_euler_a_step_fused).  coef fp32 [n_steps, 4]
+    (EulerAncestralDiscreteScheduler.coefficient_table); x fp32, unscaled (sigma space); x_in receives bf16(x' * in_scale_next).
+    ticket None: the counter and the ordinal stay."""
+    _require_gpu(x)
+    _check_state(rng_state)
+    B = x.shape[0]
+    n = x.numel() // B
+    row = table[0].numel() if table is not None else 0
+    assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.shape[1] == 4 and step_idx.dtype == torch.int32
+    assert eps.numel() == x.numel() * (2 if cfg else 1)
+    assert ticket is None or (ticket.dtype == torch.int32 and timesteps_f32 is not None and t_out is not None)
+    n_steps = timesteps_f32.numel() if timesteps_f32 is not None else coef.shape[0]
+    # flops: guidance + update + ~100 for ten Philox rounds and a Box-Muller per element; bytes: the DDIM step's (no noise tensor)
+    check(_launch("euler_a_step_fused", 110.0 * x.numel(), (4.0 * (2 if cfg else 1) + 8.0 + 2.0 * (2 if cfg else 1)) * x.numel() + 8.0 * row,
+                  lambda: _lib.load().aldm_euler_a_step_fused(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in),
+                                                              _p(rng_state), _p(table), row, _p(rowbias), _p(timesteps_f32), n_steps,
+                                                              _p(t_out), _p(ticket), _stream())), "aldm_euler_a_step_fused")
+
+
+def euler_a_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, rng_state, table, rowbias, timesteps_f32, t_out, ticket, x0, noise,
+                              mask, blend):
+    """euler_a_step_fused followed by the inpainting blend (aldm_euler_a_step_fused_masked); operands as ddim_step_fused_masked, blend
+    rows (1, sigma_next).  ticket None: the counter and the ordinal stay (table must be None then)."""
+    _require_gpu(x)
+    _check_state(rng_state)
+    B = x.shape[0]
+    n = x.numel() // B
+    row = table[0].numel() if table is not None else 0
+    assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.shape[1] == 4 and step_idx.dtype == torch.int32
+    assert eps.numel() == x.numel() * (2 if cfg else 1)
+    assert ticket is None or (ticket.dtype == torch.int32 and timesteps_f32 is not None and t_out is not None)
+    n_steps = timesteps_f32.numel() if timesteps_f32 is not None else coef.shape[0]
+    C = _inpaint_args(x, x0, noise, mask, blend, n_steps)
+    check(_launch("euler_a_step_fused_masked", 114.0 * x.numel(),
+                  (4.0 * (2 if cfg else 1) + 8.0 + 8.0 + 4.0 / C + 2.0 * (2 if cfg else 1)) * x.numel() + 8.0 * row,
+                  lambda: _lib.load().aldm_euler_a_step_fused_masked(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx),
+                                                                     _p(x_in), _p(rng_state), _p(table), row, _p(rowbias), _p(timesteps_f32),
+                                                                     n_steps, _p(t_out), _p(ticket), _p(x0), _p(noise), _p(mask), _p(blend),
+                                                                     C, _stream())), "aldm_euler_a_step_fused_masked")
+
+
 def add_noise(x, noise, coef):
     _require_gpu(x)
     B = x.shape[0]

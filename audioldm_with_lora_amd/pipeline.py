@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 from .engine import DenoiseEngine
-from .scheduler import DDIMScheduler
+from .scheduler import DDIMScheduler, _fresh_seed
 from .unet import UNet2DConditionModel
 from .vae import AutoencoderKL
 from .vocoder import SpeechT5HifiGan
@@ -127,6 +127,15 @@ class AudioLDMPipeline:
             eng = self._engines[key] = DenoiseEngine(self._unet, self.scheduler, batch, h, w, steps, guidance, device=self.device)
         return eng
 
+    @staticmethod
+    def _seed_engine(eng, generator):
+        """Stochastic samplers (EulerAncestralDiscreteScheduler) draw their per-step noise on the device, inside the replayed graph, from
+        a Philox stream of this library's own.  Its seed is `generator.initial_seed()` when a generator is passed -- only that number is
+        read, the generator's stream is neither used nor advanced by the loop -- else a fresh one from torch's global CPU generator (new
+        on every call, reproducible after torch.manual_seed).  Deterministic samplers draw nothing: no-op."""
+        if eng.euler:
+            eng.set_seed(generator.initial_seed() if generator is not None else _fresh_seed())
+
     def decode_latents_nhwc(self, x_nhwc_f32):
         """steps 6-7: latents [B, h, w, 8] fp32 channels-last -> waveform [B, 160*4h + 32] fp32 (device)."""
         z = ops.f32_to_bf16(x_nhwc_f32, 1.0 / self.vae.config.scaling_factor)
@@ -159,10 +168,12 @@ class AudioLDMPipeline:
             latents = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32)
         elif tuple(latents.shape) != shape:
             raise ValueError(f"Unexpected latents shape, got {tuple(latents.shape)}, expected {shape}")
+        self.scheduler.set_timesteps(num_inference_steps)       # (host-only) init_noise_sigma of a sigma-space scheduler depends on the schedule
         latents = latents.to(self.device, torch.float32) * self.scheduler.init_noise_sigma
 
         eng = self.engine(batch, h, w, num_inference_steps, guidance_scale)
         eng.set_condition(prompt_embeds, negative_prompt_embeds)
+        self._seed_engine(eng, generator)
         eng.set_latents(latents)
         if eng.graph is None and eng.use_graph:
             eng.capture()

@@ -1,4 +1,4 @@
-"""DDIMScheduler and DPMSolverMultistepScheduler for the HIP path (host-side integer logic + device step kernels).
+"""DDIMScheduler, DPMSolverMultistepScheduler and EulerAncestralDiscreteScheduler for the HIP path (host-side integer logic + device step kernels).
 
 Same surface the reference touches: `from_pretrained(id, subfolder="scheduler")`, `.config.num_train_timesteps`,
 `.add_noise` [REF script/train/train_audioldm_lora.py:367,503-504] and, through the pipeline,
@@ -7,6 +7,8 @@ Arithmetic spec: SURVEY.md Appendix B.1 (diffusers 0.32.2).  Timestep indices ar
 diffusers does ("leading" spacing, steps_offset); the fp32 alpha-bar table uses the same torch ops as diffusers.
 DPMSolverMultistepScheduler is diffusers 0.32.2's deterministic multistep solver, swapped in the way diffusers
 users do it: `pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)`.
+EulerAncestralDiscreteScheduler is diffusers 0.32.2's stochastic sampler, swapped in the same way; its per-step
+noise is drawn on the device by the step kernel itself (a Philox stream, ops.philox_state).
 """
 import json
 import os
@@ -395,3 +397,219 @@ class DPMSolverMultistepScheduler(_SuffixMixin):
         if not return_dict:
             return (prev,)
         return SimpleNamespace(prev_sample=prev)
+
+
+# diffusers 0.32.2 EulerAncestralDiscreteScheduler defaults; the keys it shares with DDIMScheduler default to the AudioLDM scheduler
+# configuration, as the other classes' do here
+EULER_A_CONFIG = dict(
+    num_train_timesteps=SCHEDULER["num_train_timesteps"], beta_start=SCHEDULER["beta_start"], beta_end=SCHEDULER["beta_end"],
+    beta_schedule=SCHEDULER["beta_schedule"], trained_betas=None, prediction_type=SCHEDULER["prediction_type"],
+    timestep_spacing=SCHEDULER["timestep_spacing"], steps_offset=SCHEDULER["steps_offset"], rescale_betas_zero_snr=False,
+    use_karras_sigmas=False,
+)
+
+
+def _fresh_seed():
+    """a 63-bit seed from torch's global CPU generator: fresh on every call, reproducible after torch.manual_seed"""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+
+
+class EulerAncestralDiscreteScheduler(_SuffixMixin):
+    """Ancestral sampling with Euler steps, diffusers 0.32.2 arithmetic for epsilon prediction restated.
+
+    Sigma space: sigma = sqrt((1 - abar) / abar); the sample x is UNSCALED (it starts at init_noise_sigma * noise) and the UNet sees
+    scale_model_input(x) = x / sqrt(sigma^2 + 1).  Step i, from s_from = sigmas[i] to s_to = sigmas[i + 1]:
+        sigma_up = sqrt(s_to^2 (s_from^2 - s_to^2) / s_from^2) ;  sigma_down = sqrt(s_to^2 - sigma_up^2)
+        x' = x + e (sigma_down - s_from) + sigma_up z ,  z ~ N(0, I)
+    `coefficient_table()` turns the schedule into fp32 rows {dt, sigma_up, in_scale_next, sigma_down} with dt = sigma_down - s_from and
+    in_scale_next = 1 / sqrt(s_to^2 + 1) (exactly 1 on the last row, where s_to = sigma_up = sigma_down = 0 and x' = x - s_from e).  The
+    device update (aldm_euler_a_step_fused) draws z itself from a Philox stream whose state lives in device memory, so the step
+    replays inside a captured graph.  The noise stream is this library's own (not torch's and not diffusers'): a seed reproduces this
+    library's samples, not another implementation's."""
+
+    def __init__(self, **over):
+        cfg = dict(EULER_A_CONFIG)
+        cfg.update({k: v for k, v in over.items() if k in EULER_A_CONFIG})
+        self.config = SimpleNamespace(**cfg)
+        self._check(cfg)
+        n = cfg["num_train_timesteps"]
+        self.betas = torch.linspace(cfg["beta_start"] ** 0.5, cfg["beta_end"] ** 0.5, n, dtype=torch.float32) ** 2
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        sig = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        self.sigmas = torch.from_numpy(np.concatenate([sig[::-1], [0.0]]).astype(np.float32))
+        self.timesteps = torch.from_numpy(np.linspace(0, n - 1, n, dtype=np.float32)[::-1].copy())
+        self.num_inference_steps = None
+        self._step_index = None
+        self._begin_index = None
+        self._rng = {}
+        self._dev = {}
+
+    @staticmethod
+    def _check(cfg):
+        if cfg["prediction_type"] != "epsilon":
+            raise NotImplementedError(f"prediction_type={cfg['prediction_type']!r}: only epsilon prediction is implemented")
+        if cfg["beta_schedule"] != "scaled_linear" or cfg["trained_betas"] is not None:
+            raise NotImplementedError(f"beta_schedule={cfg['beta_schedule']!r} / trained_betas: only scaled_linear is implemented")
+        for k in ("rescale_betas_zero_snr", "use_karras_sigmas"):
+            if cfg[k]:
+                raise NotImplementedError(f"{k}=True")
+        if cfg["timestep_spacing"] not in ("leading", "linspace", "trailing"):
+            raise NotImplementedError(f"timestep_spacing={cfg['timestep_spacing']!r}")
+
+    @classmethod
+    def from_pretrained(cls, path, subfolder=None, **kw):
+        return cls(**_read_config(path, subfolder))
+
+    @classmethod
+    def from_config(cls, config, **over):
+        """dict or SimpleNamespace (e.g. DDIMScheduler's or DPMSolverMultistepScheduler's `.config`); keys this class does not know
+        (clip_sample, solver_order, ...) are ignored."""
+        return cls(**_config_dict(config, over))
+
+    @property
+    def init_noise_sigma(self):
+        m = self.sigmas.max()
+        if self.config.timestep_spacing in ("linspace", "trailing"):
+            return float(m)
+        return float((m ** 2 + 1) ** 0.5)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        cfg = self.config
+        n, N = cfg.num_train_timesteps, int(num_inference_steps)
+        if not 0 < N <= n:
+            raise ValueError("need 0 < num_inference_steps <= num_train_timesteps")
+        if cfg.timestep_spacing == "linspace":
+            ts = np.linspace(0, n - 1, N, dtype=np.float32)[::-1].copy()
+        elif cfg.timestep_spacing == "leading":
+            ratio = n // N
+            ts = (np.arange(0, N) * ratio).round()[::-1].copy().astype(np.float32)
+            ts += cfg.steps_offset
+        else:                                         # trailing
+            ts = np.arange(n, 0, -n / N).round().copy().astype(np.float32)
+            ts -= 1
+        sig = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        sig = np.interp(ts, np.arange(0, len(sig)), sig)
+        self.sigmas = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
+        self.timesteps = torch.from_numpy(ts)
+        if device is not None:
+            self.timesteps = self.timesteps.to(device)
+        self.num_inference_steps = N
+        self._step_index = None
+        self._begin_index = None
+        self._rng = {}
+
+    def _need_schedule(self):
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() first")
+
+    def input_scale(self, i):
+        """fp32 1 / sqrt(sigmas[i]^2 + 1): what scale_model_input multiplies by at schedule index i (exactly 1 where sigma is 0)"""
+        return 1.0 / ((self.sigmas[i] ** 2 + 1) ** 0.5)
+
+    def step_coefficients(self, i):
+        """fp32 row {dt, sigma_up, in_scale_next, sigma_down} of step i, from diffusers' fp32 scalar torch ops."""
+        s_from, s_to = self.sigmas[i], self.sigmas[i + 1]
+        sigma_up = (s_to ** 2 * (s_from ** 2 - s_to ** 2) / s_from ** 2) ** 0.5
+        sigma_down = (s_to ** 2 - sigma_up ** 2) ** 0.5
+        return torch.stack([sigma_down - s_from, sigma_up, self.input_scale(i + 1), sigma_down]).float()
+
+    def coefficient_table(self, begin_index=0):
+        """rows of the schedule from step begin_index on (each row depends on its own pair of sigmas only)"""
+        self._need_schedule()
+        N = len(self.timesteps)
+        if not 0 <= begin_index < N:
+            raise ValueError(f"begin_index {begin_index} outside the schedule of {N} steps")
+        return torch.stack([self.step_coefficients(i) for i in range(begin_index, N)])
+
+    def add_noise_coefficients(self, i):
+        """fp32 (1, sigmas[i]): what add_noise applies at schedule index i (sigma space: x0 + sigma noise)."""
+        return torch.ones((), dtype=torch.float32), self.sigmas[i]
+
+    def set_begin_index(self, begin_index=0):
+        self._begin_index = begin_index
+
+    @property
+    def begin_index(self):
+        return self._begin_index
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def index_for_timestep(self, timestep):
+        """diffusers' index_for_timestep: the second match of `timestep` in the schedule when there are two, else the first one."""
+        cand = (self.timesteps.cpu() == float(timestep)).nonzero()
+        if len(cand) == 0:
+            raise ValueError(f"timestep {float(timestep)} is not in the schedule")
+        return int(cand[1 if len(cand) > 1 else 0])
+
+    def _init_step_index(self, timestep):
+        self._step_index = self.index_for_timestep(timestep) if self.begin_index is None else self.begin_index
+
+    def scale_model_input(self, sample, timestep):
+        """sample / sqrt(sigma^2 + 1) at the current step (the step index is found from `timestep` on the first call)."""
+        self._need_schedule()
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        return sample * self.input_scale(self._step_index).to(sample.device)
+
+    def _state_for(self, generator, dev):
+        """The Philox state a step draws from.  A device int32 [4] tensor (ops.philox_state) is used as it is and advanced in place.
+        An int seed, or a torch.Generator -- of which ONLY initial_seed() is read: its own stream is neither used nor advanced --
+        names a stream that this scheduler keeps per (seed, device) from its draw 0 on, until the next set_timesteps().  None: one
+        stream per device with a fresh seed (_fresh_seed), likewise kept until set_timesteps()."""
+        if torch.is_tensor(generator):
+            return generator
+        if generator is None:
+            key = (None, dev)
+            if key not in self._rng:
+                self._rng[key] = ops.philox_state(_fresh_seed(), 0, dev)
+            return self._rng[key]
+        seed = generator.initial_seed() if isinstance(generator, torch.Generator) else int(generator)
+        key = (seed, dev)
+        if key not in self._rng:
+            self._rng[key] = ops.philox_state(seed, 0, dev)
+        return self._rng[key]
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, **kw):
+        """x at the next sigma from eps via the device kernel (aldm_euler_a_step_fused, eager mode); fp32 tensors of any layout.  The
+        noise is drawn inside the kernel from the Philox stream `generator` names (see _state_for), whose draw ordinal grows by 1."""
+        self._need_schedule()
+        dev = sample.device
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        i = self._step_index
+        x = sample.detach().float().contiguous().clone()
+        state = self._state_for(generator, dev)
+        # a one-row schedule for the kernel: its counter wraps 0 -> 0, and its ticket advances the draw ordinal
+        coef = self.step_coefficients(i).view(1, 4).to(dev)
+        idx = self._dev.setdefault(("zero", dev), torch.zeros(1, dtype=torch.int32, device=dev))
+        ticket = self._dev.setdefault(("ticket", dev), torch.zeros(1, dtype=torch.int32, device=dev))
+        t1 = self._dev.setdefault(("t1", dev), torch.zeros(1, dtype=torch.float32, device=dev))
+        t_out = self._dev.setdefault(("t_out", dev), torch.zeros(1, dtype=torch.float32, device=dev))
+        ops.euler_a_step_fused(model_output.detach().float().contiguous(), x, False, 0.0, coef, idx, None, state, None, None, t1, t_out, ticket)
+        self._step_index += 1
+        prev = x.to(sample.dtype)
+        if not return_dict:
+            return (prev,)
+        return SimpleNamespace(prev_sample=prev)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' EulerAncestralDiscreteScheduler.add_noise: x + sigma noise, sigma by schedule index -- index_for_timestep(t) with
+        no begin index, else the current step index once a step has run, else the begin index.  The multiply-add runs on the device."""
+        self._need_schedule()
+        B = original_samples.shape[0]
+        t = torch.as_tensor(timesteps).reshape(-1).cpu()
+        if self.begin_index is None:
+            idx = [self.index_for_timestep(tb) for tb in t.tolist()]
+        elif self._step_index is not None:
+            idx = [self._step_index] * t.numel()
+        else:
+            idx = [self.begin_index] * t.numel()
+        if len(idx) == 1:
+            idx = idx * B
+        if len(idx) != B:
+            raise ValueError(f"add_noise: {len(idx)} timesteps for a batch of {B}")
+        coef = torch.stack([torch.stack(self.add_noise_coefficients(i)) for i in idx]).float().contiguous()
+        return ops.add_noise(original_samples, noise, coef.to(original_samples.device))

@@ -7,6 +7,8 @@ writes a wav.  LoRA stays un-merged and is applied inside the fused projection G
 Defaults follow the script: r=2, 50 DDIM steps, 10 s, guidance 5.0; alpha defaults to the TRAINED value 2 rather than the
 script's inconsistent 4 (quirk Q3) -- pass --lora-alpha 4 to reproduce the script literally.
 `--scheduler dpmsolver++ --steps 25` swaps in DPMSolverMultistepScheduler (from the checkpoint's scheduler config) instead of DDIM.
+`--scheduler euler-a` swaps in EulerAncestralDiscreteScheduler (stochastic: fresh noise in every step, drawn on the device); `--seed` then
+seeds both the initial noise and that in-loop stream.
 `--init-audio in.wav --strength 0.5` starts from a 16 kHz recording (AudioLDMAudioToAudioPipeline: style transfer toward the prompt);
 `--regenerate-seconds T0,T1` / `--regenerate-bands F0,F1` regenerate only that time span / fraction of the mel bins and keep the rest.
 """
@@ -19,7 +21,7 @@ import torch
 from ..lora import LoraConfig, get_peft_model
 from ..audio2audio import AudioLDMAudioToAudioPipeline, regeneration_mask
 from ..pipeline import AudioLDMPipeline
-from ..scheduler import DPMSolverMultistepScheduler
+from ..scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
 from ..unet import UNet2DConditionModel
 
 
@@ -33,14 +35,15 @@ def main(argv=None):
     ap.add_argument("--target-modules", default="to_q,to_v")
     ap.add_argument("--prompt", default="An instrumental hip-hop track in the subgenre of boom bap")
     ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--scheduler", choices=["ddim", "dpmsolver++", "dpmsolver"], default="ddim",
+    ap.add_argument("--scheduler", choices=["ddim", "dpmsolver++", "dpmsolver", "euler-a"], default="ddim",
                     help="sampler: the reference's DDIM (default) or diffusers' DPMSolverMultistepScheduler from the same config "
-                         "(dpmsolver uses final_sigmas_type='sigma_min')")
-    ap.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="DPM-Solver order (ignored with --scheduler ddim)")
+                         "(dpmsolver uses final_sigmas_type='sigma_min'), or its EulerAncestralDiscreteScheduler (euler-a)")
+    ap.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="DPM-Solver order (ignored with --scheduler ddim / euler-a)")
     ap.add_argument("--audio-length", type=float, default=None, help="seconds (default 10, or the --init-audio clip's length)")
     ap.add_argument("--guidance-scale", type=float, default=5.0)
     ap.add_argument("--output", default="./generated_audio_LoRA/ex.wav")
-    ap.add_argument("--seed", type=int, default=None, help="seed of the initial-noise generator (the reference seeds nothing, quirk Q5)")
+    ap.add_argument("--seed", type=int, default=None, help="seed of the initial-noise generator and, with --scheduler euler-a, of the in-loop noise stream (the reference seeds "
+                         "nothing, quirk Q5)")
     ap.add_argument("--init-audio", default=None, help="16 kHz wav to start from (audio-to-audio); read with scipy")
     ap.add_argument("--strength", type=float, default=0.5, help="with --init-audio: how much of the schedule to run (1 = from noise)")
     ap.add_argument("--regenerate-seconds", default=None, help="with --init-audio: T0,T1 -- regenerate only this time span")
@@ -58,7 +61,9 @@ def main(argv=None):
             from safetensors.torch import load_file
             unet_lora.load_state_dict(load_file(args.lora_weights), strict=False)
     pipe = AudioLDMPipeline.from_pretrained(args.model_dir, unet=unet).to(device)
-    if args.scheduler != "ddim":
+    if args.scheduler == "euler-a":
+        pipe.scheduler = EulerAncestralDiscreteScheduler.from_config(pipe.scheduler.config)
+    elif args.scheduler != "ddim":
         extra = {"final_sigmas_type": "sigma_min"} if args.scheduler == "dpmsolver" else {}
         pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, algorithm_type=args.scheduler,
                                                                  solver_order=args.solver_order, **extra)

@@ -397,6 +397,34 @@ int aldm_dpm_step_fused_masked(const float* eps, float* x, int B, long long n_pe
                                int* step_idx, void* x_in_bf16, float* hist, const float* table, long long row_elems, float* rowbias,
                                const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0, const float* noise,
                                const float* mask, const float* blend, int channels, void* stream);
+/* Counter-based device RNG: Philox4x32-10 (Random123 constants) with its state in DEVICE memory, so a replayed graph draws new
+   numbers on every replay with no host work.  state: 4 words {seed_lo, seed_hi, draw_lo, draw_hi}.  key = the 64-bit seed; counter =
+   (block_lo, block_hi, draw_lo, draw_hi) with block = element_index / 4 and `draw` the 64-bit ordinal of the tensor-sized draw:
+   element e is lane e % 4 of block e / 4, whatever the launch shape.
+   aldm_philox_u32: out[0..n) = the raw words of the current draw from block first_block on (block numbers wrap at 2^64; the state is
+   left alone) -- with first_block the whole 128-bit counter can be addressed, as the published known-answer vectors need.
+   aldm_randn: out[0..n) fp32 standard normals by Box-Muller on the word pairs of a block, in fp32 with the precise library functions:
+     u = w0 2^-32 + 2^-33, v = w1 (2 pi 2^-32), r = sqrt(-2 ln u); lanes 0/1 = r cos v, r sin v; lanes 2/3 the same from (w2, w3).
+   advance != 0: the draw ordinal grows by 1 behind the draw (a one-thread follow-up launch on the same stream). */
+int aldm_philox_u32(unsigned* out, long long n, const unsigned* state, unsigned long long first_block, void* stream);
+int aldm_randn(float* out, long long n, unsigned* state, int advance, void* stream);
+/* classifier-free guidance + Euler-ancestral update (diffusers' EulerAncestralDiscreteScheduler, epsilon prediction), elementwise
+   over channels-last fp32 latents in sigma space (x is the UNSCALED sample):
+     e  = eps_u + g (eps_t - eps_u)                        (cfg != 0; eps holds [uncond | text] halves)
+     x' = x + e dt + sigma_up z ;  x_in = bf16(x' in_scale_next) in both CFG halves
+   z ~ N(0, 1) is generated in the kernel: element i of [B][n] is element i of the current draw of rng_state (bit for bit what
+   aldm_randn gives for the same state); no noise tensor exists in memory.  coef: device fp32 table [n_steps][4] =
+   {dt, sigma_up, in_scale_next, sigma_down}, the row selected ON DEVICE by step_idx[0].  Counter, next time-embedding row and ticket
+   as in aldm_ddim_step_fused; the last workgroup also advances the draw ordinal of rng_state by 1.  ticket == NULL leaves step_idx
+   and rng_state alone (table NULL, timesteps/t_out unused).  The masked form applies the inpainting blend of
+   aldm_ddim_step_fused_masked to x' before x_in is formed; its blend rows are (1, sigma_next): known = x0 + sigma_next noise. */
+int aldm_euler_a_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                            int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table, long long row_elems, float* rowbias,
+                            const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream);
+int aldm_euler_a_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                   int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table, long long row_elems,
+                                   float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0,
+                                   const float* noise, const float* mask, const float* blend, int channels, void* stream);
 /* measurement aid: keeps `stream` busy for ~us microseconds so that later launches queue up behind it (bench.py) */
 int aldm_sleep_us(int us, void* stream);
 /* device-side loop counter for graph replay: step_idx[0] = (step_idx[0] + 1) mod n_steps ; t_out[0] = timesteps[step_idx[0]] */

@@ -1,6 +1,7 @@
 """Times one real `pipe(...)` call per sampler at config 2 (4 prompts x 10 s, CFG 2.5, rank-4 LoRA, random-init weights), built the
-way bench.py's end-to-end leg builds it: DDIM-200 (the reference app's call), DDIM-25 and DPM-Solver++-25 (second order,
-DPMSolverMultistepScheduler.from_config of the DDIM config).  One pipeline object; the scheduler is swapped between variants.
+way bench.py's end-to-end leg builds it: DDIM-200 (the reference app's call), DDIM-25, DPM-Solver++-25 (second order,
+DPMSolverMultistepScheduler.from_config of the DDIM config) and Euler-ancestral-25 (EulerAncestralDiscreteScheduler.from_config; its
+per-step noise is drawn inside the fused step launch).  One pipeline object; the scheduler is swapped between variants.
 
     python tools/bench_solvers.py [--repeats 3]
 
@@ -38,7 +39,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     args = ap.parse_args()
     from audioldm_with_lora_amd.pipeline import AudioLDMPipeline
-    from audioldm_with_lora_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler
+    from audioldm_with_lora_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
     from audioldm_with_lora_amd.vae import AutoencoderKL
     from audioldm_with_lora_amd.vocoder import SpeechT5HifiGan
     batch, seconds, guidance = 4, 10.0, 2.5
@@ -52,7 +53,8 @@ def main():
     ddim_cfg = pipe.scheduler.config
     variants = [("ddim_200", DDIMScheduler.from_config(ddim_cfg), 200),
                 ("ddim_25", DDIMScheduler.from_config(ddim_cfg), 25),
-                ("dpmsolver++_25", DPMSolverMultistepScheduler.from_config(ddim_cfg), 25)]
+                ("dpmsolver++_25", DPMSolverMultistepScheduler.from_config(ddim_cfg), 25),
+                ("euler-a_25", EulerAncestralDiscreteScheduler.from_config(ddim_cfg), 25)]
     res = {}
     for name, sched, n in variants:
         pipe.scheduler = sched
@@ -66,7 +68,7 @@ def main():
         assert audio.shape == (batch, int(seconds * 16000)) and bool((audio == audio).all())
         call_ms = timed(lambda: pipe(latents=lat.clone(), **call), args.repeats)
         eng = pipe.engine(batch, h, 16, n, guidance)
-        eng.set_latents(lat.cuda())
+        eng.set_latents(lat.cuda() * sched.init_noise_sigma)
         run_ms = timed(eng.run, args.repeats)
         res[name] = {"steps": n, "ms_per_call": round(call_ms, 1), "ms_per_step": round(run_ms / n, 4),
                      "first_call_ms_incl_capture": round(first, 1)}
