@@ -53,6 +53,7 @@ class IgemmArgs(C.Structure):
         ("gnin_bm1", C.c_int), ("gnin_tpi1", C.c_int), ("gnin_bm2", C.c_int), ("gnin_tpi2", C.c_int),
         ("gnin_groups", C.c_int), ("gnin_act", C.c_int), ("gnin_eps", C.c_float),
         ("xcd_map", C.c_int),
+        ("lora_gate", C.c_void_p), ("gate_rows", C.c_int),
     ]
 
 
@@ -76,6 +77,7 @@ class PgemmArgs(C.Structure):
         ("waves", C.c_int),
         ("lora_t_out", C.c_void_p),
         ("vt_dual", C.c_int),
+        ("lora_gate", C.c_void_p), ("gate_rows", C.c_int),
     ]
 
 
@@ -111,6 +113,16 @@ PROTOTYPES = {
     "aldm_attn_block64_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p]),
+    # the block kernels with a per-sample gate table on the LoRA columns (multi-adapter routing): same list + lora_gate
+    "aldm_attn_block64_gated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "aldm_attn_block64_fp8_gated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "aldm_attn_block256_gated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     "aldm_attn_block256": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p]),

@@ -65,15 +65,15 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
         new.device = pipe.device
         return new
 
-    def engine(self, batch, h, w, steps, guidance, begin_index=0, masked=False):
+    def engine(self, batch, h, w, steps, guidance, begin_index=0, masked=False, gated=False):
         key = (batch, h, w, steps, float(guidance), type(self.scheduler).__name__, _frozen_config(self.scheduler), int(begin_index),
-               bool(masked))
+               bool(masked)) + ((True,) if gated else ())
         eng = self._engines.get(key)
         if eng is not None and (eng.unet is not self._unet or eng.scheduler is not self.scheduler or eng.stale()):
             eng = None
         if eng is None:
             eng = self._engines[key] = DenoiseEngine(self._unet, self.scheduler, batch, h, w, steps, guidance, device=self.device,
-                                                     begin_index=begin_index, masked=masked)
+                                                     begin_index=begin_index, masked=masked, gated=gated)
         return eng
 
     def _audio_batch(self, audio, batch, per_prompt):
@@ -108,7 +108,8 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
     @torch.no_grad()
     def __call__(self, prompt=None, audio=None, sampling_rate=16000, strength=0.5, mask=None, audio_length_in_s=None,
                  num_inference_steps=50, guidance_scale=2.5, negative_prompt=None, num_waveforms_per_prompt=1, generator=None,
-                 latents=None, prompt_embeds=None, negative_prompt_embeds=None, return_dict=True, output_type="np"):
+                 latents=None, prompt_embeds=None, negative_prompt_embeds=None, return_dict=True, output_type="np", adapter_names=None,
+                 adapter_weights=None):
         if self.device.type != "cuda":
             raise ops._lib.AldmError("AudioLDMAudioToAudioPipeline runs on the MI355X only: call .to('cuda') (no CPU fallback)")
         if audio is None:
@@ -154,7 +155,9 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
             coef = torch.tensor([float(a), float(s)], dtype=torch.float32).repeat(batch).to(self.device)
             x = ops.add_noise(x0, eps, coef)
 
-        eng = self.engine(batch, h, w, num_inference_steps, guidance_scale, begin_index=begin, masked=m_lat is not None)
+        gated, adapter_names, adapter_weights = self._route(adapter_names, adapter_weights, batch // num_waveforms_per_prompt, num_waveforms_per_prompt)
+        eng = self.engine(batch, h, w, num_inference_steps, guidance_scale, begin_index=begin, masked=m_lat is not None, gated=gated)
+        eng.set_adapters(adapter_names, adapter_weights)
         eng.set_condition(prompt_embeds, negative_prompt_embeds)
         self._seed_engine(eng, generator)
         eng.set_latents(x)

@@ -35,11 +35,13 @@ struct Blk256Args {
   bf16* out;                // [B * N][C] attention output (heads concatenated)
   int np, Kpad, Rp, N, H, B;
   float eps;
+  const float* gate;        // [B][Rp] fp32 per-sample gates of the LoRA columns (GATED instantiations only; LAST: nothing above moves)
 };
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-template <int C, int D, int RT /* LoRA rank tiles of 16: 0, 1 or 2 */>
+// GATED (multi-adapter routing): T'' of sample b is multiplied, in fp32 and before its rounding to bf16, by row b of the gate table.
+template <int C, int D, int RT /* LoRA rank tiles of 16: 0, 1 or 2 */, bool GATED = false>
 __global__ __launch_bounds__(512) void attn_block256_kernel(const Blk256Args p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   aldm_touch_kernargs<sizeof(Blk256Args)>();
@@ -107,6 +109,11 @@ __global__ __launch_bounds__(512) void attn_block256_kernel(const Blk256Args p) 
   for (int t = 0; t < RT; ++t) {
     sa[t] = *reinterpret_cast<const f32x4*>(p.ln_sa + 16 * t + 4 * g);
     ca[t] = *reinterpret_cast<const f32x4*>(p.ln_ca + 16 * t + 4 * g);
+  }
+  f32x4 gt[(GATED && RT) ? RT : 1];
+  if constexpr (GATED) {
+#pragma unroll
+    for (int t = 0; t < RT; ++t) gt[t] = *reinterpret_cast<const f32x4*>(p.gate + (long long)b * p.Rp + 16 * t + 4 * g);
   }
   __builtin_amdgcn_sched_barrier(0);
   // ---- X fragments of this wave's 2 x 16 tokens straight into registers (B operand): lane (n, g) holds X[tok][32 ks + 8 g .. + 7].
@@ -207,7 +214,11 @@ __global__ __launch_bounds__(512) void attn_block256_kernel(const Blk256Args p) 
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) tf[tt][4 * t + j] = (bf16)(acc[tt][j] - mean[tt] * sa[t < RT ? t : 0][j] + ca[t < RT ? t : 0][j] * irs[tt]);
+        for (int j = 0; j < 4; ++j) {
+          float tv = acc[tt][j] - mean[tt] * sa[t < RT ? t : 0][j] + ca[t < RT ? t : 0][j] * irs[tt];
+          if constexpr (GATED) tv *= gt[t < RT ? t : 0][j];
+          tf[tt][4 * t + j] = (bf16)tv;
+        }
     } else {
       if (RT > 0) {
         // LoRA: one more K = 32 step, A = the pre-scaled B rows of this tile with the same k-slot order
@@ -301,11 +312,11 @@ __global__ __launch_bounds__(512) void attn_block256_kernel(const Blk256Args p) 
 #endif
 }
 
-template <int C, int D, int RT>
+template <int C, int D, int RT, bool GATED = false>
 int launch_blk256(const Blk256Args& a, hipStream_t st) {
   constexpr int LDS = 3 * (16 * C * 2 + 1024) + 256 * (D * 2 + 16) + D * (256 * 2 + 136) + 2 * 3 * D * 4;
   static_assert(LDS <= 160 * 1024, "LDS budget");
-  auto kern = attn_block256_kernel<C, D, RT>;
+  auto kern = attn_block256_kernel<C, D, RT, GATED>;
   static unsigned long long attr_done = 0;
   if (int rc = aldm_set_max_lds(reinterpret_cast<const void*>(kern), LDS, &attr_done, "attn_block256")) return rc;
   hipLaunchKernelGGL(kern, dim3(a.H * a.B), dim3(512), LDS, st, a);
@@ -314,19 +325,36 @@ int launch_blk256(const Blk256Args& a, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int aldm_attn_block256(const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
+static int attn_block256_entry(const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
                                   const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used,
                                   const float* ln_sa, const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out,
-                                  void* stream) {
+                                  const float* lora_gate, void* stream) {
   ALDM_CHECK_ARG(x && ln_parts && w && bias && ln_s && out, "attn_block256: null pointer");
+  ALDM_CHECK_ARG(!lora_gate || Rp, "attn_block256: lora_gate without an adapter");
   ALDM_CHECK_ARG(B > 0 && N > 0 && N <= 256 && ln_nparts > 0 && ln_nparts <= 16, "attn_block256: 1 <= N <= 256 tokens per sample, 1 <= ln_nparts <= 16");
   ALDM_CHECK_ARG(Rp == 0 || (Rp % 16 == 0 && ranks_used > 0 && ranks_used <= 32 && ranks_used <= Rp && lora_a && lora_b && ln_sa && ln_ca),
                  "attn_block256: LoRA needs Rp %% 16 == 0, 1 <= ranks_used <= min(32, Rp) and lora_a / lora_b / ln_sa / ln_ca");
   ALDM_CHECK_ARG(H == 8 && d == 48 && Kpad == 384, "attn_block256: built for C = 384 = 8 heads x 48 (the UNet's 252-token level); got H %d d %d Kpad %d", H, d, Kpad);
   Blk256Args a{(const bf16*)x, ln_parts, (const bf16*)w, bias, ln_s, (const bf16*)lora_a, (const bf16*)lora_b, ln_sa, ln_ca, (bf16*)out,
-               ln_nparts, Kpad, Rp, N, H, B, ln_eps};
+               ln_nparts, Kpad, Rp, N, H, B, ln_eps, lora_gate};
   hipStream_t st = (hipStream_t)stream;
+  if (lora_gate) return ranks_used <= 16 ? launch_blk256<384, 48, 1, true>(a, st) : launch_blk256<384, 48, 2, true>(a, st);
   if (Rp == 0) return launch_blk256<384, 48, 0>(a, st);
   if (ranks_used <= 16) return launch_blk256<384, 48, 1>(a, st);   // rank-4 q | k | v = 12 rows: one LoRA-A tile, the zero rows skipped
   return launch_blk256<384, 48, 2>(a, st);
+}
+
+extern "C" int aldm_attn_block256(const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
+                                  const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used,
+                                  const float* ln_sa, const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out,
+                                  void* stream) {
+  return attn_block256_entry(x, ln_parts, ln_nparts, w, Kpad, bias, ln_s, lora_a, lora_b, Rp, ranks_used, ln_sa, ln_ca, ln_eps, B, N, H, d, out, nullptr, stream);
+}
+// multi-adapter routing: the same launch with a per-sample gate table [B][Rp] (fp32) on the LoRA columns
+extern "C" int aldm_attn_block256_gated(const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
+                                        const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used,
+                                        const float* ln_sa, const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out,
+                                        void* stream, const float* lora_gate) {
+  ALDM_CHECK_ARG(lora_gate, "attn_block256_gated: null lora_gate");
+  return attn_block256_entry(x, ln_parts, ln_nparts, w, Kpad, bias, ln_s, lora_a, lora_b, Rp, ranks_used, ln_sa, ln_ca, ln_eps, B, N, H, d, out, lora_gate, stream);
 }

@@ -42,6 +42,7 @@ struct Blk64Args {
   int np, Kpad, Rp, N, H;
   float eps;
   unsigned long long* diag;   // tools/debug_b64.py: s_memtime stamps of workgroup (0, 0), wave 0 (null in production)
+  const float* gate;        // [B][Rp] fp32 per-sample gates of the LoRA columns (GATED instantiations only; LAST: nothing above moves)
 };
 
 #ifdef ALDM_B64_DIAG   // stamps are compiled in only on request: even a never-taken branch perturbs the wait-count bookkeeping
@@ -55,7 +56,9 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // F8 (BASELINE config 5): Q / K / V / P enter the two attention products as OCP e4m3 (v_mfma_f32_16x16x32_fp8_fp8, fp32 accumulation); the
 // fragments are converted where they are used, from the same bf16-rounded values the two-launch fp8 path quantises, P carries 2^8 into
 // its conversion (e4m3 tops out at 448) and the normaliser sums the converted values, so the factor cancels exactly.
-template <int C, int D, int RT /* LoRA rank tiles of 16: 0, 1 or 2 */, bool F8 = false>
+// GATED (multi-adapter routing): T'' of sample b is multiplied, in fp32 and before its rounding to bf16, by row b of the gate table --
+// column j of T belongs to one adapter, so the row selects / weights / blends the adapters of this sample.
+template <int C, int D, int RT /* LoRA rank tiles of 16: 0, 1 or 2 */, bool F8 = false, bool GATED = false>
 __global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   aldm_touch_kernargs<sizeof(Blk64Args)>();
@@ -116,6 +119,11 @@ __global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
   for (int t = 0; t < RT; ++t) {
     sa[t] = *reinterpret_cast<const f32x4*>(p.ln_sa + 16 * t + 4 * g);
     ca[t] = *reinterpret_cast<const f32x4*>(p.ln_ca + 16 * t + 4 * g);
+  }
+  f32x4 gt[(GATED && RT) ? RT : 1];
+  if constexpr (GATED) {
+#pragma unroll
+    for (int t = 0; t < RT; ++t) gt[t] = *reinterpret_cast<const f32x4*>(p.gate + (long long)b * p.Rp + 16 * t + 4 * g);
   }
   __builtin_amdgcn_sched_barrier(0);
   // ---- X fragments of this wave's 16 tokens straight into registers (B operand): lane (n, g) holds X[16 w + n][32 ks + 8 g .. + 7].
@@ -217,7 +225,11 @@ __global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
     if (t < RT) {
       // LoRA-A tile: T'' = T - mean sA + cA / rstd  (the epilogue's rstd (acc - mean s) + c then also fixes the LoRA term)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) tf[4 * t + j] = (bf16)(acc[j] - mean * sa[t < RT ? t : 0][j] + ca[t < RT ? t : 0][j] * irs);
+      for (int j = 0; j < 4; ++j) {
+        float tv = acc[j] - mean * sa[t < RT ? t : 0][j] + ca[t < RT ? t : 0][j] * irs;
+        if constexpr (GATED) tv *= gt[t < RT ? t : 0][j];
+        tf[4 * t + j] = (bf16)tv;
+      }
     } else {
       if (RT > 0) {
         // LoRA: one more K = 32 step, A = the pre-scaled B rows of this tile with the same k-slot order
@@ -328,11 +340,11 @@ __global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
 #endif
 }
 
-template <int C, int D, int RT, bool F8 = false>
+template <int C, int D, int RT, bool F8 = false, bool GATED = false>
 int launch_blk64(const Blk64Args& a, int B, hipStream_t st) {
   constexpr int LDS = 3 * (16 * C * 2 + 1024) + 64 * (D * 2 + 16) + D * (64 * 2 + 8) + 2 * 3 * D * 4;
   static_assert(LDS <= 160 * 1024, "LDS budget");
-  auto kern = attn_block64_kernel<C, D, RT, F8>;
+  auto kern = attn_block64_kernel<C, D, RT, F8, GATED>;
   static unsigned long long attr_done = 0;
   if (int rc = aldm_set_max_lds(reinterpret_cast<const void*>(kern), LDS, &attr_done, "attn_block64")) return rc;
   hipLaunchKernelGGL(kern, dim3(a.H, B), dim3(256), LDS, st, a);
@@ -350,15 +362,20 @@ extern "C" void aldm_attn_block64_set_diag(void* buf) { g_b64_diag = (unsigned l
 static int attn_block64_entry(bool f8, const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
                                  const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used,
                                  const float* ln_sa, const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out,
-                                 void* stream) {
+                                 const float* lora_gate, void* stream) {
   ALDM_CHECK_ARG(x && ln_parts && w && bias && ln_s && out, "attn_block64: null pointer");
+  ALDM_CHECK_ARG(!lora_gate || Rp, "attn_block64: lora_gate without an adapter");
   ALDM_CHECK_ARG(B > 0 && N > 0 && N <= 64 && ln_nparts > 0 && ln_nparts <= 16, "attn_block64: 1 <= N <= 64 tokens per sample, 1 <= ln_nparts <= 16");
   ALDM_CHECK_ARG(Rp == 0 || (Rp % 16 == 0 && ranks_used > 0 && ranks_used <= 32 && ranks_used <= Rp && lora_a && lora_b && ln_sa && ln_ca),
                  "attn_block64: LoRA needs Rp %% 16 == 0, 1 <= ranks_used <= min(32, Rp) and lora_a / lora_b / ln_sa / ln_ca");
   ALDM_CHECK_ARG(H == 8 && d == 80 && Kpad == 640, "attn_block64: built for C = 640 = 8 heads x 80 (the UNet's 64-token level); got H %d d %d Kpad %d", H, d, Kpad);
   Blk64Args a{(const bf16*)x, ln_parts, (const bf16*)w, bias, ln_s, (const bf16*)lora_a, (const bf16*)lora_b, ln_sa, ln_ca, (bf16*)out,
-              ln_nparts, Kpad, Rp, N, H, ln_eps, g_b64_diag};
+              ln_nparts, Kpad, Rp, N, H, ln_eps, g_b64_diag, lora_gate};
   hipStream_t st = (hipStream_t)stream;
+  if (lora_gate) {   // (Rp != 0: checked above)
+    if (f8) return ranks_used <= 16 ? launch_blk64<640, 80, 1, true, true>(a, B, st) : launch_blk64<640, 80, 2, true, true>(a, B, st);
+    return ranks_used <= 16 ? launch_blk64<640, 80, 1, false, true>(a, B, st) : launch_blk64<640, 80, 2, false, true>(a, B, st);
+  }
   if (f8) {
     if (Rp == 0) return launch_blk64<640, 80, 0, true>(a, B, st);
     if (ranks_used <= 16) return launch_blk64<640, 80, 1, true>(a, B, st);
@@ -373,12 +390,27 @@ extern "C" int aldm_attn_block64(const void* x, const float* ln_parts, int ln_np
                                  const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used,
                                  const float* ln_sa, const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out,
                                  void* stream) {
-  return attn_block64_entry(false, x, ln_parts, ln_nparts, w, Kpad, bias, ln_s, lora_a, lora_b, Rp, ranks_used, ln_sa, ln_ca, ln_eps, B, N, H, d, out, stream);
+  return attn_block64_entry(false, x, ln_parts, ln_nparts, w, Kpad, bias, ln_s, lora_a, lora_b, Rp, ranks_used, ln_sa, ln_ca, ln_eps, B, N, H, d, out, nullptr, stream);
 }
 // config 5: the same launch with e4m3 Q / K / V / P attention operands (see F8 above)
 extern "C" int aldm_attn_block64_fp8(const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
                                      const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used,
                                      const float* ln_sa, const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out,
                                      void* stream) {
-  return attn_block64_entry(true, x, ln_parts, ln_nparts, w, Kpad, bias, ln_s, lora_a, lora_b, Rp, ranks_used, ln_sa, ln_ca, ln_eps, B, N, H, d, out, stream);
+  return attn_block64_entry(true, x, ln_parts, ln_nparts, w, Kpad, bias, ln_s, lora_a, lora_b, Rp, ranks_used, ln_sa, ln_ca, ln_eps, B, N, H, d, out, nullptr, stream);
+}
+// multi-adapter routing: the same launches with a per-sample gate table [B][Rp] (fp32) on the LoRA columns
+extern "C" int aldm_attn_block64_gated(const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
+                                       const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used,
+                                       const float* ln_sa, const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out,
+                                       void* stream, const float* lora_gate) {
+  ALDM_CHECK_ARG(lora_gate, "attn_block64_gated: null lora_gate");
+  return attn_block64_entry(false, x, ln_parts, ln_nparts, w, Kpad, bias, ln_s, lora_a, lora_b, Rp, ranks_used, ln_sa, ln_ca, ln_eps, B, N, H, d, out, lora_gate, stream);
+}
+extern "C" int aldm_attn_block64_fp8_gated(const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
+                                           const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used,
+                                           const float* ln_sa, const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out,
+                                           void* stream, const float* lora_gate) {
+  ALDM_CHECK_ARG(lora_gate, "attn_block64_fp8_gated: null lora_gate");
+  return attn_block64_entry(true, x, ln_parts, ln_nparts, w, Kpad, bias, ln_s, lora_a, lora_b, Rp, ranks_used, ln_sa, ln_ca, ln_eps, B, N, H, d, out, lora_gate, stream);
 }

@@ -66,6 +66,11 @@ extern "C" int aldm_igemm(const aldm_igemm_t* p, void* stream) {
                  "igemm: vt_dual needs vt and the plain bf16 epilogue (bias only)");
   ALDM_CHECK_ARG(p->Rp == 0 || p->Rp == 32 || p->Rp == 64, "igemm: Rp must be 0/32/64");
   ALDM_CHECK_ARG(p->Rp == 0 || (p->lora_a && p->lora_b), "igemm: Rp without lora_a/lora_b");
+  ALDM_CHECK_ARG(!p->lora_gate || p->Rp, "igemm: lora_gate without an adapter");
+  ALDM_CHECK_ARG(!p->lora_gate || p->Rp == 32, "igemm: lora_gate needs Rp == 32 (the gate table's width; got %d)", p->Rp);
+  ALDM_CHECK_ARG(!p->lora_gate || !p->lora_t_out, "igemm: lora_t_out (the trainer's copy of T) is not combined with lora_gate");
+  ALDM_CHECK_ARG(!p->lora_gate || (p->gate_rows > 0 && (p->B * p->OH * p->OW) % p->gate_rows == 0),
+                 "igemm: lora_gate needs gate_rows > 0 dividing M (got %d rows per sample, M %d)", p->gate_rows, p->B * p->OH * p->OW);
   ALDM_CHECK_ARG(!p->geglu || (p->Cout % 32 == 0 && !p->rowbias), "igemm: GEGLU needs Cout %% 32 == 0");
   ALDM_CHECK_ARG(!p->vt || (p->vt_col0 % 16 == 0 && p->splits <= 1 && !p->geglu), "igemm: bad vt config");
   ALDM_CHECK_ARG(!p->vt || p->vt_col0 > 0 || p->out, "igemm: out required");
@@ -112,6 +117,7 @@ extern "C" int aldm_igemm(const aldm_igemm_t* p, void* stream) {
   d.kt_per_split = cdiv(d.nkt, d.splits);
   d.splits = cdiv(d.nkt, d.kt_per_split);
   d.ws_rows = d.M;
+  d.lora_gate = p->lora_gate; d.fd_gate = make_fastdiv((unsigned)(p->lora_gate ? p->gate_rows : 1)); d.gate_m1 = d.M - 1;
   d.tiles_n = 0; d.tiles_m = 0; d.nwg = 0;
   ALDM_CHECK_ARG(p->xcd_map >= 0 && p->xcd_map <= 2, "igemm: xcd_map must be 0 (auto), 1 (activation-stationary) or 2 (weight-stationary)");
   {

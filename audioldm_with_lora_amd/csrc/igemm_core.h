@@ -73,6 +73,10 @@ struct IgemmDev {
   int gi_bm1, gi_tpi1, gi_bm2, gi_tpi2, gi_groups, gi_act; float gi_eps;
   int ws_rows;                // rows of one split-K slab of the workspace (= the launch's M; the halo tiles cut p.M per image for the bound checks).
                               // LAST on purpose: a new member anywhere above shifts the scalar-load groups of every kernel's prologue
+  // (after it: read only on the LoRA tail's gated branch, never in a prologue)
+  const float* lora_gate;     // multi-adapter routing: fp32 [M / gate_rows][RP] per-sample gates of the T columns; null = ungated
+  FastDiv fd_gate;            // / gate_rows (rows of the GEMM per sample)
+  int gate_m1;                // M - 1 of the launch: rows past the end (never stored) read the last sample's gates
 };
 
 __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
@@ -103,6 +107,17 @@ __device__ __forceinline__ void igemm_work_item(const IgemmDev& p, int& tile_m, 
     tile_m = fdiv(t, p.fd_tiles_n);
     tile_n = t - tile_m * p.tiles_n;
   }
+}
+
+// ---- multi-adapter routing: the gate on the LoRA side channel ----------------------------------
+// T[row m][col .. col + 3] *= gate[sample of m][col .. col + 3], in fp32, before T is rounded to bf16.  Column j of T belongs to one
+// adapter, so a gate row selects (0 / 1), weights or blends the adapters of its sample.  The sample is the ROW's (m / gate_rows): a tile
+// straddles two samples whenever the rows per sample are no multiple of BM (252 tokens under BM = 64 / 128).
+__device__ __forceinline__ void igemm_gate4(const IgemmDev& p, f32x4& t, int m, int col, int rp) {
+  const int mm = m < p.gate_m1 ? m : p.gate_m1;
+  const f32x4 g = *reinterpret_cast<const f32x4*>(p.lora_gate + (long long)fdiv(mm, p.fd_gate) * rp + col);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) t[e] *= g[e];
 }
 
 // ---- epilogue helpers -------------------------------------------------------------------------
@@ -669,7 +684,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmDev& p, f32x4 (&acc)[M
 }
 
 // ---- main kernel ------------------------------------------------------------------------------
-template <int BM, int BN, int WM, int WN, int RP, bool VT>
+template <int BM, int BN, int WM, int WN, int RP, bool VT, bool GATE = false>
 __global__ __launch_bounds__(THREADS) void igemm_kernel(const IgemmDev p) {
   aldm_touch_kernargs<sizeof(IgemmDev)>();
   static_assert(WM * WN == 4, "4 waves");
@@ -859,6 +874,7 @@ __global__ __launch_bounds__(THREADS) void igemm_kernel(const IgemmDev p) {
       for (int t = 0; t < RT_W; ++t) {
         const int r = wm * (BM / WM) + i * 16 + lrow;  // T row (pixel)
         const int col = (wn * RT_W + t) * 16 + lq * 4; // T column (rank index)
+        if constexpr (GATE) igemm_gate4(p, tacc[i][t], m0 + r, col, RP);
         bf16x4 tv = {(bf16)tacc[i][t][0], (bf16)tacc[i][t][1], (bf16)tacc[i][t][2], (bf16)tacc[i][t][3]};
         *reinterpret_cast<bf16x4*>(As + r * 128 + swz(r, col >> 3) * 16 + (col & 7) * 2) = tv;
         if (p.lora_t_out && tile_n == 0 && m0 + r < p.M)
@@ -910,7 +926,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, un
 }
 #endif
 
-template <int BM, int BN, int WM, int WN, int RP, bool VT, int S, int EPI = 0>
+template <int BM, int BN, int WM, int WN, int RP, bool VT, int S, int EPI = 0, bool GATE = false>
 __global__ __launch_bounds__(64 * WM * WN) void igemm_pipe_kernel(const IgemmDev p) {
   constexpr bool LEAN = EPI == 1 || EPI == 4;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1257,6 +1273,7 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_pipe_kernel(const IgemmDev
 #pragma unroll
           for (int e = 0; e < 4; ++e) tacc[i][t][e] = tacc[i][t][e] - mu * sa4[e] + ca4[e] * irs;
         }
+        if constexpr (GATE) igemm_gate4(p, tacc[i][t], m0 + r, col, RP);
         bf16x4 tv = {(bf16)tacc[i][t][0], (bf16)tacc[i][t][1], (bf16)tacc[i][t][2], (bf16)tacc[i][t][3]};
         *reinterpret_cast<bf16x4*>(As + r * 128 + swz(r, col >> 3) * 16 + (col & 7) * 2) = tv;
         if (p.lora_t_out && tile_n == 0 && m0 + r < p.M)
@@ -1340,15 +1357,17 @@ static __global__ __launch_bounds__(256) void igemm_reduce_kernel(const IgemmDev
   }
 }
 
-template <int BM, int BN, int WM, int WN, int RP, bool VT, int S, int EPI = 0>
+// GATE: multi-adapter routing (igemm_gate4) as a compile-time variant of the Rp = 32 kernels -- the ungated instantiations are exactly
+// the kernels without it
+template <int BM, int BN, int WM, int WN, int RP, bool VT, int S, int EPI = 0, bool GATE = false>
 int launch_cfg(const IgemmDev& d, hipStream_t st) {
   // S == 0: register-staged double buffer (needed when the gather applies an activation); else LDS-DMA ring
   constexpr size_t lds_loop = (S == 0 ? 2 : S) * (size_t)(BM + BN + RP) * 128 + ((S != 0 && RP > 0) ? (size_t)BN * 128 : 0);
   constexpr size_t lds = (lds_loop > (size_t)EpiCfg<BM, BN>::BYTES ? lds_loop : (size_t)EpiCfg<BM, BN>::BYTES) + 2 * BM * sizeof(float);
   static unsigned long long attr_done = 0;   // per-device bit mask (aldm_set_max_lds); one-time, idempotent, races are benign
   void (*kern)(const IgemmDev);
-  if constexpr (S == 0) kern = igemm_kernel<BM, BN, WM, WN, RP, VT>;
-  else kern = igemm_pipe_kernel<BM, BN, WM, WN, RP, VT, S, EPI>;
+  if constexpr (S == 0) kern = igemm_kernel<BM, BN, WM, WN, RP, VT, GATE>;
+  else kern = igemm_pipe_kernel<BM, BN, WM, WN, RP, VT, S, EPI, GATE>;
   if (int rc = aldm_set_max_lds(reinterpret_cast<const void*>(kern), (int)lds, &attr_done, "igemm")) return rc;
   if (d.qstat && !(EPI == 0 || EPI == 4)) {
     aldm_set_error("igemm: qstat_out reached an epilogue instantiation without the statistics code (EPI %d)", EPI);
@@ -1384,18 +1403,18 @@ int launch_rp(const IgemmDev& d, int Rp, bool vt, hipStream_t st) {
     if constexpr (S != 0) {
       if (d.splits <= 1 && !d.geglu && d.out_act == ALDM_ACT_NONE && d.post_act == ALDM_ACT_NONE) {   // LEAN V^T: no split / GEGLU / act code
         if (Rp == 0) return launch_cfg<BM, BN, WM, WN, 0, true, S, 1>(d, st);
-        if (Rp == 32) return launch_cfg<BM, BN, WM, WN, 32, true, S, 1>(d, st);
+        if (Rp == 32) return d.lora_gate ? launch_cfg<BM, BN, WM, WN, 32, true, S, 1, true>(d, st) : launch_cfg<BM, BN, WM, WN, 32, true, S, 1>(d, st);
         return launch_cfg<BM, BN, WM, WN, 64, true, S, 1>(d, st);
       }
     }
     if (Rp == 0) return launch_cfg<BM, BN, WM, WN, 0, true, S>(d, st);
-    if (Rp == 32) return launch_cfg<BM, BN, WM, WN, 32, true, S>(d, st);
+    if (Rp == 32) return d.lora_gate ? launch_cfg<BM, BN, WM, WN, 32, true, S, 0, true>(d, st) : launch_cfg<BM, BN, WM, WN, 32, true, S>(d, st);
     return launch_cfg<BM, BN, WM, WN, 64, true, S>(d, st);
   }
   if constexpr (S != 0) {
     if (d.splits > 1) {                                                   // split-K: only the partial-tile store is compiled in
       if (Rp == 0) return launch_cfg<BM, BN, WM, WN, 0, false, S, 3>(d, st);
-      if (Rp == 32) return launch_cfg<BM, BN, WM, WN, 32, false, S, 3>(d, st);
+      if (Rp == 32) return d.lora_gate ? launch_cfg<BM, BN, WM, WN, 32, false, S, 3, true>(d, st) : launch_cfg<BM, BN, WM, WN, 32, false, S, 3>(d, st);
       return launch_cfg<BM, BN, WM, WN, 64, false, S, 3>(d, st);
     }
     if (Rp == 0 && d.geglu && d.splits <= 1 && !d.res && !d.res2 && !d.out_f32 && d.out_act == ALDM_ACT_NONE &&
@@ -1405,12 +1424,12 @@ int launch_rp(const IgemmDev& d, int Rp, bool vt, hipStream_t st) {
     if (d.splits <= 1 && !d.geglu && d.out_act == ALDM_ACT_NONE && d.post_act == ALDM_ACT_NONE && !d.ln_s) {
       if (Rp == 0 && d.qstat) return launch_cfg<BM, BN, WM, WN, 0, false, S, 4>(d, st);   // + GroupNorm statistics
       if (Rp == 0) return launch_cfg<BM, BN, WM, WN, 0, false, S, 1>(d, st);
-      if (Rp == 32) return launch_cfg<BM, BN, WM, WN, 32, false, S, 1>(d, st);
+      if (Rp == 32) return d.lora_gate ? launch_cfg<BM, BN, WM, WN, 32, false, S, 1, true>(d, st) : launch_cfg<BM, BN, WM, WN, 32, false, S, 1>(d, st);
       return launch_cfg<BM, BN, WM, WN, 64, false, S, 1>(d, st);
     }
   }
   if (Rp == 0) return launch_cfg<BM, BN, WM, WN, 0, false, S>(d, st);
-  if (Rp == 32) return launch_cfg<BM, BN, WM, WN, 32, false, S>(d, st);
+  if (Rp == 32) return d.lora_gate ? launch_cfg<BM, BN, WM, WN, 32, false, S, 0, true>(d, st) : launch_cfg<BM, BN, WM, WN, 32, false, S>(d, st);
   return launch_cfg<BM, BN, WM, WN, 64, false, S>(d, st);
 }
 

@@ -47,6 +47,8 @@ struct PgArgs {
   FastDiv fd_ohw;
   float ln_eps;
   unsigned long long* diag;                // diagnostic builds (make DIAG=1, tools/diag_pgemm.py): s_memtime stamps; null otherwise
+  const float* gate;                       // multi-adapter routing: fp32 [M / gate_rows][Rp] per-sample gates of the T columns; null = ungated
+  FastDiv fd_gate;                         // / gate_rows (rows of the GEMM per sample).  LAST: nothing above moves
 };
 #ifndef PG_LDS_PAD
 #define PG_LDS_PAD 0
@@ -79,7 +81,8 @@ __device__ __forceinline__ bf16x8 pg_cat(bf16x2 a, bf16x2 b, bf16x2 c2, bf16x2 d
 }
 __device__ __forceinline__ int pg_hsw(int R) { return ((R & 3) | (((R >> 3) & 1) << 2)) << 1; }   // chunk XOR of weight row R
 
-template <int K, int NT, int MI, int RT, int EPI, int FL, int NW>
+// GATED: multi-adapter routing (a compile-time variant: the ungated instantiations are exactly the kernels without it)
+template <int K, int NT, int MI, int RT, int EPI, int FL, int NW, bool GATED = false>
 __global__ __launch_bounds__(64 * NW) void pgemm_kernel(const bf16* __restrict__ xg, const bf16* __restrict__ wg, const int M, const int N,
                                                     const int nranges, const int T, const unsigned fd_mul, const unsigned fd_shift,
                                                     const int nwg, const PgArgs p_segment) {
@@ -170,6 +173,7 @@ __global__ __launch_bounds__(64 * NW) void pgemm_kernel(const bf16* __restrict__
     p.Rp = ps->Rp; p.ln_np = ps->ln_np; p.out_ld = ps->out_ld; p.vt_col0 = ps->vt_col0; p.vt_ld = ps->vt_ld; p.OHW = ps->OHW;
     p.vt_vec = ps->vt_vec; p.vt_bs = ps->vt_bs; p.fd_ohw.mul = ps->fd_ohw.mul; p.fd_ohw.shift = ps->fd_ohw.shift; p.dual = ps->dual;
     p.ln_eps = ps->ln_eps; p.diag = ps->diag;
+    if constexpr (GATED) { p.gate = ps->gate; p.fd_gate.mul = ps->fd_gate.mul; p.fd_gate.shift = ps->fd_gate.shift; }
   }
   PG_STAMP(0)
   // ---- LoRA-A fragments (A operand: lane (c, q) holds A[16 rt + c][32 ks + 8 q ..]) ----
@@ -280,6 +284,14 @@ __global__ __launch_bounds__(64 * NW) void pgemm_kernel(const bf16* __restrict__
 #pragma unroll
       for (int i = 0; i < MI; ++i) {
         const float irs = 1.f / rstd[i];
+        // multi-adapter routing: the gates of this row's sample, columns 16 rt + 4 q .. + 3.  A row block may
+        // straddle two samples, so the sample is the ROW's; rows >= M (never stored) read the last sample's row.
+        f32x4 gt[RT];
+        if constexpr (GATED) {
+          const float* grow = p.gate + (long long)fdiv(mrow[i] < M ? mrow[i] : M - 1, p.fd_gate) * p.Rp + 4 * q;
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) gt[rt] = *reinterpret_cast<const f32x4*>(grow + 16 * rt);
+        }
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
           f32x4 ta = {0.f, 0.f, 0.f, 0.f}, tb = {0.f, 0.f, 0.f, 0.f};
@@ -293,6 +305,7 @@ __global__ __launch_bounds__(64 * NW) void pgemm_kernel(const bf16* __restrict__
           for (int e = 0; e < 4; ++e) {
             float v = ta[e];
             if constexpr (LN) v = v - mean[i] * sa[rt][e] + ca[rt][e] * irs;
+            if constexpr (GATED) v *= gt[rt][e];                      // in fp32, before the rounding of T
             tf[i][4 * rt + e] = (bf16)v;
           }
           // training: T = x A^T is an operand of the LoRA gradient products (dB = s dY^T T): the first column range of every row
@@ -587,7 +600,7 @@ __global__ __launch_bounds__(64 * NW) void pgemm_kernel(const bf16* __restrict__
 #endif
 }
 
-template <int K, int NT, int MI, int RT, int EPI, int FL, int NW>
+template <int K, int NT, int MI, int RT, int EPI, int FL, int NW, bool GATED = false>
 int pg_launch(const PgHost& h, hipStream_t st) {
   constexpr int BM = 16 * MI * NW;
   constexpr int STG = NT * K * 2 + ((FL & PG_RES) ? BM * NT * 2 : 0);
@@ -597,7 +610,7 @@ int pg_launch(const PgHost& h, hipStream_t st) {
     aldm_set_error("pgemm: %d B of LDS (K %d, tile %d x %d, %d tiles per range)", lds, K, BM, NT, h.tpr);
     return ALDM_E_UNSUPPORTED;
   }
-  auto kern = pgemm_kernel<K, NT, MI, RT, EPI, FL, NW>;
+  auto kern = pgemm_kernel<K, NT, MI, RT, EPI, FL, NW, GATED>;
   static unsigned long long attr_done = 0;
   if (int rc = aldm_set_max_lds(reinterpret_cast<const void*>(kern), 160 * 1024, &attr_done, "pgemm")) return rc;
   const int grid = cdiv(h.M, BM) * h.nranges;
@@ -609,7 +622,9 @@ int pg_launch(const PgHost& h, hipStream_t st) {
 // the instantiations the transformer blocks use; anything else is refused (the caller keeps aldm_igemm)
 template <int K, int NT, int MI, int NW>
 int pg_dispatch(const PgHost& a, int rt, int epi, int fl, hipStream_t st) {
-#define PG_CASE(RT_, EPI_, FL_) if constexpr ((RT_) == 0 || K <= 384 || MI == 1) { if (rt == (RT_) && epi == (EPI_) && fl == (FL_)) return pg_launch<K, NT, MI, RT_, EPI_, FL_, NW>(a, st); }
+#define PG_CASE(RT_, EPI_, FL_) if constexpr ((RT_) == 0 || K <= 384 || MI == 1) { if (rt == (RT_) && epi == (EPI_) && fl == (FL_)) { \
+    if constexpr ((RT_) > 0) { if (a.a.gate) return pg_launch<K, NT, MI, RT_, EPI_, FL_, NW, true>(a, st); } \
+    return pg_launch<K, NT, MI, RT_, EPI_, FL_, NW>(a, st); } }
   PG_CASE(0, EPI_STD, 0)                                     // plain linear (+ bias)
   PG_CASE(0, EPI_STD, PG_RSTAT)                              // proj_in: + statistics for norm1
   PG_CASE(0, EPI_STD, PG_RES)
@@ -725,6 +740,10 @@ extern "C" int aldm_pgemm(const aldm_pgemm_t* g0, void* stream) {
     ALDM_CHECK_ARG(!g->ln_s || (g->ln_sa && g->ln_ca), "pgemm: folded LayerNorm with LoRA needs ln_sa / ln_ca");
   }
   ALDM_CHECK_ARG(!g->lora_t_out || g->Rp, "pgemm: lora_t_out without an adapter");
+  ALDM_CHECK_ARG(!g->lora_gate || g->Rp, "pgemm: lora_gate without an adapter");
+  ALDM_CHECK_ARG(!g->lora_gate || !g->lora_t_out, "pgemm: lora_t_out (the trainer's copy of T) is not combined with lora_gate");
+  ALDM_CHECK_ARG(!g->lora_gate || (g->gate_rows > 0 && g->M % g->gate_rows == 0),
+                 "pgemm: lora_gate needs gate_rows > 0 dividing M (got %d rows per sample, M %d)", g->gate_rows, g->M);
   ALDM_CHECK_ARG(!g->ln_s || (g->ln_parts && g->ln_nparts > 0 && g->ln_nparts <= 16), "pgemm: the folded LayerNorm takes its statistics from ln_parts (1 .. 16 pairs per row)");
   ALDM_CHECK_ARG(!(g->geglu && (g->vt || g->res || g->rowstat_out || g->Rp)), "pgemm: GEGLU launches take no V^T / residual / statistics / LoRA");
   ALDM_CHECK_ARG(!g->geglu || nt == 64, "pgemm: GEGLU needs nt = 64");
@@ -754,6 +773,7 @@ extern "C" int aldm_pgemm(const aldm_pgemm_t* g0, void* stream) {
   a.fd_ohw = make_fastdiv((unsigned)a.OHW);
   a.ln_eps = g->ln_eps;
   a.diag = g_pg_diag;
+  a.gate = g->lora_gate; a.fd_gate = make_fastdiv((unsigned)(g->lora_gate ? g->gate_rows : 1));
   const int epi = g->geglu ? EPI_GEGLU : (g->vt ? EPI_VT : EPI_STD);
   const int fl = (g->ln_s ? PG_LN : 0) | (g->res ? PG_RES : 0) | (g->rowstat_out ? PG_RSTAT : 0);
   hipStream_t st = (hipStream_t)stream;

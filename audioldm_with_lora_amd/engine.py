@@ -16,6 +16,8 @@ With an EulerAncestralDiscreteScheduler the update is the
 draws its noise inside the launch from a Philox stream whose state {seed, draw ordinal} is one more device buffer: the last workgroup
 moves the ordinal with the step counter, so every replay draws fresh noise.  In sigma space `x` is the unscaled sample and `x_in` holds
 x / sqrt(sigma^2 + 1).
+Multi-adapter LoRA: a gated engine's UNet launches read a per-sample gate table from one more device buffer
+(set_adapters): another routing, other weights or no adapter at all is a copy into that buffer -- no repack, no re-capture.
 """
 import torch
 
@@ -25,7 +27,7 @@ from .scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteSchedu
 
 class DenoiseEngine:
     def __init__(self, unet, scheduler, batch, height, width, num_inference_steps, guidance_scale=2.5,
-                 device="cuda", use_graph=True, chains=None, begin_index=0, masked=False):
+                 device="cuda", use_graph=True, chains=None, begin_index=0, masked=False, gated=False):
         self.unet, self.scheduler = unet, scheduler
         self.B, self.H, self.W = batch, height, width
         self.C = unet.cfg["in_channels"]
@@ -77,6 +79,12 @@ class DenoiseEngine:
         self.t_buf = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)      # the fused step's last-workgroup ticket (rests at 0)
+        # Multi-adapter routing: [chains][nbc][32] fp32 gate tables the UNet's fused-LoRA launches read.  An engine is GATED when the
+        # model needs a gate at construction (more than one adapter, or non-default routing); an engine for a plain single-adapter model
+        # passes none and its launches are the ungated ones.
+        self.gate = None
+        if gated or (hasattr(unet, "routing_is_plain") and not unet.routing_is_plain()):
+            self._fill_gate(None, None)
         self.cls = None
         self.temb = None             # [chains][n_steps, nbc, temb_total] fp32: time-embedding projections of every step
         self.rowbias = None          # [chains][nbc, temb_total] fp32: the current step's row (gathered on the device)
@@ -125,6 +133,41 @@ class DenoiseEngine:
             for dst, src in zip(self.temb, tabs):
                 dst.copy_(src)
         self._prime()
+
+    @property
+    def gated(self):
+        return self.gate is not None
+
+    def set_adapters(self, adapter_names=None, adapter_weights=None):
+        """Per-clip adapter routing: adapter_names has one entry per clip of the batch (a name, "__base__", a list or a dict name ->
+        weight; None = the model's active adapters with their set weights), adapter_weights an optional factor per clip.  The gate rows
+        go into the engine's own device buffer, so a captured graph replays with the new routing; under CFG both halves of a clip get
+        the same gates."""
+        plain = adapter_weights is None and self.unet.routing_is_plain(adapter_names)
+        if self.gate is None:
+            if plain:
+                return
+            if getattr(self, "graph", None) is not None:
+                raise ops._lib.AldmError("DenoiseEngine: this graph was captured without a gate table (plain single-adapter model); "
+                                         "build a new engine to route adapters per clip")
+        self._fill_gate(adapter_names, adapter_weights)
+
+    def _fill_gate(self, adapter_names, adapter_weights):
+        g = self.unet.device_gate(adapter_names, self.B, adapter_weights)
+        if g is None:                                        # plain routing on a gated engine: the table of the active adapter
+            g = self.unet.gate_table(adapter_names, self.B).to(self.dev)
+        new = []
+        for i in range(self.chains):
+            sl = g[i * self.bc:(i + 1) * self.bc]
+            new.append((torch.cat([sl, sl]) if self.cfg else sl).contiguous())
+        if self.gate is None:
+            self.gate = new
+        else:
+            for dst, src in zip(self.gate, new):
+                dst.copy_(src)
+
+    def _gate(self, i):
+        return None if self.gate is None else self.gate[i]
 
     def set_seed(self, seed):
         """Euler-ancestral engines: the 64-bit seed of the in-loop noise stream, written into the device state (draw ordinal 0), so a
@@ -175,13 +218,13 @@ class DenoiseEngine:
 
     def _chain_step(self, i):
         ops.gather_row(self.temb[i], self.step_idx, self.rowbias[i])
-        eps = self.unet.forward_nhwc(self.x_in[i], self.t_buf, self.cls[i], rowbias=self.rowbias[i])
+        eps = self.unet.forward_nhwc(self.x_in[i], self.t_buf, self.cls[i], rowbias=self.rowbias[i], gate=self._gate(i))
         ops.cfg_ddim_step(eps, self.x[i * self.bc:(i + 1) * self.bc], self.cfg, self.g, self.coef, self.step_idx, self.x_in[i])
 
     def _one_step(self):
         if self.chains == 1:
             # one chain: guidance + the scheduler's update, the next step's time-embedding row and the step counter in ONE launch behind the UNet
-            eps = self.unet.forward_nhwc(self.x_in[0], self.t_buf, self.cls[0], rowbias=self.rowbias[0])
+            eps = self.unet.forward_nhwc(self.x_in[0], self.t_buf, self.cls[0], rowbias=self.rowbias[0], gate=self._gate(0))
             if self.masked:
                 ip = (self.x0, self.noise, self.mask, self.blend)
                 if self.euler:

@@ -126,15 +126,34 @@ def pack_linear_ln(weight, bias, gamma, beta, eps=1e-5, geglu=False):
     return pw
 
 
-def attach_lora(pw: PackedW, parts):
+def attach_lora(pw: PackedW, parts, layout=None):
     """parts: list of (row_offset, n_rows, A [r, K], B [n_rows, r], scaling) -- one per LoRA-wrapped target
-    that shares this GEMM.  Builds A_cat [Rp][Kpad] and the block-structured, pre-scaled B_ext [N][Rp]."""
+    that shares this GEMM.  Builds A_cat [Rp][Kpad] and the block-structured, pre-scaled B_ext [N][Rp].
+
+    Several adapters: parts carry a sixth element, the adapter's name, and layout = {adapter: (first column, width)} (lora.lora_layout)
+    gives every adapter the same column block in every fused GEMM of the model; the parts of an adapter fill its block from the left
+    in the order given, unused columns stay zero.  ranks_used = one past the last column in use.  A single adapter whose block starts
+    at column 0 gives exactly the packing without a layout."""
     parts = [p for p in parts if p is not None]
     if not parts:
         pw.lora_a = pw.lora_b = None
         pw.Rp = 0
         return pw
-    rtot = sum(p[2].shape[0] for p in parts)
+    if layout is None:
+        cols, c = [], 0
+        for p in parts:
+            cols.append(c)
+            c += p[2].shape[0]
+    else:
+        cursor = {n: c0 for n, (c0, _) in layout.items()}
+        cols = []
+        for p in parts:
+            c0, wd = layout[p[5]]
+            cols.append(cursor[p[5]])
+            cursor[p[5]] += p[2].shape[0]
+            if cursor[p[5]] > c0 + wd:
+                raise _lib.AldmError(f"attach_lora: adapter {p[5]!r} overflows its column block {layout[p[5]]}")
+    rtot = max(c + p[2].shape[0] for c, p in zip(cols, parts))
     rp = 32 if rtot <= 32 else 64
     if rtot > 64:
         raise _lib.AldmError(f"fused LoRA supports a combined rank <= 64 per GEMM (got {rtot})")
@@ -144,8 +163,7 @@ def attach_lora(pw: PackedW, parts):
     ln = getattr(pw, "_ln", None) if pw.ln_s is not None else None
     sa = torch.zeros(rp, dtype=torch.float32, device=dev)
     ca = torch.zeros(rp, dtype=torch.float32, device=dev)
-    col = 0
-    for row0, nrows, A, Bm, s in parts:
+    for col, (row0, nrows, A, Bm, s, *_) in zip(cols, parts):
         r, k = A.shape
         Af = A.detach().float()
         if ln is not None:                      # LayerNorm folded: A' = A diag(gamma), sA = row sums, cA = A beta
@@ -156,9 +174,8 @@ def attach_lora(pw: PackedW, parts):
             Ap = Af.to(torch.bfloat16)
         a[col:col + r, :k] = Ap
         b[row0:row0 + nrows, col:col + r] = (Bm.detach().float() * s).to(torch.bfloat16)
-        col += r
     pw.lora_a, pw.lora_b, pw.Rp = a.contiguous(), b.contiguous(), rp
-    pw.ranks_used = col
+    pw.ranks_used = rtot
     if ln is not None:
         pw.ln_sa, pw.ln_ca = sa, ca
     return pw
@@ -357,6 +374,43 @@ TILE_NAMES = {1: "128x128", 2: "64x64", 3: "128x64", 4: "64x128", 6: "128x128w8"
 # (unet.run_attention) so that bench.py can price the module as a whole.
 PROFILE = None
 SITE = None
+
+# Multi-adapter routing: the per-sample gate table (fp32 [samples][32], device) of the forward pass in progress.  Every launch with a
+# LoRA side channel takes it (UNet2DConditionModel.forward sets it for the duration of a pass); None = ungated launches.
+LORA_GATE = None
+
+
+class lora_gate_scope:
+    """with ops.lora_gate_scope(table): every fused-LoRA launch inside reads `table` (None: ungated)."""
+
+    def __init__(self, table):
+        self.table = table
+
+    def __enter__(self):
+        global LORA_GATE
+        self.prev, LORA_GATE = LORA_GATE, self.table
+        return self.table
+
+    def __exit__(self, *exc):
+        global LORA_GATE
+        LORA_GATE = self.prev
+        return False
+
+
+def _gate_for(pw, M, lora_gate, lora_t_out=None):
+    """(gate tensor, rows of the GEMM per sample) for a launch over M rows with this weight pack, or (None, 0)"""
+    g = lora_gate if lora_gate is not None else LORA_GATE
+    if g is None or not pw.Rp:
+        if lora_gate is not None:
+            raise _lib.AldmError("lora_gate given for a weight pack without an adapter")
+        return None, 0
+    if lora_t_out is not None:
+        raise _lib.AldmError("lora_t_out (the trainer's copy of T) is not combined with a gate table")
+    if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.dim() == 2 and g.shape[1] == pw.Rp):
+        raise _lib.AldmError(f"gate table must be a contiguous fp32 device tensor [samples][{pw.Rp}] (got {tuple(g.shape)} {g.dtype})")
+    if M % g.shape[0]:
+        raise _lib.AldmError(f"gate table has {g.shape[0]} rows, which does not divide the launch's {M} rows")
+    return g, M // g.shape[0]
 KEYLOG = None        # with PROFILE: (row index, (tuning-table key, (tile, ring, splits) used)) of every igemm launch (tools/ab_overlay.py)
 
 
@@ -471,7 +525,7 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
          out_slope=0.0, res=None, res2=None, alpha=1.0, post_act=ACT_NONE, post_slope=0.0, out2=None, out=None, out_f32=False, out_ld=None, out_batch_stride=None,
          out_pix_stride=1, out_pix_offset=0, vt=None, vt_col0=0, vt_ld=0, vt_batch_stride=0, lora_t_out=None,
          splits=None, tile=0, ring=0, gn=None, gn_keep=False, defer=False, rowstats=False, ln_parts=None, x3=None, x4=None,
-         vt_dual=False, qstats=False, gn_in=None):
+         vt_dual=False, qstats=False, gn_in=None, lora_gate=None):
     """Implicit-GEMM convolution over channels-last x [B, IH, IW, C1] (+ x2 [B, IH, IW, C2]).
 
     gn=(gamma, beta, groups, eps, act) returns GroupNorm(+act) of the convolution instead of the convolution: when the launch
@@ -486,7 +540,9 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
 
     LayerNorm hand-over (BasicTransformerBlock: h -> LayerNorm -> projection): rowstats=True returns (out, stats), stats fp32
     [M, N / BN, 2] = per-row partial (sum, sum of squares) written by the epilogue; a consumer packed with pack_linear_ln takes
-    them as ln_parts= and derives mean / rstd from them -- no LayerNorm launch, no statistics pass in either GEMM's K loop."""
+    them as ln_parts= and derives mean / rstd from them -- no LayerNorm launch, no statistics pass in either GEMM's K loop.
+
+    lora_gate (default: ops.LORA_GATE): fp32 [samples][Rp] per-sample gates of the LoRA side channel's columns (multi-adapter routing)."""
     _require_gpu(x)
     if _pending_get(x) is not None:
         raise _lib.AldmError("conv: a deferred split-K reduce is pending on this stream -- its consumer groupnorm() must be the next launch")
@@ -530,7 +586,8 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
             and not (vt is not None and (res is not None or rowstats or vt_col0 % 32 or (vt_col0 <= 0 and not vt_dual) or vt_col0 < 0))
             and (res is None or (res.is_contiguous() and res.numel() == B * OH * OW * out_ld))
             and PGEMM_CFG.get(_pgemm_key(B * OH * OW, pw, C1, res, vt, rowstats, lora_t_out is not None, vt_dual)) != PGEMM_USE_IGEMM):
-        return _pgemm(x, pw, out, out_ld, B * OH * OW, C1, OH * OW, res, vt, vt_col0, vt_ld, vt_batch_stride, rowstats, ln_parts, lora_t_out, vt_dual)
+        return _pgemm(x, pw, out, out_ld, B * OH * OW, C1, OH * OW, res, vt, vt_col0, vt_ld, vt_batch_stride, rowstats, ln_parts, lora_t_out, vt_dual,
+                      lora_gate=lora_gate)
     a = IgemmArgs()
     if x3 is not None:
         for t in (x3, x4):
@@ -552,6 +609,9 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
     if pw.Rp:
         a.lora_a, a.lora_b, a.Rp = pw.lora_a.data_ptr(), pw.lora_b.data_ptr(), pw.Rp
         a.lora_t_out = lora_t_out.data_ptr() if lora_t_out is not None else None
+    gate, gate_rows = _gate_for(pw, B * OH * OW, lora_gate, lora_t_out)
+    if gate is not None:
+        a.lora_gate, a.gate_rows = gate.data_ptr(), gate_rows
     a.bias = pw.bias.data_ptr() if pw.bias is not None else None
     if pw.ln_s is not None:
         a.ln_s, a.ln_eps = pw.ln_s.data_ptr(), pw.ln_eps
@@ -753,7 +813,7 @@ def _pgemm_key(M, pw, K, res, vt, rowstats=False, lora_t=False, dual=False):
     return (M, pw.N, K, kind)
 
 
-def _pgemm(x, pw, out, out_ld, M, K, OHW, res, vt, vt_col0, vt_ld, vt_bs, rowstats, ln_parts, lora_t_out=None, vt_dual=False):
+def _pgemm(x, pw, out, out_ld, M, K, OHW, res, vt, vt_col0, vt_ld, vt_bs, rowstats, ln_parts, lora_t_out=None, vt_dual=False, lora_gate=None):
     """conv()'s 1x1 / short-K case on aldm_pgemm: same operands, same results (to rounding), a kernel built for it."""
     lib = _lib.load()
     a = _lib.PgemmArgs()
@@ -772,6 +832,9 @@ def _pgemm(x, pw, out, out_ld, M, K, OHW, res, vt, vt_col0, vt_ld, vt_bs, rowsta
         if lora_t_out is not None:
             assert lora_t_out.dtype == torch.bfloat16 and lora_t_out.is_contiguous() and tuple(lora_t_out.shape) == (M, pw.Rp)
             a.lora_t_out = lora_t_out.data_ptr()
+    gate, gate_rows = _gate_for(pw, M, lora_gate, lora_t_out)
+    if gate is not None:
+        a.lora_gate, a.gate_rows = gate.data_ptr(), gate_rows
     a.geglu = 1 if pw.geglu else 0
     a.res = res.data_ptr() if res is not None else None
     a.out, a.out_ld = out.data_ptr(), out_ld
@@ -975,12 +1038,12 @@ def attn_block_ok(pw, N, H, d, ln_parts):
     return 0
 
 
-def attn_block(x2d, pw, ln_parts, B, N, H, d, fp8=False):
+def attn_block(x2d, pw, ln_parts, B, N, H, d, fp8=False, lora_gate=None):
     """x2d [B*N, C] raw hidden state -> attention output [B*N, C] through the fused launch attn_block_ok() names (fp8: config 5's e4m3
     attention operands; the 64-token launch has that form, the 256-token one does not)."""
     kind = attn_block_ok(pw, N, H, d, ln_parts)
     if kind == 64:
-        return attn_block64(x2d, pw, ln_parts, B, N, H, d, fp8=fp8)
+        return attn_block64(x2d, pw, ln_parts, B, N, H, d, fp8=fp8, lora_gate=lora_gate)
     if fp8:
         raise _lib.AldmError("attn_block: the 256-token fused launch has no fp8 form")
     if kind != 256:
@@ -991,14 +1054,19 @@ def attn_block(x2d, pw, ln_parts, B, N, H, d, fp8=False):
     assert ln_parts.dtype == torch.float32 and ln_parts.is_contiguous() and ln_parts.shape[0] == B * N
     out = torch.empty(B * N, Cc, dtype=torch.bfloat16, device=x2d.device)
     fl = B * (6.0 * N * Cc * Cc + 4.0 * N * N * Cc + (12.0 * N * Cc * getattr(pw, "ranks_used", 0) if pw.Rp else 0.0))
-    check(_launch(f"attn_block256_d{d}_n{N}", fl, 2.0 * (2 * B * N * Cc + 3 * Cc * Cc), lambda: _lib.load().aldm_attn_block256(
+    gate, _ = _gate_for(pw, B, lora_gate)                    # one row per sample: the workgroup's
+    if gate is not None and gate.shape[0] != B:
+        raise _lib.AldmError(f"gate table has {gate.shape[0]} rows for {B} samples")
+    fn = _lib.load().aldm_attn_block256_gated if gate is not None else _lib.load().aldm_attn_block256
+    check(_launch(f"attn_block256_d{d}_n{N}", fl, 2.0 * (2 * B * N * Cc + 3 * Cc * Cc), lambda: fn(
         _p(x2d), _p(ln_parts), ln_parts.shape[1], _p(pw.w), pw.Kpad, _p(pw.bias), _p(pw.ln_s), _p(pw.lora_a), _p(pw.lora_b), pw.Rp,
-        getattr(pw, "ranks_used", 0) if pw.Rp else 0, _p(pw.ln_sa), _p(pw.ln_ca), pw.ln_eps, B, N, H, d, _p(out), _stream())),
+        getattr(pw, "ranks_used", 0) if pw.Rp else 0, _p(pw.ln_sa), _p(pw.ln_ca), pw.ln_eps, B, N, H, d, _p(out), _stream(),
+        *(() if gate is None else (_p(gate),)))),
         "aldm_attn_block256")
     return out
 
 
-def attn_block64(x2d, pw, ln_parts, B, N, H, d, fp8=False):
+def attn_block64(x2d, pw, ln_parts, B, N, H, d, fp8=False, lora_gate=None):
     """x2d [B*N, C] raw hidden state -> attention output [B*N, C]: LayerNorm-folded QKV projection with LoRA + 64-token attention,
     one launch (aldm_attn_block64)."""
     _require_gpu(x2d)
@@ -1007,10 +1075,14 @@ def attn_block64(x2d, pw, ln_parts, B, N, H, d, fp8=False):
     assert ln_parts.dtype == torch.float32 and ln_parts.is_contiguous() and ln_parts.shape[0] == B * N
     out = torch.empty(B * N, Cc, dtype=torch.bfloat16, device=x2d.device)
     fl = B * (6.0 * N * Cc * Cc + 4.0 * N * N * Cc + (12.0 * N * Cc * getattr(pw, "ranks_used", 0) if pw.Rp else 0.0))
-    fn = _lib.load().aldm_attn_block64_fp8 if fp8 else _lib.load().aldm_attn_block64
+    gate, _ = _gate_for(pw, B, lora_gate)                    # one row per sample: the workgroup's
+    if gate is not None and gate.shape[0] != B:
+        raise _lib.AldmError(f"gate table has {gate.shape[0]} rows for {B} samples")
+    fn = getattr(_lib.load(), "aldm_attn_block64" + ("_fp8" if fp8 else "") + ("_gated" if gate is not None else ""))
     check(_launch(f"attn_block64{'_fp8' if fp8 else ''}_d{d}_n{N}", fl, 2.0 * (2 * B * N * Cc + 3 * Cc * Cc), lambda: fn(
         _p(x2d), _p(ln_parts), ln_parts.shape[1], _p(pw.w), pw.Kpad, _p(pw.bias), _p(pw.ln_s), _p(pw.lora_a), _p(pw.lora_b), pw.Rp,
-        getattr(pw, "ranks_used", 0) if pw.Rp else 0, _p(pw.ln_sa), _p(pw.ln_ca), pw.ln_eps, B, N, H, d, _p(out), _stream())),
+        getattr(pw, "ranks_used", 0) if pw.Rp else 0, _p(pw.ln_sa), _p(pw.ln_ca), pw.ln_eps, B, N, H, d, _p(out), _stream(),
+        *(() if gate is None else (_p(gate),)))),
         "aldm_attn_block64")
     return out
 

@@ -117,15 +117,83 @@ class AudioLDMPipeline:
             height = int(np.ceil(height / self.vae_scale_factor)) * self.vae_scale_factor
         return height, n_samples
 
-    def engine(self, batch, h, w, steps, guidance):
+    def engine(self, batch, h, w, steps, guidance, gated=False):
         # the scheduler is part of the key: a graph captured with one scheduler's update and coefficients must never replay for another
-        key = (batch, h, w, steps, float(guidance), type(self.scheduler).__name__, _frozen_config(self.scheduler))
+        # (gated: a graph whose fused-LoRA launches read a per-clip gate table is another graph than the plain single-adapter one)
+        key = (batch, h, w, steps, float(guidance), type(self.scheduler).__name__, _frozen_config(self.scheduler)) + ((True,) if gated else ())
         eng = self._engines.get(key)
         if eng is not None and (eng.unet is not self._unet or eng.scheduler is not self.scheduler or eng.stale()):
             eng = None                                  # weights / adapter / scheduler changed since the capture: never replay the old graph
         if eng is None:
-            eng = self._engines[key] = DenoiseEngine(self._unet, self.scheduler, batch, h, w, steps, guidance, device=self.device)
+            eng = self._engines[key] = DenoiseEngine(self._unet, self.scheduler, batch, h, w, steps, guidance, device=self.device, gated=gated)
         return eng
+
+    # ---- LoRA adapters (diffusers' surface) ----
+    def _peft(self):
+        from .lora import PeftModel
+        if not isinstance(self.unet, PeftModel):
+            for p in self.unet.parameters():
+                p.requires_grad_(False)
+            self.unet = PeftModel(self.unet, None)
+        return self.unet
+
+    def load_lora_weights(self, path_or_state_dict, adapter_name="default", r=None, lora_alpha=None, target_modules=None):
+        """A local .safetensors / .bin file or directory, or a state dict in peft's saved form or the diffusers form.  Rank and targets
+        are read from the tensors when not given; lora_alpha from an adapter_config.json next to the file, else = r.  Repacks the UNet's
+        operands (captured graphs are rebuilt on the next call); choosing between loaded adapters afterwards does not."""
+        from .lora import LoraConfig, _read_adapter_file, normalize_adapter_state_dict
+        sd, cfg_json = path_or_state_dict, None
+        if isinstance(sd, (str, os.PathLike)):
+            sd, cfg_json = _read_adapter_file(os.fspath(sd))
+        cfg = None
+        if r is not None or lora_alpha is not None or target_modules is not None:
+            t = normalize_adapter_state_dict(sd)
+            rr = r if r is not None else next(v.shape[0] for (m, ab), v in t.items() if ab == "A")
+            la = lora_alpha if lora_alpha is not None else (cfg_json or {}).get("lora_alpha", rr)
+            cfg = LoraConfig(r=rr, lora_alpha=la, init_lora_weights="gaussian",
+                             target_modules=list(target_modules) if target_modules is not None else sorted({m for m, _ in t}))
+        elif cfg_json is not None and "lora_alpha" in cfg_json:
+            t = normalize_adapter_state_dict(sd)
+            rr = next(v.shape[0] for (m, ab), v in t.items() if ab == "A")
+            cfg = LoraConfig(r=rr, lora_alpha=cfg_json["lora_alpha"], init_lora_weights="gaussian", target_modules=sorted({m for m, _ in t}))
+        self._peft().load_adapter(sd, adapter_name, cfg)
+
+    def set_adapters(self, names, adapter_weights=None):
+        self._unet.set_adapters(names, adapter_weights)
+
+    def get_active_adapters(self):
+        return list(self._unet.active_adapters) if self._unet.lora_enabled else []
+
+    def get_list_adapters(self):
+        return {"unet": self._unet.lora_adapters()}
+
+    def disable_lora(self):
+        self._unet.set_lora_enabled(False)
+
+    def enable_lora(self):
+        self._unet.set_lora_enabled(True)
+
+    def delete_adapters(self, names):
+        for n in ([names] if isinstance(names, str) else list(names)):
+            self._peft().delete_adapter(n)
+
+    def unload_lora_weights(self):
+        self.delete_adapters(self._unet.lora_adapters())
+
+    def _route(self, adapter_names, adapter_weights, n_prompts, num_waveforms_per_prompt):
+        """(gated?, per-clip adapter_names, per-clip adapter_weights): one entry per prompt, repeated over num_waveforms_per_prompt
+        like the prompt embeddings"""
+        u = self._unet
+        if adapter_names is not None:
+            if isinstance(adapter_names, (str, dict)) or len(adapter_names) != n_prompts:
+                raise ValueError(f"adapter_names needs one entry per prompt ({n_prompts}), got {adapter_names!r}")
+            adapter_names = [a for a in adapter_names for _ in range(num_waveforms_per_prompt)]
+        if adapter_weights is not None:
+            if len(adapter_weights) != n_prompts:
+                raise ValueError(f"adapter_weights needs one entry per prompt ({n_prompts})")
+            adapter_weights = [a for a in adapter_weights for _ in range(num_waveforms_per_prompt)]
+        gated = adapter_weights is not None or not u.routing_is_plain(adapter_names)
+        return gated, adapter_names, adapter_weights
 
     @staticmethod
     def _seed_engine(eng, generator):
@@ -147,7 +215,8 @@ class AudioLDMPipeline:
     @torch.no_grad()
     def __call__(self, prompt=None, audio_length_in_s=None, num_inference_steps=10, guidance_scale=2.5,
                  negative_prompt=None, num_waveforms_per_prompt=1, eta=0.0, generator=None, latents=None,
-                 prompt_embeds=None, negative_prompt_embeds=None, return_dict=True, output_type="np", **kw):
+                 prompt_embeds=None, negative_prompt_embeds=None, return_dict=True, output_type="np", adapter_names=None,
+                 adapter_weights=None, **kw):
         if self.device.type != "cuda":
             raise ops._lib.AldmError("AudioLDMPipeline runs on the MI355X only: call .to('cuda') (no CPU fallback)")
         if eta != 0.0:
@@ -171,7 +240,9 @@ class AudioLDMPipeline:
         self.scheduler.set_timesteps(num_inference_steps)       # (host-only) init_noise_sigma of a sigma-space scheduler depends on the schedule
         latents = latents.to(self.device, torch.float32) * self.scheduler.init_noise_sigma
 
-        eng = self.engine(batch, h, w, num_inference_steps, guidance_scale)
+        gated, adapter_names, adapter_weights = self._route(adapter_names, adapter_weights, batch // num_waveforms_per_prompt, num_waveforms_per_prompt)
+        eng = self.engine(batch, h, w, num_inference_steps, guidance_scale, gated=gated)
+        eng.set_adapters(adapter_names, adapter_weights)
         eng.set_condition(prompt_embeds, negative_prompt_embeds)
         self._seed_engine(eng, generator)
         eng.set_latents(latents)

@@ -11,6 +11,9 @@ script's inconsistent 4 (quirk Q3) -- pass --lora-alpha 4 to reproduce the scrip
 seeds both the initial noise and that in-loop stream.
 `--init-audio in.wav --strength 0.5` starts from a 16 kHz recording (AudioLDMAudioToAudioPipeline: style transfer toward the prompt);
 `--regenerate-seconds T0,T1` / `--regenerate-bands F0,F1` regenerate only that time span / fraction of the mel bins and keep the rest.
+`--lora NAME=PATH` (repeatable) loads named adapters side by side; `--adapters SPEC` routes them per prompt -- a comma list with one item
+per prompt (`--prompt` then takes prompts separated by `|`): `NAME`, `NAME:0.7`, `base`, or a blend `A:0.5+B:0.5`.  One call, one
+captured graph: the adapted and the original model of the reference's log_validation side by side.
 """
 import argparse
 import os
@@ -23,6 +26,35 @@ from ..audio2audio import AudioLDMAudioToAudioPipeline, regeneration_mask
 from ..pipeline import AudioLDMPipeline
 from ..scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
 from ..unet import UNet2DConditionModel
+
+
+def parse_adapters(spec):
+    """--adapters SPEC -> the pipeline's adapter_names: 'boom_bap,trap:0.7,base,a:0.5+b:0.5' ->
+    ['boom_bap', {'trap': 0.7}, '__base__', {'a': 0.5, 'b': 0.5}]"""
+    out = []
+    for item in spec.split(","):
+        item = item.strip()
+        if not item:
+            raise ValueError(f"--adapters: empty item in {spec!r}")
+        if item in ("base", "__base__"):
+            out.append("__base__")
+            continue
+        blend = {}
+        for part in item.split("+"):
+            name, sep, w = part.strip().partition(":")
+            if not name or name in ("base", "__base__"):
+                raise ValueError(f"--adapters: bad item {item!r} ('base' stands alone)")
+            try:
+                blend[name] = float(w) if sep else None
+            except ValueError:
+                raise ValueError(f"--adapters: weight of {name!r} in {item!r} is not a number")
+            if blend[name] is not None and not np.isfinite(blend[name]):
+                raise ValueError(f"--adapters: weight of {name!r} in {item!r} is not finite")
+        if len(blend) == 1 and next(iter(blend.values())) is None:
+            out.append(next(iter(blend)))
+        else:
+            out.append({n: (1.0 if w is None else w) for n, w in blend.items()})
+    return out
 
 
 def main(argv=None):
@@ -48,13 +80,19 @@ def main(argv=None):
     ap.add_argument("--strength", type=float, default=0.5, help="with --init-audio: how much of the schedule to run (1 = from noise)")
     ap.add_argument("--regenerate-seconds", default=None, help="with --init-audio: T0,T1 -- regenerate only this time span")
     ap.add_argument("--regenerate-bands", default=None, help="with --init-audio: F0,F1 -- regenerate only this fraction of the mel bins")
+    ap.add_argument("--lora", action="append", default=[], metavar="NAME=PATH",
+                    help="load a named adapter (.safetensors / .bin file or directory; repeatable).  Rank and targets come from the tensors")
+    ap.add_argument("--adapters", default=None, metavar="SPEC",
+                    help="per-prompt routing, one item per prompt (prompts separated by '|'): NAME, NAME:0.7, base, A:0.5+B:0.5")
     args = ap.parse_args(argv)
+    if args.adapters and not args.lora:
+        ap.error("--adapters needs --lora NAME=PATH")
     if args.init_audio is None and (args.regenerate_seconds or args.regenerate_bands):
         ap.error("--regenerate-seconds / --regenerate-bands need --init-audio")
 
     device = "cuda"
     unet = UNet2DConditionModel.from_pretrained(args.model_dir, subfolder="unet")
-    if not args.no_lora:
+    if not args.no_lora and not args.lora:
         unet_lora = get_peft_model(unet, LoraConfig(r=args.rank, lora_alpha=args.lora_alpha, init_lora_weights="gaussian",
                                                     target_modules=args.target_modules.split(",")))
         if args.lora_weights:
@@ -67,7 +105,27 @@ def main(argv=None):
         extra = {"final_sigmas_type": "sigma_min"} if args.scheduler == "dpmsolver" else {}
         pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, algorithm_type=args.scheduler,
                                                                  solver_order=args.solver_order, **extra)
+    for item in args.lora:
+        name, sep, path = item.partition("=")
+        if not sep or not name or not path:
+            ap.error(f"--lora expects NAME=PATH, got {item!r}")
+        pipe.load_lora_weights(path, adapter_name=name)
     generator = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
+    if args.adapters is not None:
+        routing = parse_adapters(args.adapters)
+        prompts = [p.strip() for p in args.prompt.split("|")]
+        if len(prompts) == 1:
+            prompts = prompts * len(routing)
+        audios = pipe(prompt=prompts, num_inference_steps=args.steps, adapter_names=routing,
+                      audio_length_in_s=10.0 if args.audio_length is None else args.audio_length,
+                      guidance_scale=args.guidance_scale, generator=generator).audios
+        from scipy.io import wavfile
+        stem, ext = os.path.splitext(os.path.abspath(args.output))
+        os.makedirs(os.path.dirname(stem), exist_ok=True)
+        for i, a in enumerate(audios):
+            wavfile.write(f"{stem}_{i}{ext or '.wav'}", 16000, np.asarray(a, dtype=np.float32))
+        print(f"Generated {len(audios)} clips saved to: {stem}_*{ext or '.wav'}")
+        return
     if args.init_audio is None:
         audio = pipe(prompt=args.prompt, num_inference_steps=args.steps,
                      audio_length_in_s=10.0 if args.audio_length is None else args.audio_length,

@@ -285,9 +285,22 @@ def t_lora_linear(tape, x, site, res=None, tok=None, rowstats=False):
 
 
 def _lin_parts(mod, row0):
-    if isinstance(mod, LoraLinear):
-        return (row0, mod.base_layer.out_features, mod.lora_A["default"].weight, mod.lora_B["default"].weight, mod.scaling)
+    if isinstance(mod, LoraLinear) and mod.adapters:
+        (name,) = mod.adapters                               # (single adapter: _check_single_adapter)
+        return (row0, mod.base_layer.out_features, mod.lora_A[name].weight, mod.lora_B[name].weight, mod.scale[name])
     return None
+
+
+def _check_single_adapter(unet):
+    """Training stays single-adapter: it trains the one adapter of the model and refuses a model that holds several adapters or on
+    which a gate (weights, disabled adapters) is set -- the training launches carry no gate table."""
+    names = unet.lora_adapters()
+    if len(names) > 1:
+        raise ops._lib.AldmError(f"LoraTrainer trains one adapter; this model holds {names} -- delete_adapter() the others "
+                                 "(fine-tuning one adapter next to frozen ones is not supported)")
+    if not unet.routing_is_plain():
+        raise ops._lib.AldmError("LoraTrainer: the model's adapter routing is not the plain one (set_adapters weights / disable_adapter); "
+                                 "training runs the adapter at weight 1 without a gate table")
 
 
 def _base(mod):
@@ -380,6 +393,7 @@ def trainer_of(unet, create=True):
         else:
             tr = LoraTrainer(unet, None, use_graph=False)
     elif tr is not None:
+        _check_single_adapter(unet)
         tr._ensure_fresh()
     return tr
 
@@ -402,6 +416,7 @@ class LoraTrainer:
         self.world = self.dist.get_world_size() if self.dist else 1
         if not any("lora_" in n for n, _ in unet.named_parameters()):
             raise ops._lib.AldmError("LoraTrainer: the UNet carries no LoRA parameters (call get_peft_model first)")
+        _check_single_adapter(unet)
         self.flat = FlatLora(unet, self.dev)
         self.flat.on_change = unet.invalidate_packed         # an optimiser update makes the UNet's inference plan stale
         self.use_graph, self.graph, self._static, self._eager_steps = use_graph, None, None, 0

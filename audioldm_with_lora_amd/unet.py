@@ -28,7 +28,7 @@ from torch import nn
 from . import ops
 from ._lib import ACT_NONE, ACT_SILU
 from .configs import UNET
-from .lora import LoraLinear
+from .lora import GATE_COLS, AdapterRouting, LoraLinear, lora_layout
 
 
 # ----------------------------------------------------------------------------------------------
@@ -154,11 +154,11 @@ def _f32(t):
 
 
 def _lin(mod):
-    """(weight, bias, lora) of an nn.Linear or a LoraLinear wrapper."""
+    """(weight, bias, lora) of an nn.Linear or a LoraLinear wrapper; lora = [(adapter, A, B, scaling)], one per adapter on the layer."""
     if isinstance(mod, LoraLinear):
         b = mod.base_layer
-        return b.weight, b.bias, (mod.lora_A["default"].weight, mod.lora_B["default"].weight, mod.scaling)
-    return mod.weight, mod.bias, None
+        return b.weight, b.bias, mod.parts()
+    return mod.weight, mod.bias, []
 
 
 def pack_resnet(r: ResnetBlock2D):
@@ -181,9 +181,10 @@ def pack_resnet(r: ResnetBlock2D):
 LN_FOLD_MIN_C = 64
 
 
-def pack_attention(a: Attention, ln=None):
+def pack_attention(a: Attention, ln=None, layout=None):
     """ln = (gamma, beta) of the LayerNorm feeding this attention: folded into the fused QKV GEMM when the LDS-DMA
-    path can take it (C % 64 == 0); the caller then passes the RAW hidden state."""
+    path can take it (C % 64 == 0); the caller then passes the RAW hidden state.  layout = the model's LoRA column layout
+    (lora.lora_layout): every adapter's to_q | to_k | to_v (and to_out.0) rows go into that adapter's column block."""
     wq, bq, lq = _lin(a.to_q)
     wk, bk, lk = _lin(a.to_k)
     wv, bv, lv = _lin(a.to_v)
@@ -195,16 +196,16 @@ def pack_attention(a: Attention, ln=None):
     qs = ops.LOG2E / math.sqrt(a.dim_head)
     wq = wq.detach().float() * qs
     bq = None if bq is None else bq.detach().float() * qs
-    lq = None if lq is None else (lq[0], lq[1], lq[2] * qs)
+    lq = [(n, A, Bm, sc * qs) for n, A, Bm, sc in lq]
     bias = None
     if bq is not None:
         bias = torch.cat([bq, bk.detach().float(), bv.detach().float()])
     fold = ln is not None and c % 64 == 0 and c >= LN_FOLD_MIN_C
     wqkv = torch.cat([wq, wk.detach().float(), wv.detach().float()])
     qkv = ops.pack_linear_ln(wqkv, bias, ln[0], ln[1]) if fold else ops.pack_linear(wqkv, bias)
-    ops.attach_lora(qkv, [None if l is None else (i * c, c, l[0], l[1], l[2]) for i, l in enumerate((lq, lk, lv))])
+    ops.attach_lora(qkv, [(i * c, c, A, Bm, sc, n) for i, l in enumerate((lq, lk, lv)) for n, A, Bm, sc in l], layout)
     out = ops.pack_linear(wo, bo)
-    ops.attach_lora(out, [None if lo is None else (0, wo.shape[0], lo[0], lo[1], lo[2])])
+    ops.attach_lora(out, [(0, wo.shape[0], A, Bm, sc, n) for n, A, Bm, sc in lo], layout)
     return SimpleNamespace(qkv=qkv, out=out, heads=a.heads, d=a.dim_head, c=c, ln_folded=fold)
 
 
@@ -222,7 +223,7 @@ def _merge_ff2_proj_out(t: Transformer2DModel):
     return ops.pack_conv(wm[:, :, None, None].contiguous(), (wp @ b2 + bp).contiguous())
 
 
-def pack_transformer(t: Transformer2DModel):
+def pack_transformer(t: Transformer2DModel, layout=None):
     blk = t.transformer_blocks[0]
     merged = (t.channels % 64 == 0 and not isinstance(blk.ff.net[2], LoraLinear) and not isinstance(t.proj_out, LoraLinear))
     return SimpleNamespace(
@@ -230,8 +231,8 @@ def pack_transformer(t: Transformer2DModel):
         gn_g=_f32(t.norm.weight), gn_b=_f32(t.norm.bias), groups=t.groups,
         proj_in=ops.pack_conv(t.proj_in.weight, t.proj_in.bias), proj_out=ops.pack_conv(t.proj_out.weight, t.proj_out.bias),
         ln=[(_f32(n.weight), _f32(n.bias)) for n in (blk.norm1, blk.norm2, blk.norm3)],
-        attn1=pack_attention(blk.attn1, (blk.norm1.weight, blk.norm1.bias)),
-        attn2=pack_attention(blk.attn2, (blk.norm2.weight, blk.norm2.bias)),
+        attn1=pack_attention(blk.attn1, (blk.norm1.weight, blk.norm1.bias), layout),
+        attn2=pack_attention(blk.attn2, (blk.norm2.weight, blk.norm2.bias), layout),
         ff1=(ops.pack_linear_ln(blk.ff.net[0].proj.weight, blk.ff.net[0].proj.bias, blk.norm3.weight, blk.norm3.bias, geglu=True)
              if (t.channels % 64 == 0 and t.channels >= LN_FOLD_MIN_C) else ops.pack_geglu(blk.ff.net[0].proj.weight, blk.ff.net[0].proj.bias)),
         ff2=ops.pack_linear(blk.ff.net[2].weight, blk.ff.net[2].bias))
@@ -352,7 +353,7 @@ def run_transformer(P, x, fp8=False, xn=None, defer=None):
 
 
 # ----------------------------------------------------------------------------------------------
-class UNet2DConditionModel(nn.Module):
+class UNet2DConditionModel(AdapterRouting, nn.Module):
     config_name = "config.json"
 
     def __init__(self, **cfg_over):
@@ -414,7 +415,7 @@ class UNet2DConditionModel(nn.Module):
         return m
 
     def _has_trainable_lora(self):
-        return any(isinstance(m, LoraLinear) and m.lora_A["default"].weight.requires_grad for m in self.modules())
+        return any(isinstance(m, LoraLinear) and any(a.weight.requires_grad for a in m.lora_A.values()) for m in self.modules())
 
     def invalidate_packed(self):
         """Forget the packed bf16 operands: call after ANY change of parameter values the module hooks cannot see (in-place
@@ -449,6 +450,7 @@ class UNet2DConditionModel(nn.Module):
         if dev.type != "cuda":
             raise ops._lib.AldmError("UNet2DConditionModel runs on the MI355X only: call .to('cuda') first (no CPU fallback)")
         P = SimpleNamespace()
+        layout = P.lora_layout = lora_layout(self)          # one column layout for every fused GEMM (multi-adapter routing)
         P.te1 = ops.pack_linear(self.time_embedding.linear_1.weight, self.time_embedding.linear_1.bias)
         P.te2 = ops.pack_linear(self.time_embedding.linear_2.weight, self.time_embedding.linear_2.bias)
         P.cls = ops.pack_linear(self.class_embedding.weight, self.class_embedding.bias)
@@ -463,15 +465,15 @@ class UNet2DConditionModel(nn.Module):
         P.down = []
         for blk in self.down_blocks:
             b = SimpleNamespace(resnets=[res(r) for r in blk.resnets],
-                                attns=[pack_transformer(t) for t in blk.attentions] if blk.has_attn else None,
+                                attns=[pack_transformer(t, layout) for t in blk.attentions] if blk.has_attn else None,
                                 down=ops.pack_conv(blk.downsamplers[0].conv.weight, blk.downsamplers[0].conv.bias) if blk.has_down else None)
             P.down.append(b)
         P.mid = SimpleNamespace(resnets=[res(r) for r in self.mid_block.resnets],
-                                attns=[pack_transformer(self.mid_block.attentions[0])])
+                                attns=[pack_transformer(self.mid_block.attentions[0], layout)])
         P.up = []
         for blk in self.up_blocks:
             b = SimpleNamespace(resnets=[res(r) for r in blk.resnets],
-                                attns=[pack_transformer(t) for t in blk.attentions] if blk.has_attn else None,
+                                attns=[pack_transformer(t, layout) for t in blk.attentions] if blk.has_attn else None,
                                 up=ops.pack_conv(blk.upsamplers[0].conv.weight, blk.upsamplers[0].conv.bias) if blk.has_up else None)
             P.up.append(b)
         # all time_emb_proj layers as one GEMM: rows concatenated in forward order
@@ -505,10 +507,35 @@ class UNet2DConditionModel(nn.Module):
         semb = torch.cat([e2[:, None, :].expand(n, b, ted), c[None].expand(n, b, ted)], dim=2).reshape(n * b, 2 * ted).contiguous()
         return ops.linear(semb, P.temb_all, out_f32=True).view(n, b, P.temb_total)
 
-    def forward_nhwc(self, x, t_dev, class_labels_bf16, rowbias=None):
+    def forward_nhwc(self, x, t_dev, class_labels_bf16, rowbias=None, gate=None):
         """x [b, H, W, Cin] bf16 channels-last, t_dev fp32 [1] or [b] (device), class_labels [b, D] bf16.
         rowbias: optional precomputed time-embedding projections [b, temb_total] fp32 (temb_table); t_dev / class_labels are
-        then unused.  Returns eps fp32 [b, H, W, Cout]."""
+        then unused.  gate: fp32 [b][32] device gate table (device_gate / gate_table), None = ungated launches.
+        Returns eps fp32 [b, H, W, Cout]."""
+        if gate is not None and tuple(gate.shape) != (x.shape[0], GATE_COLS):
+            raise ValueError(f"gate table must be [{x.shape[0]}][{GATE_COLS}], got {tuple(gate.shape)}")
+        with ops.lora_gate_scope(gate):
+            return self._forward_nhwc(x, t_dev, class_labels_bf16, rowbias)
+
+    def device_gate(self, adapter_names=None, batch=1, adapter_weights=None, **kw):
+        """The gate table of a pass on the model's device, or None when the pass needs none (routing_is_plain: the launches are then
+        exactly the single-adapter ones).  adapter_weights: optional per-prompt factors on top of the entries' own weights."""
+        if adapter_weights is None and self.routing_is_plain(adapter_names):
+            return None
+        g = self.gate_table(adapter_names, batch, **kw)
+        if adapter_weights is not None:
+            w = torch.as_tensor(adapter_weights, dtype=torch.float32).reshape(-1)
+            if not bool(torch.isfinite(w).all()):
+                raise ValueError("adapter_weights must be finite")
+            reps = g.shape[0] // max(1, w.numel())
+            if w.numel() * reps != g.shape[0]:
+                raise ValueError(f"adapter_weights needs one entry per prompt, got {w.numel()} for a batch of {g.shape[0]}")
+            nw = kw.get("num_waveforms_per_prompt", 1)
+            w = w.repeat_interleave(nw)
+            g = g * (torch.cat([w, w]) if kw.get("do_classifier_free_guidance") else w)[:, None]
+        return g.to(self.conv_in.weight.device).contiguous()
+
+    def _forward_nhwc(self, x, t_dev, class_labels_bf16, rowbias=None):
         ops.drop_pending(x)
         cfg, P = self.cfg, self.plan()
         fp8 = bool(getattr(self, "attention_fp8", False))       # BASELINE config 5: e4m3 Q / K / V / P attention operands
@@ -583,8 +610,11 @@ class UNet2DConditionModel(nn.Module):
         return ops.conv(h, P.conv_out, pad=(1, 1), out_f32=True)
 
     def forward(self, sample, timestep, encoder_hidden_states=None, class_labels=None, cross_attention_kwargs=None,
-                return_dict=False, **kw):
-        """diffusers signature: NCHW `sample`, scalar / [b] `timestep`, `class_labels` [b, D]."""
+                return_dict=False, adapter_names=None, adapter_weights=None, **kw):
+        """diffusers signature: NCHW `sample`, scalar / [b] `timestep`, `class_labels` [b, D].
+        adapter_names: one entry per sample -- an adapter's name, "__base__", a list of names or a dict name -> weight (a blend); None =
+        the active adapters with their set weights for every sample (peft's mixed-adapter batches).  adapter_weights: optional factor
+        per sample."""
         assert encoder_hidden_states is None, "AudioLDM conditions through class_labels only"
         if not sample.is_cuda:
             raise ops._lib.AldmError("UNet2DConditionModel.forward needs CUDA/HIP tensors (no CPU fallback)")
@@ -594,7 +624,10 @@ class UNet2DConditionModel(nn.Module):
         t = timestep.to(device=sample.device, dtype=torch.float32).reshape(-1)
         if t.numel() not in (1, b):
             raise ValueError("timestep must be a scalar or have one entry per sample")
+        gate = self.device_gate(adapter_names, b, adapter_weights)
         if self.training and torch.is_grad_enabled() and self._has_trainable_lora():
+            if gate is not None:
+                raise ops._lib.AldmError("training runs the single active adapter: no adapter_names / weights / several adapters")
             # the reference's training call [REF train:479,539-546]: return a tensor autograd can differentiate -- forward and
             # backward both run on the HIP launch tape (training._UNetTrainFn)
             from .training import trainer_of
@@ -602,7 +635,7 @@ class UNet2DConditionModel(nn.Module):
             return SimpleNamespace(sample=out) if return_dict else (out,)
         x = ops.nchw_to_nhwc(sample.float())
         cls_bf16 = ops.f32_to_bf16(class_labels.to(device=sample.device, dtype=torch.float32).contiguous())
-        eps = self.forward_nhwc(x, t.contiguous(), cls_bf16)
+        eps = self.forward_nhwc(x, t.contiguous(), cls_bf16, gate=gate)
         out = ops.nhwc_to_nchw_f32(eps).to(sample.dtype)
         if return_dict:
             return SimpleNamespace(sample=out)

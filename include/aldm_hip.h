@@ -130,6 +130,12 @@ typedef struct {
      0 = auto: weight-stationary iff the launch is not split-K and the weight matrix is larger than the activation image (measured:
      csrc/igemm.hip).  Speed only; results are identical. */
   int xcd_map;
+  /* Multi-adapter routing (LAST: no existing offset moves).  lora_a / lora_b hold several adapters side by side (adapter a owns a block
+     of the Rp columns of T = x A_cat^T); lora_gate is fp32 [M / gate_rows][Rp], one row per sample, and T[m][j] is multiplied by
+     lora_gate[m / gate_rows][j] in fp32 before it is rounded to bf16:  y[b] = W x[b] + sum_a gate[b][a] (alpha_a / r_a) B_a (A_a x[b]).
+     gate_rows = rows of the GEMM per sample (must divide M).  NULL = ungated: the launch is exactly the one without these fields.
+     Not combined with lora_t_out. */
+  const float* lora_gate; int gate_rows;
 } aldm_igemm_t;
 
 enum { ALDM_TILE_AUTO = 0, ALDM_TILE_128x128 = 1, ALDM_TILE_64x64 = 2, ALDM_TILE_128x64 = 3, ALDM_TILE_64x128 = 4,
@@ -187,6 +193,7 @@ typedef struct {
   int waves;
   void* lora_t_out;         /* optional [M][Rp] bf16 copy of T = x A^T (the LoRA trainer saves it for dB = s dY^T T), as aldm_igemm_t */
   int vt_dual;              /* columns >= vt_col0 (which may then be 0) are stored token-major in vt AND row-major in out (as aldm_igemm_t) */
+  const float* lora_gate; int gate_rows;   /* multi-adapter routing, as aldm_igemm_t (LAST: no existing offset moves) */
 } aldm_pgemm_t;
 
 int aldm_pgemm_supported(int K);
@@ -282,6 +289,17 @@ int aldm_attn_block64(const void* x, const float* ln_parts, int ln_nparts, const
 int aldm_attn_block64_fp8(const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
                           const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used, const float* ln_sa,
                           const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out, void* stream);
+/* Multi-adapter routing for the block kernels: the same launches plus lora_gate, fp32 [B][Rp] -- row b gates the LoRA columns of sample
+   b's workgroups (see aldm_igemm_t.lora_gate); Rp != 0 and a non-null table are required. */
+int aldm_attn_block64_gated(const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
+                            const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used, const float* ln_sa,
+                            const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out, void* stream, const float* lora_gate);
+int aldm_attn_block64_fp8_gated(const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
+                                const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used, const float* ln_sa,
+                                const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out, void* stream, const float* lora_gate);
+int aldm_attn_block256_gated(const void* x, const float* ln_parts, int ln_nparts, const void* w, int Kpad, const float* bias,
+                             const float* ln_s, const void* lora_a, const void* lora_b, int Rp, int ranks_used, const float* ln_sa,
+                             const float* ln_ca, float ln_eps, int B, int N, int H, int d, void* out, void* stream, const float* lora_gate);
 
 /* The same launch for the UNet's 252-token level (C = 384 = 8 heads x 48, N <= 256 tokens per sample: 63 x 4 for a 10 s clip, 64 x 4 in
    training): a (sample, head) workgroup of 8 waves keeps its tokens of X in registers, streams the head's 144 weight rows once and runs
