@@ -11,6 +11,8 @@ LIB_PATH = os.environ.get("ALDM_LIB") or os.path.join(_HERE, "libaldm_hip.so")  
 ACT_NONE, ACT_SILU, ACT_LRELU, ACT_TANH, ACT_GELU = 0, 1, 2, 3, 4
 OUT_BF16, OUT_F32 = 0, 1
 TILE_AUTO, TILE_128x128, TILE_64x64, TILE_128x64, TILE_64x128 = 0, 1, 2, 3, 4
+DEFER_ROWMAJOR, DEFER_PLANAR, DEFER_WRITE_THROUGH = 1, 2, 4     # aldm_igemm_t.defer_reduce flags
+SLAB_ROWMAJOR, SLAB_PLANAR = 0, 1                               # slab layout as aldm_groupnorm_partials_layout is told it
 
 
 class IgemmArgs(C.Structure):
@@ -94,6 +96,10 @@ PROTOTYPES = {
     "aldm_groupnorm_partials": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "aldm_groupnorm_partials_layout": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "aldm_igemm_slab_offset": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "aldm_groupnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "aldm_groupnorm_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,

@@ -33,17 +33,45 @@ extern "C" size_t aldm_igemm_workspace_bytes(const aldm_igemm_t* p) {
   return (size_t)p->splits * M * p->Cout * sizeof(float);
 }
 
+static bool is_halo_tile(int tile) {
+  return tile == ALDM_TILE_HALO_128x128 || tile == ALDM_TILE_HALO_64x128 || tile == ALDM_TILE_HALO_128x128_WS || tile == ALDM_TILE_HALO_64x128_WS;
+}
+
+// THE split rule, for aldm_igemm_effective_splits and for the launch itself (a consumer that sums a different number of slabs than the
+// launch wrote reads stale data -- or, with planar slabs, another image's).  nkt = K-tiles of the whole launch including the fused
+// x3 | x4 segment, nch = 64-channel chunks of the first source pair.  Generic clamp first (as every tile), then the halo tiles' per-chunk
+// rule on the clamped count: they split by whole chunks (a chunk's halo serves its KH * KW taps in one workgroup).
+static void plan_splits(int want, int nkt, int nch, int taps, bool halo, int& splits, int& kt_per_split) {
+  splits = want > 1 ? want : 1;
+  if (splits > nkt) splits = nkt;
+  kt_per_split = cdiv(nkt, splits);
+  splits = cdiv(nkt, kt_per_split);
+  if (halo && splits > 1) {
+    const int cps = cdiv(nch, splits > nch ? nch : splits);
+    kt_per_split = taps * cps;
+    splits = cdiv(nch, cps);
+  }
+}
+
 extern "C" int aldm_igemm_effective_splits(const aldm_igemm_t* p) {
   if (!p || p->splits <= 1) return 1;
   const int nkt = cdiv(p->KH * p->KW * (p->Cin + p->Cin2), BK) + (p->x3 ? (p->Cin3 + (p->x4 ? p->Cin4 : 0)) / BK : 0);
-  if (p->tile == ALDM_TILE_HALO_128x128 || p->tile == ALDM_TILE_HALO_64x128 || p->tile == ALDM_TILE_HALO_128x128_WS ||
-      p->tile == ALDM_TILE_HALO_64x128_WS) {   // the halo tiles split by 64-channel chunk (9 taps each)
-    const int nch = (p->Cin + p->Cin2) / BK;
-    return cdiv(nch, cdiv(nch, p->splits > nch ? nch : p->splits));
-  }
-  int splits = p->splits > nkt ? nkt : p->splits;
-  const int per = cdiv(nkt, splits);
-  return cdiv(nkt, per);
+  int splits, per;
+  plan_splits(p->splits, nkt, (p->Cin + p->Cin2) / BK, p->KH * p->KW, is_halo_tile(p->tile), splits, per);
+  return splits;
+}
+
+// Element offset, inside the workspace of a split-K launch over B images of HW pixels and C channels, of channel n of output row m in
+// slab `split` -- the arithmetic of the kernels' slab stores (igemm_slab_index behind the same magic-number division), on the host, so
+// that the layouts can be checked without a GPU.  layout: 0 row-major, 1 quad-planar.  -1 for an argument out of range.
+extern "C" long long aldm_igemm_slab_offset(int layout, int B, int HW, int C, int split, int m, int n) {
+  if (layout < 0 || layout > 1 || B <= 0 || HW <= 0 || C <= 0 || (C & 3) || split < 0 || m < 0 || n < 0 || n >= C ||
+      (long long)B * HW > 0x7fffffffll || m >= B * HW)
+    return -1;
+  const FastDiv fd = make_fastdiv((unsigned)HW);
+  const int b = (int)(((((unsigned long long)(unsigned)m * fd.mul) >> 32) + (unsigned)m) >> fd.shift);   // fdiv() without __umulhi
+  const int pix = m - b * HW;
+  return (long long)split * B * HW * C + (layout ? igemm_slab_index(1, b, pix, n, C, HW) : igemm_slab_index(0, 0, m, n, C, 0));
 }
 
 extern "C" int aldm_igemm(const aldm_igemm_t* p, void* stream) {
@@ -76,6 +104,7 @@ extern "C" int aldm_igemm(const aldm_igemm_t* p, void* stream) {
   ALDM_CHECK_ARG(!p->vt || p->vt_col0 > 0 || p->out, "igemm: out required");
   ALDM_CHECK_ARG(p->splits <= 1 || (p->workspace && p->Cout % 4 == 0), "igemm: split-K needs workspace and Cout %% 4 == 0");
   ALDM_CHECK_ARG(p->out_ld > 0, "igemm: out_ld");
+  ALDM_CHECK_ARG(p->defer_reduce >= 0 && p->defer_reduce <= 7 && (!(p->defer_reduce & 6) || (p->defer_reduce & 1)), "igemm: defer_reduce is a set of ALDM_DEFER_* flags");
   ALDM_CHECK_ARG(!p->defer_reduce || (!p->geglu && !p->res2 && !p->out2 && p->out_act == ALDM_ACT_NONE && p->post_act == ALDM_ACT_NONE && p->alpha == 1.f),
                  "igemm: defer_reduce leaves bias / row bias / res to the consumer and supports nothing else in the epilogue");
   ALDM_CHECK_ARG(!(p->geglu && p->out2) || (p->Rp == 0 && p->splits <= 1 && !p->res && !p->res2 && p->out_dtype == ALDM_OUT_BF16 &&
@@ -112,11 +141,12 @@ extern "C" int aldm_igemm(const aldm_igemm_t* p, void* stream) {
   d.x3 = (const bf16*)p->x3; d.x4 = (const bf16*)p->x4; d.Cin3 = p->x3 ? p->Cin3 : 0; d.Cin4 = (p->x3 && p->x4) ? p->Cin4 : 0;
   d.C3tot = d.Cin3 + d.Cin4;
   d.nkt = cdiv(Ktot, BK) + d.C3tot / BK;
-  d.splits = p->splits > 1 ? p->splits : 1;
-  if (d.splits > d.nkt) d.splits = d.nkt;
-  d.kt_per_split = cdiv(d.nkt, d.splits);
-  d.splits = cdiv(d.nkt, d.kt_per_split);
+  const int tile = p->tile ? p->tile : pick_tile(p->B * p->OH * p->OW, p->Cout);
+  plan_splits(p->splits, d.nkt, Ctot / BK, p->KH * p->KW, is_halo_tile(tile), d.splits, d.kt_per_split);
   d.ws_rows = d.M;
+  // slab layout / store policy of a deferred reduce (the in-library reduce reads row-major slabs: flags only with defer_reduce)
+  d.ws_mode = (d.splits > 1 && p->defer_reduce) ? (p->defer_reduce >> 1) & 3 : 0;
+  if ((long long)p->B * p->OH * p->OW * p->Cout * 4 >= 0x80000000ll) d.ws_mode &= ~2;   // write-through stores take 32-bit byte offsets into a slab
   d.lora_gate = p->lora_gate; d.fd_gate = make_fastdiv((unsigned)(p->lora_gate ? p->gate_rows : 1)); d.gate_m1 = d.M - 1;
   d.tiles_n = 0; d.tiles_m = 0; d.nwg = 0;
   ALDM_CHECK_ARG(p->xcd_map >= 0 && p->xcd_map <= 2, "igemm: xcd_map must be 0 (auto), 1 (activation-stationary) or 2 (weight-stationary)");
@@ -159,7 +189,6 @@ extern "C" int aldm_igemm(const aldm_igemm_t* p, void* stream) {
   }
   hipStream_t st = (hipStream_t)stream;
 
-  int tile = p->tile ? p->tile : pick_tile(d.M, d.N);
   if (p->gnin_gamma) {
     ALDM_CHECK_ARG(tile == ALDM_TILE_HALO_128x128 || tile == ALDM_TILE_HALO_64x128 || tile == ALDM_TILE_HALO_128x128_WS || tile == ALDM_TILE_HALO_64x128_WS, "igemm: gnin_* (GroupNorm of the input inside the launch) needs a halo tile");
     const int Ct = p->Cin + p->Cin2;
@@ -193,12 +222,7 @@ extern "C" int aldm_igemm(const aldm_igemm_t* p, void* stream) {
         aldm_set_error("igemm: the halo tiles take no LoRA / V^T / row statistics (and a second-source segment only in the wave-specialised forms)");
         return ALDM_E_UNSUPPORTED;
       }
-      if (d.splits > 1) {   // split-K by whole 64-channel chunks: a chunk's halo serves its nine taps in one workgroup
-        const int nch = (d.Cin + d.Cin2) / BK;
-        const int cps = cdiv(nch, d.splits > nch ? nch : d.splits);
-        d.kt_per_split = d.KH * d.KW * cps;
-        d.splits = cdiv(nch, cps);
-      }
+      // (split-K by whole 64-channel chunks: plan_splits above)
       rc = aldm_launch_halo(d, tile, p->ring, st);
       break;
     default: aldm_set_error("igemm: unknown tile %d", tile); return ALDM_E_UNSUPPORTED;

@@ -77,7 +77,31 @@ struct IgemmDev {
   const float* lora_gate;     // multi-adapter routing: fp32 [M / gate_rows][RP] per-sample gates of the T columns; null = ungated
   FastDiv fd_gate;            // / gate_rows (rows of the GEMM per sample)
   int gate_m1;                // M - 1 of the launch: rows past the end (never stored) read the last sample's gates
+  // (split-K epilogue only)
+  int ws_mode;                // bit 0: quad-planar slabs (igemm_slab_index) for a deferred reduce; bit 1: write-through slab stores
 };
+
+// ---- split-K slab layouts ----------------------------------------------------------------------------------------
+// Element index of channel quad n / 4 of output row m = b * HW + pix inside ONE fp32 slab of M * N elements.
+//   row-major    [M][N]               -- what igemm_reduce_kernel (and the backward GroupNorm) read
+//   quad-planar  [B][N / 4][HW][4]    -- a 4-channel quad of all pixels of one image is one run of HW * 16 bytes, so the Cg channels one
+//                                        (image, group) workgroup of the deferred GroupNorm sums are Cg / 4 contiguous runs instead of a
+//                                        Cg * 4-byte piece out of every N * 4-byte row.  Needs only HW at the producer.
+// Both are bijections of [0, M) x {0, 4, .. N - 4} x [0, 4) onto [0, M * N) (N % 4 == 0); host + device, so that the host can check it.
+__host__ __device__ __forceinline__ long long igemm_slab_index(int planar, int b, int pix, int n, int N, int HW) {
+  return planar ? ((long long)(b * (N >> 2) + (n >> 2)) * HW + pix) * 4 + (n & 3) : ((long long)b * HW + pix) * N + n;
+}
+// one 16-byte slab store: plain, or write-through (sc1: the line leaves for memory while the kernel still runs instead of staying dirty
+// in this XCD's L2 until the kernel boundary's write-back; the only reader is the NEXT launch, on any XCD)
+__device__ __forceinline__ void igemm_slab_store4(float* slab, long long idx, const f32x4 v, bool wt, unsigned slab_bytes) {
+  if (wt) {
+    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(slab, 0, slab_bytes, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs, (int)(idx * 4), 0, 16);   // aux 16 = sc1
+  } else {
+    *reinterpret_cast<f32x4*>(slab + idx) = v;
+  }
+}
 
 __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 
@@ -297,13 +321,21 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmDev& p, f32x4 (&acc)[M
     // Split-K partial tile straight from the accumulators: with the swapped MFMA a lane holds 4 consecutive channels of one pixel row, so
     // the fp32 partials leave as 16-byte stores (four lanes = 64 contiguous bytes of a row) without the LDS transposition and its two
     // barriers -- the consumer (igemm_reduce_kernel / the deferred GroupNorm) reads the slab row-major either way.
+    // Quad-planar slabs (ws_mode bit 0, deferred reduces): the 16 `lrow` lanes of a quad column are 256 contiguous bytes of one plane.
+    float* slab = p.ws + (long long)split * p.ws_rows * p.N;
+    const int planar = p.ws_mode & 1;
+    const bool wt = (p.ws_mode & 2) != 0;
+    const unsigned slab_bytes = (unsigned)p.ws_rows * (unsigned)p.N * 4u;   // (write-through: < 2 GiB, host-checked)
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
       const int m = m0 + wm_off + i * 16 + lrow;
+      int b = 0, pix = m;
+      if (planar) { b = fdiv(m, p.fd_ohw); pix = m - b * p.OHW; }
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
         const int n = n0 + wn_off + j * 16 + lq * 4;
-        if (m < p.M && n < p.N) *reinterpret_cast<f32x4*>(p.ws + ((long long)split * p.ws_rows + m) * p.N + n) = acc[i][j];   // (N % 4 == 0, host-checked)
+        if (m < p.M && n < p.N)   // (N % 4 == 0, host-checked)
+          igemm_slab_store4(slab, igemm_slab_index(planar, b, pix, n, p.N, planar ? p.OHW : 0), acc[i][j], wt, slab_bytes);
       }
     }
     return;
@@ -554,8 +586,20 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmDev& p, f32x4 (&acc)[M
       const int r = g / (BN / 8), c = (g - r * (BN / 8)) * 8;
       const int m = m0 + r, n = n0 + c;
       if (m >= p.M || n >= p.N) continue;
-      float* o = p.ws + ((long long)split * p.ws_rows + m) * p.N + n;
       const float* src = Cs + r * E::LD + c;
+      if (p.ws_mode) {                                         // quad-planar and / or write-through slabs: whole quads (N % 4 == 0)
+        float* slab = p.ws + (long long)split * p.ws_rows * p.N;
+        const int planar = p.ws_mode & 1;
+        const bool wt = (p.ws_mode & 2) != 0;
+        const unsigned slab_bytes = (unsigned)p.ws_rows * (unsigned)p.N * 4u;
+        int b = 0, pix = m;
+        if (planar) { b = fdiv(m, p.fd_ohw); pix = m - b * p.OHW; }
+        igemm_slab_store4(slab, igemm_slab_index(planar, b, pix, n, p.N, planar ? p.OHW : 0), *reinterpret_cast<const f32x4*>(src), wt, slab_bytes);
+        if (n + 4 < p.N)
+          igemm_slab_store4(slab, igemm_slab_index(planar, b, pix, n + 4, p.N, planar ? p.OHW : 0), *reinterpret_cast<const f32x4*>(src + 4), wt, slab_bytes);
+        continue;
+      }
+      float* o = p.ws + ((long long)split * p.ws_rows + m) * p.N + n;
       if (n + 7 < p.N) {
         *reinterpret_cast<f32x4*>(o) = *reinterpret_cast<const f32x4*>(src);
         *reinterpret_cast<f32x4*>(o + 4) = *reinterpret_cast<const f32x4*>(src + 4);

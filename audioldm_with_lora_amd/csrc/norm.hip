@@ -180,7 +180,10 @@ __global__ __launch_bounds__(GN_THREADS) void groupnorm_reg_kernel(const bf16* _
 // GroupNorm(+SiLU) over split-K partial tiles (aldm_groupnorm_partials): the strip is summed out of the fp32 workspace
 // [splits][B*HW][C] in split order (as igemm_reduce_kernel sums), bias and the per-image row bias (the time-embedding
 // projection of ResnetBlock2D) are added, and the fp32 strip stays in registers for the statistics.
-template <int QPT>
+// PLANAR: the slabs are quad-planar, [splits][B][C / 4][HW][4] (igemm_slab_index in igemm_core.h): the group's strip is Cg / 4 runs of
+// HW * 16 bytes per slab instead of Cg * 4 bytes out of every C * 4-byte row.  Only the slab address changes -- a thread's unit is still
+// one quad of one pixel and the partials are added in the same order, so both layouts give the same bits.
+template <int QPT, bool PLANAR>
 __global__ __launch_bounds__(GN_THREADS) void groupnorm_partials_kernel(const float* __restrict__ ws, int splits, long long sstride,
                                                                         int HW, int C, int groups, float eps,
                                                                         const float* __restrict__ bias,
@@ -221,7 +224,7 @@ __global__ __launch_bounds__(GN_THREADS) void groupnorm_partials_kernel(const fl
 
   f32x4 v[QPT];
   bf16x4 rv[QPT];
-  long long off[QPT], yoff[QPT];
+  long long off[QPT], woff[QPT], yoff[QPT];
   int ch[QPT];
   const bool second = c0 >= C;                 // (workgroup-uniform) this group's channels come from x2
 #pragma unroll
@@ -231,6 +234,7 @@ __global__ __launch_bounds__(GN_THREADS) void groupnorm_partials_kernel(const fl
     const int pix = aldm_div(qq, dqpp), j = qq - pix * qpp;
     ch[i] = c0 + 4 * j;
     off[i] = ((long long)b * HW + pix) * C + ch[i];
+    woff[i] = PLANAR ? (((long long)b * (C >> 2) + (ch[i] >> 2)) * HW + pix) * 4 : off[i];   // (second: ch >= C, never read)
     yoff[i] = ((long long)b * HW + pix) * Ct + ch[i];
     v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     rv[i] = bf16x4{0, 0, 0, 0};
@@ -246,7 +250,7 @@ __global__ __launch_bounds__(GN_THREADS) void groupnorm_partials_kernel(const fl
 #pragma unroll
     for (int i = 0; i < QPT; ++i) {
       if (tid + i * GN_THREADS < nquads) {
-        const float* w0 = ws + off[i] + sp * sstride;
+        const float* w0 = ws + woff[i] + sp * sstride;
         const f32x4 a0 = *reinterpret_cast<const f32x4*>(w0), a1 = *reinterpret_cast<const f32x4*>(w0 + sstride);
         const f32x4 a2 = *reinterpret_cast<const f32x4*>(w0 + 2 * sstride), a3 = *reinterpret_cast<const f32x4*>(w0 + 3 * sstride);
 #pragma unroll
@@ -259,7 +263,7 @@ __global__ __launch_bounds__(GN_THREADS) void groupnorm_partials_kernel(const fl
 #pragma unroll
     for (int i = 0; i < QPT; ++i) {
       if (tid + i * GN_THREADS < nquads) {
-        const float* w0 = ws + off[i] + sp * sstride;
+        const float* w0 = ws + woff[i] + sp * sstride;
         const f32x4 a0 = *reinterpret_cast<const f32x4*>(w0);
         const f32x4 a1 = *reinterpret_cast<const f32x4*>(w0 + (rem > 1 ? 1 : 0) * sstride);
         const f32x4 a2 = *reinterpret_cast<const f32x4*>(w0 + (rem > 2 ? 2 : 0) * sstride);
@@ -686,12 +690,13 @@ extern "C" int aldm_groupnorm(const void* x, const void* x2, int B, int HW, int 
   return aldm_launch_status("groupnorm");
 }
 
-extern "C" int aldm_groupnorm_partials(const float* ws, int splits, int B, int HW, int C, const float* bias,
-                                       const float* rowbias, int rowbias_ld, const void* res, void* sum_out,
-                                       const void* x2, int C2, int groups, float eps, const float* gamma, const float* beta,
-                                       int act, void* y, void* stream) {
+extern "C" int aldm_groupnorm_partials_layout(const float* ws, int splits, int B, int HW, int C, const float* bias,
+                                              const float* rowbias, int rowbias_ld, const void* res, void* sum_out,
+                                              const void* x2, int C2, int groups, float eps, const float* gamma, const float* beta,
+                                              int act, void* y, int layout, void* stream) {
   ALDM_CHECK_ARG(ws && y && gamma && beta && splits >= 1, "groupnorm_partials: null pointer / bad splits");
   ALDM_CHECK_ARG(B > 0 && HW > 0 && C > 0 && C2 >= 0 && groups > 0 && (C2 == 0 || x2), "groupnorm_partials: bad dims");
+  ALDM_CHECK_ARG(layout == ALDM_SLAB_ROWMAJOR || layout == ALDM_SLAB_PLANAR, "groupnorm_partials: unknown slab layout %d", layout);
   const int Ct = C + C2;
   ALDM_CHECK_ARG(Ct % groups == 0 && (Ct / groups) % 4 == 0 && C % (Ct / groups) == 0,
                  "groupnorm_partials: group width %d must be a multiple of 4 and divide the first source's %d channels", Ct / groups, C);
@@ -701,16 +706,26 @@ extern "C" int aldm_groupnorm_partials(const float* ws, int splits, int B, int H
   ALDM_CHECK_ARG(nquads <= 8 * GN_THREADS, "groupnorm_partials: strip of %lld quads exceeds the register-resident limit %d", nquads, 8 * GN_THREADS);
   const AldmDiv dq = aldm_make_div((unsigned)(Ct / groups / 4));
   const long long sstride = (long long)B * HW * C;
-#define ALDM_GNP(QPT)                                                                                                  \
-  hipLaunchKernelGGL(groupnorm_partials_kernel<QPT>, dim3(B * groups), dim3(GN_THREADS), 0, (hipStream_t)stream, ws,   \
+#define ALDM_GNP2(QPT, PL)                                                                                             \
+  hipLaunchKernelGGL((groupnorm_partials_kernel<QPT, PL>), dim3(B * groups), dim3(GN_THREADS), 0, (hipStream_t)stream, ws,   \
                      splits, sstride, HW, C, groups, eps, bias, rowbias, rowbias_ld, (const bf16*)res, (bf16*)sum_out,        \
                      (const bf16*)x2, C2, gamma, beta, act, (bf16*)y, dq)
+#define ALDM_GNP(QPT) do { if (layout == ALDM_SLAB_PLANAR) ALDM_GNP2(QPT, true); else ALDM_GNP2(QPT, false); } while (0)
   if (nquads <= GN_THREADS) ALDM_GNP(1);
   else if (nquads <= 2 * GN_THREADS) ALDM_GNP(2);
   else if (nquads <= 4 * GN_THREADS) ALDM_GNP(4);
   else ALDM_GNP(8);
 #undef ALDM_GNP
+#undef ALDM_GNP2
   return aldm_launch_status("groupnorm_partials");
+}
+
+extern "C" int aldm_groupnorm_partials(const float* ws, int splits, int B, int HW, int C, const float* bias,
+                                       const float* rowbias, int rowbias_ld, const void* res, void* sum_out,
+                                       const void* x2, int C2, int groups, float eps, const float* gamma, const float* beta,
+                                       int act, void* y, void* stream) {
+  return aldm_groupnorm_partials_layout(ws, splits, B, HW, C, bias, rowbias, rowbias_ld, res, sum_out, x2, C2, groups, eps, gamma, beta,
+                                        act, y, ALDM_SLAB_ROWMAJOR, stream);
 }
 
 extern "C" int aldm_layernorm(const void* x, int M, int C, const float* gamma, const float* beta, float eps, void* y,

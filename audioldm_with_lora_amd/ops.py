@@ -312,12 +312,14 @@ class Tuner:
                     cands += [(t, rg, sp) for sp in (2, 3, 4, 5, 6, 8, 10) for rg in (3, 4)
                               if sp <= nch and base * sp <= 2560 and sp * M * pw.N * 4 <= (1 << 28)]
         max_sp = max(c[2] for c in cands)
+        defer_flags = (_lib.DEFER_ROWMAJOR | (_lib.DEFER_PLANAR if SLAB_LAYOUT == _lib.SLAB_PLANAR else 0)
+                       | (_lib.DEFER_WRITE_THROUGH if SLAB_WT else 0))
         ws = _workspace(max_sp * M * pw.N * 4, device) if max_sp > 1 else None
         results = []
         for t, rg, sp in cands:
             a.tile, a.ring, a.splits = t, rg, sp
             a.workspace = ws.data_ptr() if sp > 1 else None
-            a.defer_reduce = 1 if (sp > 1 and key.endswith(" gn")) else 0   # the consumer GroupNorm pays the reduce
+            a.defer_reduce = defer_flags if (sp > 1 and key.endswith(" gn")) else 0   # the consumer GroupNorm pays the reduce
             if lib.aldm_igemm(C.byref(a), _stream()) != 0:              # warm-up doubles as the validity check
                 continue
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -461,18 +463,29 @@ QSTATS_MIN_HW = 2048
 XCD_MAP = int(os.environ.get("ALDM_XCD_MAP", "0"))
 
 
+# Layout of the fp32 slabs a split-K launch leaves for a deferred reduce: quad-planar ([split][image][C / 4][HW][4]: what one
+# (image, group) workgroup of the consuming GroupNorm reads is contiguous) unless ALDM_NO_SLAB_PLANAR=1 (row-major [split][M][C], the
+# layout of every non-deferred split-K launch).  The slab stores of a deferred launch are write-through (the partials drain to memory
+# while the kernel still runs instead of at the kernel boundary) unless ALDM_NO_SLAB_WT=1.  Same results bit for bit either way; measured
+# in the replayed denoise step: 2.949 ms row-major / plain, 2.930 planar, 2.929 write-through, 2.900 both.
+SLAB_LAYOUT = _lib.SLAB_ROWMAJOR if os.environ.get("ALDM_NO_SLAB_PLANAR") == "1" else _lib.SLAB_PLANAR
+SLAB_WT = os.environ.get("ALDM_NO_SLAB_WT") != "1"
+
+
 class Deferred:
     """A split-K convolution whose reduce is still pending (conv(..., defer=True)): the fp32 partial tiles sit in the shared
     workspace, `out` is the bf16 tensor the consumer will fill.  The ONLY valid consumer is the next groupnorm() call on this
     stream -- it sums the tiles, adds bias / row bias / residual, writes `out` and returns the norm; no other split-K conv may
-    run in between (the workspace is shared; conv() refuses)."""
-    __slots__ = ("out", "ws", "eff", "bias", "rowbias", "rowbias_ld", "res", "keep")
+    run in between (the workspace is shared; conv() refuses).  `layout` (_lib.SLAB_*) is how the launch wrote its slabs: a
+    consumer either reads that layout or refuses the Deferred."""
+    __slots__ = ("out", "ws", "eff", "bias", "rowbias", "rowbias_ld", "res", "keep", "layout")
 
-    def __init__(self, out, ws, eff, bias, rowbias, rowbias_ld, res, keep):
+    def __init__(self, out, ws, eff, bias, rowbias, rowbias_ld, res, keep, layout=_lib.SLAB_ROWMAJOR):
         global DEFERRED_COUNT
         DEFERRED_COUNT += 1
         self.out, self.ws, self.eff, self.bias, self.rowbias, self.rowbias_ld, self.res = out, ws, eff, bias, rowbias, rowbias_ld, res
         self.keep = keep                                   # tensors the pointers above refer to
+        self.layout = layout
 
     @property
     def shape(self):
@@ -525,7 +538,7 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
          out_slope=0.0, res=None, res2=None, alpha=1.0, post_act=ACT_NONE, post_slope=0.0, out2=None, out=None, out_f32=False, out_ld=None, out_batch_stride=None,
          out_pix_stride=1, out_pix_offset=0, vt=None, vt_col0=0, vt_ld=0, vt_batch_stride=0, lora_t_out=None,
          splits=None, tile=0, ring=0, gn=None, gn_keep=False, defer=False, rowstats=False, ln_parts=None, x3=None, x4=None,
-         vt_dual=False, qstats=False, gn_in=None, lora_gate=None):
+         vt_dual=False, qstats=False, gn_in=None, lora_gate=None, slab_layout=None, slab_wt=None):
     """Implicit-GEMM convolution over channels-last x [B, IH, IW, C1] (+ x2 [B, IH, IW, C2]).
 
     gn=(gamma, beta, groups, eps, act) returns GroupNorm(+act) of the convolution instead of the convolution: when the launch
@@ -541,6 +554,11 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
     LayerNorm hand-over (BasicTransformerBlock: h -> LayerNorm -> projection): rowstats=True returns (out, stats), stats fp32
     [M, N / BN, 2] = per-row partial (sum, sum of squares) written by the epilogue; a consumer packed with pack_linear_ln takes
     them as ln_parts= and derives mean / rstd from them -- no LayerNorm launch, no statistics pass in either GEMM's K loop.
+
+    slab_layout / slab_wt: layout (_lib.SLAB_*) and store policy of the slabs a deferred split-K launch leaves for its consumer.
+    gn= (the consumer is this call's own groupnorm) takes ops.SLAB_LAYOUT; a defer= caller names the layout its consumer reads --
+    groupnorm() reads either (the UNet forward passes ops.SLAB_LAYOUT), groupnorm_bwd() reads row-major only, which is the default.
+    slab_wt defaults to ops.SLAB_WT.
 
     lora_gate (default: ops.LORA_GATE): fp32 [samples][Rp] per-sample gates of the LoRA side channel's columns (multi-adapter routing)."""
     _require_gpu(x)
@@ -738,7 +756,11 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
     a.xcd_map = XCD_MAP
     lib = _lib.load()
     eff = lib.aldm_igemm_effective_splits(C.byref(a)) if (gn_defer and splits > 1) else 1
-    a.defer_reduce = 1 if eff > 1 else 0
+    layout = _lib.SLAB_ROWMAJOR
+    if eff > 1:
+        layout = slab_layout if slab_layout is not None else (SLAB_LAYOUT if gn is not None else _lib.SLAB_ROWMAJOR)
+    a.defer_reduce = ((_lib.DEFER_ROWMAJOR | (_lib.DEFER_PLANAR if layout == _lib.SLAB_PLANAR else 0)
+                       | (_lib.DEFER_WRITE_THROUGH if (SLAB_WT if slab_wt is None else slab_wt) else 0)) if eff > 1 else 0)
     ktot = KH * KW * pw.Cin + pw.Cext
     flops = 2.0 * M * pw.N * ktot + (2.0 * M * pw.Rp * (ktot + pw.N) if pw.Rp else 0.0)
     nbytes = 2.0 * (B * IH * IW * pw.Cin + M * pw.Cext + pw.N * ktot + M * ncols)
@@ -754,7 +776,7 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
         # the GroupNorm of gn=: over the partial tiles when the launch deferred its reduce, else over the bf16 output
         if gn is None:
             if eff > 1:
-                d = Deferred(out, a.workspace, eff, a.bias, a.rowbias, a.rowbias_ld, a.res, (pw, rowbias, res, x3, x4))
+                d = Deferred(out, a.workspace, eff, a.bias, a.rowbias, a.rowbias_ld, a.res, (pw, rowbias, res, x3, x4), layout)
                 _pending_set(out, d)
                 return d
             return (out, stats) if rowstats else out
@@ -764,9 +786,9 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
             return (out, y) if gn_keep else y
         y = torch.empty(B, OH, OW, pw.N, dtype=torch.bfloat16, device=x.device)
         n = M * pw.N
-        check(_launch(f"groupnorm_partials|HW{OH * OW} C{pw.N} S{eff}", 10.0 * n, (4.0 * eff + 2.0) * n, lambda: lib.aldm_groupnorm_partials(
+        check(_launch(f"groupnorm_partials|HW{OH * OW} C{pw.N} S{eff}", 10.0 * n, (4.0 * eff + 2.0) * n, lambda: lib.aldm_groupnorm_partials_layout(
             a.workspace, eff, B, OH * OW, pw.N, a.bias, a.rowbias, a.rowbias_ld, a.res, (a.out if gn_keep else None), None, 0,
-            groups, eps, _p(gamma), _p(beta), act, _p(y), _stream())), "aldm_groupnorm_partials")
+            groups, eps, _p(gamma), _p(beta), act, _p(y), layout, _stream())), "aldm_groupnorm_partials")
         return (out, y) if gn_keep else y
 
     if tuning and TUNER.slot is not None:                      # stage 2 of the tuner: time this launch in context
@@ -891,9 +913,9 @@ def groupnorm(x, gamma, beta, groups, eps, act=ACT_NONE, x2=None):
         y = torch.empty(B, H, W, C1 + C2, dtype=torch.bfloat16, device=x.out.device)
         lib = _lib.load()
         n = B * H * W * (C1 + C2)
-        check(_launch(f"groupnorm_partials|HW{H * W} C{C1}+{C2} S{x.eff}", 10.0 * n, (4.0 * x.eff + 2.0) * n, lambda: lib.aldm_groupnorm_partials(
+        check(_launch(f"groupnorm_partials|HW{H * W} C{C1}+{C2} S{x.eff}", 10.0 * n, (4.0 * x.eff + 2.0) * n, lambda: lib.aldm_groupnorm_partials_layout(
             x.ws, x.eff, B, H * W, C1, x.bias, x.rowbias, x.rowbias_ld, x.res, _p(x.out), _p(x2), C2, groups, eps,
-            _p(gamma), _p(beta), act, _p(y), _stream())), "aldm_groupnorm_partials")
+            _p(gamma), _p(beta), act, _p(y), x.layout, _stream())), "aldm_groupnorm_partials")
         _pending_set(x.out, None)
         return y
     _require_gpu(x)
@@ -1485,6 +1507,8 @@ def groupnorm_bwd(x, dy, gamma, beta, groups, eps, act, x2=None, need_dx2=True, 
     if isinstance(dy, Deferred):                           # dY = partial tiles of the dX convolution launched just before
         if dy is not _pending_get(dy.out) or dy.bias is not None or dy.rowbias is not None or dy.res is not None:
             raise _lib.AldmError("groupnorm_bwd: deferred dY must be the pending split-K launch, without bias / residual")
+        if dy.layout != _lib.SLAB_ROWMAJOR:
+            raise _lib.AldmError("groupnorm_bwd: deferred dY must be left in row-major slabs (conv(..., slab_layout=_lib.SLAB_ROWMAJOR))")
         assert tuple(dy.out.shape) == (B, H, W, C1 + C2)
         check(_lib.load().aldm_groupnorm_bwd_partials(_p(x), _p(x2), dy.ws, dy.eff, B, H * W, C1, C2, groups, eps, _p(gamma), _p(beta),
                                                       act, _p(dx), _p(dx2), _p(a1), _p(a2), _stream()), "aldm_groupnorm_bwd_partials")

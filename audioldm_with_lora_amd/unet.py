@@ -284,7 +284,7 @@ def run_resnet(P, x, x2=None, rowbias=None, rowbias_ld=0, next_gn=None, defer=No
         # the 1x1 shortcut over the block input (| skip) rides at the end of conv2's K loop: one launch instead of two
         if next_gn is not None:
             return ops.conv(h, P.conv2s, pad=(1, 1), x3=x, x4=x2, gn=next_gn, gn_keep=True, qstats=True)
-        return ops.conv(h, P.conv2s, pad=(1, 1), x3=x, x4=x2, defer=(defer or False), qstats=True)
+        return ops.conv(h, P.conv2s, pad=(1, 1), x3=x, x4=x2, defer=(defer or False), slab_layout=ops.SLAB_LAYOUT, qstats=True)
     if P.shortcut is not None:
         xs = ops.conv(x, P.shortcut, x2=x2)
     else:
@@ -293,7 +293,7 @@ def run_resnet(P, x, x2=None, rowbias=None, rowbias_ld=0, next_gn=None, defer=No
     src, fold = (h1, dict(gn_in=gn2)) if h1 is not None else (h, {})      # (norm2 + SiLU inside conv2's halo tile)
     if next_gn is not None:
         return ops.conv(src, P.conv2, pad=(1, 1), res=xs, gn=next_gn, gn_keep=True, qstats=True, **fold)
-    return ops.conv(src, P.conv2, pad=(1, 1), res=xs, defer=(defer or False), qstats=True, **fold)
+    return ops.conv(src, P.conv2, pad=(1, 1), res=xs, defer=(defer or False), slab_layout=ops.SLAB_LAYOUT, qstats=True, **fold)
 
 
 def run_attention(P, hn, h_res, B, N, fp8=False, ln_parts=None, rowstats=False):
@@ -347,9 +347,9 @@ def run_transformer(P, x, fp8=False, xn=None, defer=None):
         h, st = h
     g = ops.linear(h if f3 else ops.layernorm(h, *P.ln[2]), P.ff1, ln_parts=st)
     if P.ff2_proj is not None:                                # ff2 and proj_out as ONE GEMM over the virtual concat [g | h]
-        return ops.conv(g.view(B, H, W, 4 * C), P.ff2_proj, x2=h.view(B, H, W, C), res=x, defer=(defer or False), qstats=True)
+        return ops.conv(g.view(B, H, W, 4 * C), P.ff2_proj, x2=h.view(B, H, W, C), res=x, defer=(defer or False), slab_layout=ops.SLAB_LAYOUT, qstats=True)
     h = ops.linear(g, P.ff2, res=h)
-    return ops.conv(h.view(B, H, W, C), P.proj_out, res=x, defer=(defer or False), qstats=True)
+    return ops.conv(h.view(B, H, W, C), P.proj_out, res=x, defer=(defer or False), slab_layout=ops.SLAB_LAYOUT, qstats=True)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -579,7 +579,7 @@ class UNet2DConditionModel(AdapterRouting, nn.Module):
                     h = run_resnet(r, h, None, rowbias, ld, defer=nxt)
                 skips.append(ops.tensor_of(h))
             if blk.down is not None:
-                h = ops.conv(h, blk.down, stride=(2, 2), pad=(1, 1), defer=norm1_of(P.down[bi + 1].resnets[0]), qstats=True)
+                h = ops.conv(h, blk.down, stride=(2, 2), pad=(1, 1), defer=norm1_of(P.down[bi + 1].resnets[0]), slab_layout=ops.SLAB_LAYOUT, qstats=True)
                 skips.append(ops.tensor_of(h))
         h, hn = run_resnet(P.mid.resnets[0], h, None, rowbias, ld, next_gn=transformer_gn(P.mid.attns[0]))
         h = run_transformer(P.mid.attns[0], h, fp8, xn=hn, defer=norm1_of(P.mid.resnets[1]))
@@ -603,7 +603,7 @@ class UNet2DConditionModel(AdapterRouting, nn.Module):
                     size = (skips[-1].shape[1], skips[-1].shape[2])
                 else:
                     size = (h.shape[1] * 2, h.shape[2] * 2)
-                h = ops.conv(h, blk.up, pad=(1, 1), up_size=size, defer=norm1_of(P.up[bi + 1].resnets[0]), qstats=True)
+                h = ops.conv(h, blk.up, pad=(1, 1), up_size=size, defer=norm1_of(P.up[bi + 1].resnets[0]), slab_layout=ops.SLAB_LAYOUT, qstats=True)
         if ops.gn_silu_conv_out_ok(h, P.conv_out, groups):        # norm + SiLU + the 128 -> 8 channel convolution as one launch
             return ops.gn_silu_conv_out(h, P.gn_out[0], P.gn_out[1], groups, eps, P.conv_out)
         h = ops.groupnorm(h, P.gn_out[0], P.gn_out[1], groups, eps, ACT_SILU)

@@ -94,7 +94,10 @@ typedef struct {
   int ring;                 /* 0 = auto, else LDS-DMA ring depth 2..4 (tuning) */
   int defer_reduce;         /* split-K only: leave the partial tiles in `workspace` and launch no reduce -- the consumer sums
                                them itself and adds bias / rowbias / res (aldm_groupnorm_partials: ResnetBlock2D convs
-                               in front of a GroupNorm) */
+                               in front of a GroupNorm).  A set of ALDM_DEFER_* flags: 1 = defer, row-major slabs
+                               [splits][M][Cout]; | ALDM_DEFER_PLANAR = quad-planar slabs [splits][B][Cout / 4][OH*OW][4] (what one
+                               (image, group) workgroup of the consumer reads is contiguous; the consumer must be told:
+                               aldm_groupnorm_partials_layout); | ALDM_DEFER_WRITE_THROUGH = the slab stores are write-through */
   /* LayerNorm statistics handed from one GEMM to the next (BasicTransformerBlock: h -> norm -> projection).  The producer of h
      (bf16 output, standard epilogue, Cout a multiple of its tile width BN) writes, per output row and per N-tile, the sum and
      the sum of squares of the row's bf16-rounded values: rowstat_out [M][Cout / BN][2] fp32.  The consumer (ln_s != NULL)
@@ -155,10 +158,17 @@ enum { ALDM_TILE_AUTO = 0, ALDM_TILE_128x128 = 1, ALDM_TILE_64x64 = 2, ALDM_TILE
        ALDM_TILE_64x128_W8 = 10, ALDM_TILE_128x64_W8 = 11 /* 8-wave forms of the small tiles: two waves per SIMD where the grid is ~one
           workgroup per CU (split-K convolutions of the low-resolution levels); LDS-DMA path, no LoRA / V^T */ };
 
+enum { ALDM_DEFER_ROWMAJOR = 1, ALDM_DEFER_PLANAR = 2, ALDM_DEFER_WRITE_THROUGH = 4 };   /* aldm_igemm_t.defer_reduce */
+enum { ALDM_SLAB_ROWMAJOR = 0, ALDM_SLAB_PLANAR = 1 };                                    /* slab layout as a consumer is told it */
+
 int aldm_igemm(const aldm_igemm_t* p, void* stream);
 size_t aldm_igemm_workspace_bytes(const aldm_igemm_t* p);
 /* the split count the launch will really use (splits is clamped so that every split gets whole 64-wide K-tiles) */
 int aldm_igemm_effective_splits(const aldm_igemm_t* p);
+/* Host-side restatement of the kernels' slab store address: element offset, in the workspace of a split-K launch over B images of HW
+   pixels and C channels, of channel n of output row m (= b * HW + pix) in slab `split`, for layout ALDM_SLAB_*.  Needs no GPU (layout
+   checks); -1 for an argument out of range. */
+long long aldm_igemm_slab_offset(int layout, int B, int HW, int C, int split, int m, int n);
 
 /* ------------------------------------------------------------------------------------------
  * Projection GEMM of the transformer blocks: out[M][N] = epilogue(x[M][K] w[N][K]^T), K = 256 / 384 / 640.
@@ -244,6 +254,11 @@ int aldm_groupnorm_partials(const float* ws, int splits, int B, int HW, int C, c
                             int rowbias_ld, const void* res, void* sum_out, const void* x2, int C2, int groups, float eps,
                             const float* gamma, const float* beta, int act, void* y,
                             void* stream);
+/* the same over slabs of the given layout (ALDM_SLAB_*; aldm_groupnorm_partials = ALDM_SLAB_ROWMAJOR).  The partials are added in
+   split order either way: the results are equal bit for bit. */
+int aldm_groupnorm_partials_layout(const float* ws, int splits, int B, int HW, int C, const float* bias, const float* rowbias,
+                                   int rowbias_ld, const void* res, void* sum_out, const void* x2, int C2, int groups, float eps,
+                                   const float* gamma, const float* beta, int act, void* y, int layout, void* stream);
 /* ClapTextEmbeddings: y[b*L+j] = LayerNorm(word[ids[b][j]] + type0 + pos[pid]) as bf16 [B*L][C]; pid counts the non-pad
    tokens up to and including j (offset by pad_idx; pad tokens use pid = pad_idx).  ids int64 on the device, fp32 tables.
    First op of `text_encoder(input_ids, attention_mask)` [REF script/train/train_audioldm_lora.py:513-518]. */
