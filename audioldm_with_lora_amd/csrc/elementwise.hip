@@ -1,8 +1,11 @@
 // Small fused elementwise kernels of the denoise loop and the training step (gfx950, HBM/latency-bound):
 // timestep embedding, SiLU, layout/precision boundary conversions, the fused CFG + DDIM (or DPM-Solver multistep) update with a
-// device-side step counter (so one captured hipGraph replays all 200 steps), and flat AdamW.
+// device-side step counter (so one captured hipGraph replays all 200 steps), flat AdamW, and the flat gradient-norm clip /
+// gradient accumulation around it.
 // [REF script/inference/generate_audio.py:47-52] (AudioLDMPipeline.__call__ loop body)
-// [REF script/train/train_audioldm_lora.py:396-403,563-565] (torch.optim.AdamW on the LoRA parameters)
+// [REF script/train/train_audioldm_lora.py:396-403,559-565] (clip_grad_norm_ and torch.optim.AdamW on the LoRA parameters)
+#include <initializer_list>
+
 #include "common.h"
 #include "philox.h"
 
@@ -430,6 +433,124 @@ __global__ void adamw_flat_kernel(float* __restrict__ p, const float* __restrict
   p[i] = pv;
 }
 
+// ---- gradient-norm clipping over the flat LoRA gradient buffer (torch.nn.utils.clip_grad_norm_, 2-norm) ----
+// The norm is TWO steps so that no float atomic is needed and the result is bitwise reproducible: sumsq_flat leaves one partial sum of
+// squares per workgroup (a fixed grid: which elements a thread sees, and the order it adds them in, depend on n and npart only), and
+// every consumer adds the npart partials itself, in index order, so all of them see the same total.
+constexpr int FLAT_THREADS = 256;
+constexpr int FLAT_MAX_PARTS = 1024;
+
+// Quads [0, nvec) as 16-byte loads, elements [4 nvec, n) one by one (n is no multiple of anything; nvec = 0 for an unaligned buffer).
+__global__ __launch_bounds__(FLAT_THREADS) void sumsq_flat_kernel(const float* __restrict__ g, long long n, long long nvec,
+                                                                  float* __restrict__ partials) {
+  __shared__ float red[FLAT_THREADS / 64];
+  const long long stride = (long long)gridDim.x * FLAT_THREADS;
+  const long long t0 = (long long)blockIdx.x * FLAT_THREADS + threadIdx.x;
+  float s = 0.f;
+  for (long long q = t0; q < nvec; q += stride) {
+    const f32x4 x = *reinterpret_cast<const f32x4*>(g + 4 * q);
+    s += (x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]);
+  }
+  for (long long i = 4 * nvec + t0; i < n; i += stride) s += g[i] * g[i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// total = sqrt(sum of the partials, in index order) * gscale: the 2-norm of the gradient the optimiser will see (g * gscale), and
+// coef = min(1, max_norm / (total + 1e-6)) as clip_grad_norm_ forms it (a NaN norm stays a NaN coefficient, as torch.clamp leaves it).
+// One thread adds, everybody reads the pair back from LDS: every workgroup of every consumer computes the same two numbers.
+__device__ __forceinline__ void clip_coef(const float* __restrict__ partials, int npart, float gscale, float max_norm, float* sh,
+                                          float& total, float& coef) {
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+#pragma unroll 8
+    for (int i = 0; i < npart; ++i) s += partials[i];
+    const float t = sqrtf(s) * gscale;
+    const float c = max_norm / (t + 1e-6f);
+    sh[0] = t;
+    sh[1] = c > 1.f ? 1.f : c;
+  }
+  __syncthreads();
+  total = sh[0];
+  coef = sh[1];
+}
+
+// aldm_adamw_flat on g * gscale * coef, the coefficient taken from device memory (nothing about clipping reaches the host)
+__global__ __launch_bounds__(FLAT_THREADS) void adamw_flat_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                       float* __restrict__ m, float* __restrict__ v, long long n,
+                                                                       long long nvec, float lr, float b1, float b2, float eps,
+                                                                       float wd, float bc1, float bc2_sqrt, float gscale,
+                                                                       const float* __restrict__ partials, int npart,
+                                                                       float max_norm, float* __restrict__ norm_out) {
+  __shared__ float sh[2];
+  float total, coef;
+  clip_coef(partials, npart, gscale, max_norm, sh, total, coef);
+  if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = total;
+  struct Pmv { float p, m, v; };
+  auto update = [&](float p0, float gv, float m0, float v0) {           // the arithmetic of adamw_flat_kernel, term by term
+    const float grad = gv * gscale * coef;
+    float pv = p0 * (1.f - lr * wd);
+    const float mv = b1 * m0 + (1.f - b1) * grad;
+    const float vv = b2 * v0 + (1.f - b2) * grad * grad;
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    pv -= (lr / bc1) * (mv / denom);
+    return Pmv{pv, mv, vv};
+  };
+  const long long stride = (long long)gridDim.x * FLAT_THREADS;
+  const long long t0 = (long long)blockIdx.x * FLAT_THREADS + threadIdx.x;
+  for (long long q = t0; q < nvec; q += stride) {
+    f32x4 pv = *reinterpret_cast<const f32x4*>(p + 4 * q), mv = *reinterpret_cast<const f32x4*>(m + 4 * q);
+    f32x4 vv = *reinterpret_cast<const f32x4*>(v + 4 * q);
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + 4 * q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const Pmv r = update(pv[k], gv[k], mv[k], vv[k]);
+      pv[k] = r.p; mv[k] = r.m; vv[k] = r.v;
+    }
+    *reinterpret_cast<f32x4*>(m + 4 * q) = mv;
+    *reinterpret_cast<f32x4*>(v + 4 * q) = vv;
+    *reinterpret_cast<f32x4*>(p + 4 * q) = pv;
+  }
+  for (long long i = 4 * nvec + t0; i < n; i += stride) {
+    const Pmv r = update(p[i], g[i], m[i], v[i]);
+    m[i] = r.m; v[i] = r.v; p[i] = r.p;
+  }
+}
+
+// g *= coef in place (the autograd-shaped facade: clip_grad_norm_ must leave scaled .grads behind); coef = 1 leaves every bit as it was
+__global__ __launch_bounds__(FLAT_THREADS) void clip_flat_kernel(float* __restrict__ g, long long n, long long nvec,
+                                                                 const float* __restrict__ partials, int npart, float max_norm,
+                                                                 float gscale, float* __restrict__ norm_out) {
+  __shared__ float sh[2];
+  float total, coef;
+  clip_coef(partials, npart, gscale, max_norm, sh, total, coef);
+  if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = total;
+  const long long stride = (long long)gridDim.x * FLAT_THREADS;
+  const long long t0 = (long long)blockIdx.x * FLAT_THREADS + threadIdx.x;
+  for (long long q = t0; q < nvec; q += stride) {
+    f32x4 x = *reinterpret_cast<const f32x4*>(g + 4 * q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] *= coef;
+    *reinterpret_cast<f32x4*>(g + 4 * q) = x;
+  }
+  for (long long i = 4 * nvec + t0; i < n; i += stride) g[i] *= coef;
+}
+
+// acc = first ? g : acc + g (gradient accumulation: the micro-batch's flat gradients + loss slot into the window's buffer)
+__global__ __launch_bounds__(FLAT_THREADS) void accum_flat_kernel(float* __restrict__ acc, const float* __restrict__ g, long long n,
+                                                                  long long nvec, int first) {
+  const long long stride = (long long)gridDim.x * FLAT_THREADS;
+  const long long t0 = (long long)blockIdx.x * FLAT_THREADS + threadIdx.x;
+  for (long long q = t0; q < nvec; q += stride) {
+    f32x4 x = *reinterpret_cast<const f32x4*>(g + 4 * q);
+    if (!first) x += *reinterpret_cast<const f32x4*>(acc + 4 * q);
+    *reinterpret_cast<f32x4*>(acc + 4 * q) = x;
+  }
+  for (long long i = 4 * nvec + t0; i < n; i += stride) acc[i] = first ? g[i] : acc[i] + g[i];
+}
+
 __global__ void add_noise_kernel(const float* __restrict__ x, const float* __restrict__ nz, const float* __restrict__ coef,
                                  int B, long long n, float* __restrict__ out) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -699,6 +820,53 @@ extern "C" int aldm_adamw_flat(float* p, const float* g, float* m, float* v, lon
   const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
   hipLaunchKernelGGL(adamw_flat_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
   return aldm_launch_status("adamw_flat");
+}
+
+// quads the flat kernels may take as 16-byte accesses (every buffer 16-byte aligned), and their grid-stride grid
+static inline long long flat_nvec(long long n, std::initializer_list<const void*> bufs) {
+  for (const void* b : bufs)
+    if (reinterpret_cast<uintptr_t>(b) & 15) return 0;
+  return n / 4;
+}
+static inline unsigned flat_grid(long long n, long long nvec) {
+  const long long work = nvec > n - 4 * nvec ? nvec : n - 4 * nvec;
+  const long long b = (work + FLAT_THREADS - 1) / FLAT_THREADS;
+  return (unsigned)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
+}
+
+extern "C" int aldm_sumsq_flat(const float* g, long long n, float* partials, int npart, void* stream) {
+  ALDM_CHECK_ARG(g && partials && n > 0 && npart >= 1 && npart <= FLAT_MAX_PARTS, "sumsq_flat: bad args (1 <= npart <= %d)", FLAT_MAX_PARTS);
+  hipLaunchKernelGGL(sumsq_flat_kernel, dim3(npart), dim3(FLAT_THREADS), 0, (hipStream_t)stream, g, n, flat_nvec(n, {g}), partials);
+  return aldm_launch_status("sumsq_flat");
+}
+
+extern "C" int aldm_adamw_flat_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+                                    float eps, float weight_decay, int step, float grad_scale, const float* partials, int npart,
+                                    float max_norm, float* norm_out, void* stream) {
+  ALDM_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "adamw_flat_clip: bad args");
+  ALDM_CHECK_ARG(partials && norm_out && npart >= 1 && npart <= FLAT_MAX_PARTS, "adamw_flat_clip: bad partials (1 <= npart <= %d)", FLAT_MAX_PARTS);
+  const float bc1 = 1.f - powf(beta1, (float)step);
+  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+  const long long nvec = flat_nvec(n, {p, g, m, v});
+  hipLaunchKernelGGL(adamw_flat_clip_kernel, dim3(flat_grid(n, nvec)), dim3(FLAT_THREADS), 0, (hipStream_t)stream, p, g, m, v, n, nvec, lr,
+                     beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, partials, npart, max_norm, norm_out);
+  return aldm_launch_status("adamw_flat_clip");
+}
+
+extern "C" int aldm_clip_flat(float* g, long long n, const float* partials, int npart, float max_norm, float grad_scale, float* norm_out,
+                              void* stream) {
+  ALDM_CHECK_ARG(g && n > 0 && partials && norm_out && npart >= 1 && npart <= FLAT_MAX_PARTS, "clip_flat: bad args (1 <= npart <= %d)", FLAT_MAX_PARTS);
+  const long long nvec = flat_nvec(n, {g});
+  hipLaunchKernelGGL(clip_flat_kernel, dim3(flat_grid(n, nvec)), dim3(FLAT_THREADS), 0, (hipStream_t)stream, g, n, nvec, partials, npart,
+                     max_norm, grad_scale, norm_out);
+  return aldm_launch_status("clip_flat");
+}
+
+extern "C" int aldm_accum_flat(float* acc, const float* g, long long n, int first, void* stream) {
+  ALDM_CHECK_ARG(acc && g && n > 0, "accum_flat: bad args");
+  const long long nvec = flat_nvec(n, {acc, g});
+  hipLaunchKernelGGL(accum_flat_kernel, dim3(flat_grid(n, nvec)), dim3(FLAT_THREADS), 0, (hipStream_t)stream, acc, g, n, nvec, first);
+  return aldm_launch_status("accum_flat");
 }
 
 // ---- debugging hook (tools/probe_latency.py), not part of the drop-in boundary: what does a kernel's FIRST memory access cost? ----

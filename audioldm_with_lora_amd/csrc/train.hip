@@ -10,7 +10,7 @@
 //                                   into the flat fp32 LoRA gradient buffer that RCCL all-reduces
 //   lora_pack                       flat fp32 LoRA parameters -> the bf16 packed operands of the fused GEMMs (one launch)
 //   transpose_tokens                [B*N][C] row-major -> [B][C][Npad] token-major (attention operands)
-//   mse_grad                        eps-prediction MSE loss value and its gradient
+//   mse_grad / mse_grad_snr         eps-prediction MSE loss value and its gradient, plain or min-SNR-gamma weighted per sample
 #include "common.h"
 
 namespace {
@@ -576,6 +576,32 @@ __global__ __launch_bounds__(256) void mse_grad_kernel(const float* __restrict__
   if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) / (float)n);
 }
 
+// mse_grad with the min-SNR-gamma weight of sample b = i / per_sample taken on the device (epsilon prediction):
+//   snr = abar[t_b] / (1 - abar[t_b]),  w_b = min(snr, gamma) / snr   (1 where snr <= gamma, bit for bit: x / x)
+//   loss[0] += (1/n) sum w_b e_i^2,  dpred_i = 2 w_b e_i / n * gscale
+// A 256-thread block may straddle a sample boundary, so the weight is per thread.
+__global__ __launch_bounds__(256) void mse_grad_snr_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                           long long n, long long per_sample, const float* __restrict__ abar,
+                                                           const long long* __restrict__ t, int n_train, float snr_gamma,
+                                                           float gscale, bf16* __restrict__ dpred, float* __restrict__ loss) {
+  __shared__ float red[4];
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  float e = 0.f, w = 0.f;
+  if (i < n) {
+    long long tb = t[i / per_sample];
+    tb = tb < 0 ? 0 : (tb >= n_train ? n_train - 1 : tb);
+    const float a = abar[tb];
+    const float snr = a / (1.f - a);
+    w = fminf(snr, snr_gamma) / snr;
+    e = pred[i] - target[i];
+    dpred[i] = (bf16)(2.f * (w * e) / (float)n * gscale);
+  }
+  float s = wave_sum(w * e * e);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) / (float)n);
+}
+
 inline unsigned nblk(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
@@ -721,4 +747,14 @@ extern "C" int aldm_mse_grad(const float* pred, const float* target, long long n
   ALDM_CHECK_ARG(pred && target && dpred && loss && n > 0, "mse_grad: bad args");
   hipLaunchKernelGGL(mse_grad_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, pred, target, n, grad_scale, (bf16*)dpred, loss);
   return aldm_launch_status("mse_grad");
+}
+
+extern "C" int aldm_mse_grad_snr(const float* pred, const float* target, long long n, long long per_sample, const float* abar,
+                                 const long long* t, int n_train, float snr_gamma, float grad_scale, void* dpred, float* loss,
+                                 void* stream) {
+  ALDM_CHECK_ARG(pred && target && dpred && loss && abar && t && n > 0, "mse_grad_snr: bad args");
+  ALDM_CHECK_ARG(per_sample > 0 && n % per_sample == 0 && n_train > 0 && snr_gamma > 0.f, "mse_grad_snr: bad per_sample / n_train / gamma");
+  hipLaunchKernelGGL(mse_grad_snr_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, pred, target, n, per_sample, abar, t,
+                     n_train, snr_gamma, grad_scale, (bf16*)dpred, loss);
+  return aldm_launch_status("mse_grad_snr");
 }

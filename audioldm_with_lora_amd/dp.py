@@ -3,7 +3,7 @@
 Mirrors the slice of `accelerate.Accelerator` the reference trainer touches
   [REF script/train/train_audioldm_lora.py:327-332,445-447,494,551,557-561,576,615]:
   init_trackers / prepare / accumulate / backward / clip_grad_norm_ / gather / sync_gradients / log / is_main_process /
-  wait_for_everyone / save_state / unwrap_model / end_training / device / num_processes, plus `ProjectConfiguration`.
+  wait_for_everyone / save_state / load_state / unwrap_model / end_training / device / num_processes, plus `ProjectConfiguration`.
 The reference's DDP traffic collapses to:
   C1  gradient all-reduce  -> ONE all-reduce of the flat fp32 LoRA gradient buffer (<= 7.2 MB at r = 16)
   C2  loss all_gather      -> rides in the extra last slot of the same buffer
@@ -159,7 +159,7 @@ class PreparedScheduler:
         self.scheduler, self.num_processes = scheduler, num_processes
 
     def step(self, *a, **k):
-        for _ in range(self.num_processes):
+        for _ in range(self.num_processes):                  # (each a no-op inside an accumulation window: PolynomialLR.step)
             self.scheduler.step(*a, **k)
 
     def __getattr__(self, name):                             # get_last_lr, state_dict, last_epoch, ...
@@ -178,11 +178,16 @@ class Accelerator:
       * the reference's own loop body [REF train:539-565]: `unet(...)[0]` -> `F.mse_loss` -> `accelerator.backward(loss)` ->
         `optimizer.step()` (optim.AdamW) -- `backward` runs autograd (the HIP launch tape behind training._UNetTrainFn) and then
         ONE all-reduce of the flat LoRA gradient buffer of every prepared model;
-      * `training.LoraTrainer.step(...)`: the same arithmetic as one captured hipGraph + one all-reduce + the flat AdamW."""
+      * `training.LoraTrainer.step(...)`: the same arithmetic as one captured hipGraph + one all-reduce + the flat AdamW.
+
+    gradient_accumulation_steps = K follows accelerate: `accumulate(model)` counts micro-steps and raises `sync_gradients` on every
+    K-th; `backward` back-propagates loss / K and all-reduces only then; the prepared optimiser and LR schedule skip their `step()` /
+    `zero_grad()` in between.  The flat gradient buffer is the accumulator: inside a window the engine does not zero it and the
+    gradient scatter keeps adding.  K = 1 (the reference) is the plain loop."""
 
     def __init__(self, gradient_accumulation_steps=1, mixed_precision=None, log_with=None, project_config=None):
-        if gradient_accumulation_steps != 1:
-            raise NotImplementedError("the reference trains with gradient_accumulation_steps=1")
+        if int(gradient_accumulation_steps) != gradient_accumulation_steps or gradient_accumulation_steps < 1:
+            raise ValueError(f"gradient_accumulation_steps must be a positive integer (got {gradient_accumulation_steps!r})")
         if mixed_precision not in (None, "no"):
             raise NotImplementedError("the reference trains with mixed_precision=None [REF train:329]")
         init_from_env()
@@ -192,7 +197,8 @@ class Accelerator:
         self.local_process_index = int(os.environ.get("LOCAL_RANK", "0"))
         self.device = torch.device("cuda", self.local_process_index) if torch.cuda.is_available() else torch.device("cpu")
         self.sync_gradients = True
-        self.gradient_accumulation_steps = 1
+        self.gradient_accumulation_steps = int(gradient_accumulation_steps)
+        self._micro_steps = 0                          # accumulate() entries so far
         self.log_with = log_with                      # "wandb" in the reference; here every tracker is a JSONL file
         self.project_config = project_config or ProjectConfiguration()
         self._models, self._optimizers, self._schedulers = [], [], []
@@ -247,8 +253,10 @@ class Accelerator:
                 self._models.append(o)
             elif isinstance(o, optim.AdamW):
                 self._optimizers.append(o)
+                o.accelerator = self                  # AcceleratedOptimizer: step() / zero_grad() wait for sync_gradients
             elif isinstance(o, optim.PolynomialLR):
                 self._schedulers.append(o)
+                o.accelerator = self                  # AcceleratedScheduler: step() waits for sync_gradients
                 if self.num_processes > 1:
                     o = PreparedScheduler(o, self.num_processes)
             elif isinstance(o, torch.utils.data.DataLoader) and self.num_processes > 1:
@@ -260,27 +268,62 @@ class Accelerator:
         """accelerate strips only the distributed wrapper (`.module`); a PeftModel stays a PeftModel [REF train:347-350,577,598]."""
         return getattr(model, "module", model)
 
-    @contextmanager
-    def accumulate(self, model):
-        yield
-
-    def backward(self, loss, **kw):
-        """[REF train:557]: autograd backward, then DDP's gradient all-reduce -- one collective per prepared model."""
-        loss.backward(**kw)
+    def _trainers(self):
         from .training import trainer_of
         for m in self._models:
             tr = trainer_of(_inner_unet(m), create=False)
             if tr is not None:
-                tr.allreduce_grads_()
+                yield tr
+
+    @contextmanager
+    def accumulate(self, model=None):
+        """[REF train:494]: one entry per micro-batch; `sync_gradients` is true on the last of every K."""
+        K = self.gradient_accumulation_steps
+        first = self._micro_steps % K == 0
+        self._micro_steps += 1
+        self.sync_gradients = self._micro_steps % K == 0
+        if K > 1:
+            for tr in self._trainers():
+                tr.keep_grads = not first             # the window's first forward zeroes the flat gradient buffer, the others add
+        yield
+
+    def backward(self, loss, **kw):
+        """[REF train:557]: autograd backward (of loss / K), then -- when the window closes -- DDP's gradient all-reduce: one
+        collective per prepared model."""
+        K = self.gradient_accumulation_steps
+        (loss / K if K > 1 else loss).backward(**kw)
+        if not self.sync_gradients:
+            return
+        for tr in self._trainers():
+            tr.allreduce_grads_()
+
+    @staticmethod
+    def _whole_flat(params):
+        """The FlatLora whose parameter views `params` are, all of them and nothing else -- or None."""
+        flat = getattr(params[0], "_aldm_flat", (None,))[0]
+        if flat is None or len(params) != len(flat._plist) or {id(p) for p in params} != {id(p) for p, _, _ in flat._plist}:
+            return None
+        base = flat.grads.data_ptr()
+        if any(p.grad.data_ptr() != base + 4 * off or not p.grad.is_contiguous() for p, off, _ in flat._plist):
+            return None
+        return flat
 
     def clip_grad_norm_(self, parameters, max_norm, norm_type=2):
         """[REF train:559-561].  In the reference `parameters` is an already-exhausted iterator, so the call clips nothing
-        (SURVEY.md quirk Q1); with a real parameter list this clips the gradients in place like torch's utility."""
+        (SURVEY.md quirk Q1); with a real parameter list this clips the gradients in place like torch's utility.  When the list
+        is exactly the LoRA parameters of one training engine, whose .grads are views of ONE flat buffer, that is two launches
+        (aldm_sumsq_flat + aldm_clip_flat) and no host synchronisation; the returned norm is a device tensor either way."""
         params = [p for p in parameters if getattr(p, "grad", None) is not None]
         if not params:
             return torch.zeros((), device=self.device)
         if norm_type != 2:
             raise NotImplementedError("only the 2-norm is implemented")
+        flat = self._whole_flat(params)
+        if flat is not None:
+            from . import ops
+            norm = torch.empty(1, dtype=torch.float32, device=flat.grads.device)
+            ops.clip_flat(flat.grads[:flat.n], ops.sumsq_flat(flat.grads[:flat.n]), float(max_norm), norm)
+            return norm[0]
         total = torch.sqrt(sum((p.grad.detach().float() ** 2).sum() for p in params))
         coef = torch.clamp(max_norm / (total + 1e-6), max=1.0)
         for p in params:
@@ -317,12 +360,41 @@ class Accelerator:
             sd = {("base_model.model." + n): p.detach().float().cpu().contiguous() for n, p in m.named_parameters() if "lora_" in n}
             save_file(sd, os.path.join(output_dir, "model.safetensors" if i == 0 else f"model_{i}.safetensors"))
         if trainer is not None:
-            torch.save({"m": trainer.flat.m.cpu(), "v": trainer.flat.v.cpu(), "step": trainer.step_count},
-                       os.path.join(output_dir, "optimizer.bin"))
+            tsd = trainer.state_dict()
+            tsd.pop("params")                                 # (model.safetensors holds them)
+            torch.save(tsd, os.path.join(output_dir, "optimizer.bin"))
         for i, o in enumerate(self._optimizers):
             torch.save(o.state_dict(), os.path.join(output_dir, "optimizer.bin" if (i == 0 and trainer is None) else f"optimizer_{i}.bin"))
         for i, sch in enumerate(self._schedulers):
             torch.save(sch.state_dict(), os.path.join(output_dir, "scheduler.bin" if i == 0 else f"scheduler_{i}.bin"))
+
+    def load_state(self, input_dir, trainer=None):
+        """The inverse of save_state, on every rank: the LoRA tensors of `model.safetensors` by peft key, copied INTO the live
+        parameters (they stay views of the engine's flat buffer); moments and step count from `optimizer.bin`, in either layout
+        save_state writes (the LoraTrainer's or optim.AdamW.state_dict()'s); `last_epoch` from `scheduler.bin`."""
+        models = [_inner_unet(m) for m in self._models]
+        if trainer is not None and all(trainer.unet is not m for m in models):
+            models.append(trainer.unet)
+        if not models:
+            raise RuntimeError("Accelerator.load_state: nothing to load into -- pass the model through accelerator.prepare(...) first "
+                               "(or give load_state the LoraTrainer)")
+        from safetensors.torch import load_file
+        for i, m in enumerate(models):
+            sd = load_file(os.path.join(input_dir, "model.safetensors" if i == 0 else f"model_{i}.safetensors"))
+            mine = {("base_model.model." + n): p for n, p in m.named_parameters() if "lora_" in n}
+            if set(sd) != set(mine):
+                odd = sorted(set(sd) ^ set(mine))
+                raise RuntimeError(f"Accelerator.load_state: {input_dir} holds another adapter ({len(odd)} keys differ, e.g. {odd[:2]})")
+            with torch.no_grad():
+                for k, p in mine.items():
+                    p.copy_(sd[k].to(p.device, p.dtype))
+            m.invalidate_packed()
+        if trainer is not None:
+            trainer.load_state_dict(torch.load(os.path.join(input_dir, "optimizer.bin")))
+        for i, o in enumerate(self._optimizers):
+            o.load_state_dict(torch.load(os.path.join(input_dir, "optimizer.bin" if (i == 0 and trainer is None) else f"optimizer_{i}.bin")))
+        for i, sch in enumerate(self._schedulers):
+            sch.load_state_dict(torch.load(os.path.join(input_dir, "scheduler.bin" if i == 0 else f"scheduler_{i}.bin")))
 
     def end_training(self):
         self.wait_for_everyone()

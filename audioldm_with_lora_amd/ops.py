@@ -1447,6 +1447,50 @@ def adamw_flat(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
                                       grad_scale, _stream()), "aldm_adamw_flat")
 
 
+SUMSQ_PARTS = 256          # workgroups (= partial sums) of sumsq_flat: plenty for the <= 1.8 M floats of a LoRA gradient buffer
+
+
+def _flat_f32(*ts):
+    for t in ts:
+        _require_gpu(t)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.AldmError("flat-buffer kernels take contiguous fp32 tensors")
+
+
+def sumsq_flat(g, partials=None):
+    """partials [SUMSQ_PARTS] fp32: per-workgroup sums of squares of g (no float atomics: bitwise reproducible).  The consumers
+    (adamw_flat_clip, clip_flat) add them in index order."""
+    if partials is None:
+        partials = torch.empty(SUMSQ_PARTS, dtype=torch.float32, device=g.device)
+    _flat_f32(g, partials)
+    check(_lib.load().aldm_sumsq_flat(_p(g), g.numel(), _p(partials), partials.numel(), _stream()), "aldm_sumsq_flat")
+    return partials
+
+
+def adamw_flat_clip(p, g, m, v, lr, beta1, beta2, eps, wd, step, partials, max_norm, norm_out, grad_scale=1.0):
+    """adamw_flat on g * grad_scale * min(1, max_norm / (total + 1e-6)), total = sqrt(sum(partials)) * grad_scale -> norm_out[0]."""
+    _flat_f32(p, g, m, v, partials, norm_out)
+    n = p.numel()
+    assert g.numel() == n and m.numel() == n and v.numel() == n and norm_out.numel() >= 1
+    check(_lib.load().aldm_adamw_flat_clip(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, wd, step, grad_scale, _p(partials),
+                                           partials.numel(), max_norm, _p(norm_out), _stream()), "aldm_adamw_flat_clip")
+
+
+def clip_flat(g, partials, max_norm, norm_out, grad_scale=1.0):
+    """g *= min(1, max_norm / (total + 1e-6)) in place; norm_out[0] = total (see adamw_flat_clip)."""
+    _flat_f32(g, partials, norm_out)
+    assert norm_out.numel() >= 1
+    check(_lib.load().aldm_clip_flat(_p(g), g.numel(), _p(partials), partials.numel(), max_norm, grad_scale, _p(norm_out), _stream()),
+          "aldm_clip_flat")
+
+
+def accum_flat(acc, g, first):
+    """acc = g if first else acc + g."""
+    _flat_f32(acc, g)
+    assert acc.numel() == g.numel()
+    check(_lib.load().aldm_accum_flat(_p(acc), _p(g), g.numel(), int(bool(first)), _stream()), "aldm_accum_flat")
+
+
 # ---------------------------------------------------------------------------------------------------------
 # training-side wrappers (LoRA fine-tune step)
 # ---------------------------------------------------------------------------------------------------------
@@ -1635,6 +1679,20 @@ def lora_pack(jobs_dev, njobs):
 def mse_grad(pred, target, loss, grad_scale=1.0):
     dp = torch.empty(pred.shape, dtype=torch.bfloat16, device=pred.device)
     check(_lib.load().aldm_mse_grad(_p(pred), _p(target), pred.numel(), grad_scale, _p(dp), _p(loss), _stream()), "aldm_mse_grad")
+    return dp
+
+
+def mse_grad_snr(pred, target, loss, alphas_cumprod, timesteps, snr_gamma, grad_scale=1.0):
+    """mse_grad with diffusers' min-SNR-gamma weight per sample (epsilon prediction), looked up on the device: pred / target fp32
+    [B, ...], alphas_cumprod fp32 [T], timesteps int64 [B]."""
+    _require_gpu(pred)
+    B = timesteps.numel()
+    assert pred.dtype == torch.float32 and target.dtype == torch.float32 and pred.is_contiguous() and target.is_contiguous()
+    assert alphas_cumprod.dtype == torch.float32 and timesteps.dtype == torch.int64 and timesteps.is_contiguous()
+    assert pred.shape[0] == B and target.numel() == pred.numel() and pred.numel() % B == 0
+    dp = torch.empty(pred.shape, dtype=torch.bfloat16, device=pred.device)
+    check(_lib.load().aldm_mse_grad_snr(_p(pred), _p(target), pred.numel(), pred.numel() // B, _p(alphas_cumprod), _p(timesteps),
+                                        alphas_cumprod.numel(), snr_gamma, grad_scale, _p(dp), _p(loss), _stream()), "aldm_mse_grad_snr")
     return dp
 
 

@@ -9,6 +9,9 @@ The parameters are the LoRA A / B matrices.  Once the training engine exists (tr
 `Accelerator.prepare` or by the first training-mode `unet(...)` call) they are views into ONE flat fp32 buffer, their `.grad`s
 views into one flat gradient buffer, and `step()` is a single `aldm_adamw_flat` launch over the whole buffer (decoupled weight
 decay, bias-corrected moments: the arithmetic of torch.optim.AdamW, tested against it in tests/test_gpu_training.py).
+
+Passed through `Accelerator.prepare`, both follow accelerate's AcceleratedOptimizer / AcceleratedScheduler: inside a gradient
+accumulation window (`accelerator.sync_gradients` false) `step()` and `zero_grad()` do nothing.
 """
 import torch
 
@@ -25,11 +28,17 @@ class AdamW:
         self.param_groups = [dict(self.defaults, params=self.params, initial_lr=lr)]
         self.state = {}                      # per-parameter moments for parameters that are NOT in a flat buffer
         self._step = 0
+        self.accelerator = None              # set by Accelerator.prepare
+
+    def _holding(self):
+        return self.accelerator is not None and not self.accelerator.sync_gradients
 
     # ---- torch.optim.Optimizer surface the reference loop touches ----
     def zero_grad(self, set_to_none=True):
-        """The flat gradient buffer is cleared by the next forward (the engine zeroes it before the tape runs), so dropping
-        the views is all there is to do; set_to_none=False zeroes them in place."""
+        """The flat gradient buffer is cleared by the first forward of the next accumulation window (the engine zeroes it before
+        the tape runs), so dropping the views is all there is to do; set_to_none=False zeroes them in place."""
+        if self._holding():
+            return
         for p in self.params:
             if set_to_none:
                 p.grad = None
@@ -48,6 +57,8 @@ class AdamW:
     def step(self, closure=None):
         if closure is not None:
             raise NotImplementedError("closures are not used by the reference trainer")
+        if self._holding():
+            return
         g = self.param_groups[0]
         self._step += 1
         b1, b2 = g["betas"]
@@ -81,6 +92,24 @@ class AdamW:
             sd["state"] = {index[k]: {"m": st["m"].detach().cpu(), "v": st["v"].detach().cpu()} for k, st in self.state.items()}
         return sd
 
+    def load_state_dict(self, sd):
+        """Takes what state_dict() returns, or the {m, v, step} a LoraTrainer checkpoint holds (Accelerator.save_state writes either
+        as optimizer.bin).  Moments are copied into the existing buffers."""
+        self._step = int(sd["step"])
+        for k, v in (sd.get("param_groups") or [{}])[0].items():
+            if k != "params":
+                self.param_groups[0][k] = v
+        if "m" in sd:
+            flat, whole = self._flat_of()
+            if flat is None or not whole or sd["m"].numel() != flat.n:
+                raise AldmError("AdamW.load_state_dict: the checkpoint holds flat-buffer moments, but this optimiser's parameters are "
+                                "not (all of) one training engine's LoRA parameters")
+            flat.m.copy_(sd["m"].reshape(-1).to(flat.m.device))
+            flat.v.copy_(sd["v"].reshape(-1).to(flat.v.device))
+        for i, st in (sd.get("state") or {}).items():
+            p = self.params[int(i)]
+            self.state[id(p)] = dict(m=st["m"].to(p.device, torch.float32).clone(), v=st["v"].to(p.device, torch.float32).clone())
+
 
 class PolynomialLR:
     """diffusers.optimization.get_polynomial_decay_schedule_with_warmup(lr_end=1e-7, power=1.0): the lambda of
@@ -92,6 +121,7 @@ class PolynomialLR:
         if not self.lr_init > lr_end:
             raise ValueError(f"lr_end ({lr_end}) must be smaller than initial lr ({self.lr_init})")
         self.last_epoch = 0
+        self.accelerator = None              # set by Accelerator.prepare
         self._apply()
 
     def lr_at(self, step):
@@ -107,6 +137,8 @@ class PolynomialLR:
             g["lr"] = self.lr_at(self.last_epoch)
 
     def step(self):
+        if self.accelerator is not None and not self.accelerator.sync_gradients:
+            return
         self.last_epoch += 1
         self._apply()
 
@@ -115,6 +147,10 @@ class PolynomialLR:
 
     def state_dict(self):
         return {"last_epoch": self.last_epoch}
+
+    def load_state_dict(self, sd):
+        self.last_epoch = int(sd["last_epoch"])
+        self._apply()
 
 
 def get_scheduler(name, optimizer, num_warmup_steps=0, num_training_steps=None, lr_end=1e-7, power=1.0, **kw):

@@ -19,6 +19,10 @@ offline).  The dataset classes, the librosa mel front end and the CLAP / KAD met
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m audioldm_with_lora_amd.script.train \
         --max-train-steps 100
+
+Beyond the reference's literals (all off by default): `--gradient-accumulation-steps K` (the optimiser runs on every K-th
+micro-batch; `--max-train-steps` counts OPTIMISER steps), `--max-grad-norm` (the clip at 1.0 the reference means to apply, SURVEY
+quirk Q1), `--snr-gamma` (min-SNR loss weighting) and `--resume-from-checkpoint DIR` (a `checkpoint-<optimiser step>` directory).
 """
 import argparse
 import json
@@ -64,7 +68,7 @@ def synthetic_batch(B, g, vocab=50265, max_len=512, pad=1):
     return {"log_mel_spec": mel, "input_ids": ids, "attention_mask": mask}
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model-dir", default=None, help="local diffusers-format directory of cvssp/audioldm-s-full-v2")
     ap.add_argument("--input", choices=("latents", "mel"), default="latents")
@@ -81,9 +85,17 @@ def main(argv=None):
     ap.add_argument("--checkpointing-steps", type=int, default=9700 * 2)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--tiny", action="store_true", help="shrunken random-init models of the same topology (smoke tests)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--gradient-accumulation-steps", type=int, default=1, help="micro-batches per optimiser step")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the gradient 2-norm (off by default)")
+    ap.add_argument("--snr-gamma", type=float, default=None, help="min-SNR-gamma loss weighting (5.0 is the usual value)")
+    ap.add_argument("--resume-from-checkpoint", default=None, metavar="DIR", help="a checkpoint-<step> directory written by this driver")
+    return ap
 
-    accelerator = dp.Accelerator(gradient_accumulation_steps=1, mixed_precision=None)
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+
+    accelerator = dp.Accelerator(gradient_accumulation_steps=1, mixed_precision=None)     # (the trainer itself accumulates)
     device = accelerator.device
     torch.manual_seed(1234)                                       # identical base weights on every rank
     if args.model_dir:
@@ -100,7 +112,11 @@ def main(argv=None):
     peft_unet = get_peft_model(unet, cfg)
     unet.to(device)
     trainer = LoraTrainer(unet, noise_scheduler, lr=args.learning_rate, betas=(0.9, 0.999), weight_decay=args.weight_decay,
-                          eps=1e-08, max_train_steps=args.max_train_steps, device=device)
+                          eps=1e-08, max_train_steps=args.max_train_steps, device=device, max_grad_norm=args.max_grad_norm,
+                          gradient_accumulation_steps=args.gradient_accumulation_steps, snr_gamma=args.snr_gamma)
+    K = args.gradient_accumulation_steps
+    if args.resume_from_checkpoint:
+        accelerator.load_state(args.resume_from_checkpoint, trainer)
 
     vae = text_encoder = None
     if args.input == "mel":
@@ -116,11 +132,12 @@ def main(argv=None):
         vae.requires_grad_(False).to(device)
         text_encoder.requires_grad_(False).to(device)
     data = torch.load(args.latents_file) if args.latents_file else (torch.load(args.batches_file) if args.batches_file else None)
-    g = torch.Generator().manual_seed(args.seed + 1000 * accelerator.process_index)      # per-rank noise / timesteps
-    g_dev = torch.Generator(device=device).manual_seed(args.seed + 1000 * accelerator.process_index + 1)
+    # per-rank noise / timesteps; a resumed run draws a fresh stream, keyed by the step it resumes from
+    g = torch.Generator().manual_seed(args.seed + 1000 * accelerator.process_index + 7919 * trainer.step_count)
+    g_dev = torch.Generator(device=device).manual_seed(args.seed + 1000 * accelerator.process_index + 7919 * trainer.step_count + 1)
     B = args.train_batch_size
-    t0, train_loss = time.time(), 0.0
-    for global_step in range(1, args.max_train_steps + 1):
+    t0, train_loss, first_step = time.time(), 0.0, trainer.step_count + 1
+    for micro_step in range(trainer.micro_step + 1, args.max_train_steps * K + 1):
         if args.input == "mel":
             if data is not None:
                 idx = torch.randint(0, data["log_mel_spec"].shape[0], (B,), generator=g)
@@ -137,11 +154,18 @@ def main(argv=None):
         noise = torch.randn(latents.shape, generator=g)
         timesteps = torch.randint(0, noise_scheduler.config.num_train_timesteps, (B,), generator=g).long()
         loss = trainer.step(latents, noise, timesteps, prompt_embeds)
+        if micro_step % K:
+            continue                                              # inside an accumulation window: no optimiser step yet
+        global_step = trainer.step_count
         if global_step % 10 == 0 or global_step == args.max_train_steps:
-            train_loss = float(loss)
+            train_loss = float(trainer.window_loss if K > 1 else loss)
             if accelerator.is_main_process:
-                print(json.dumps({"step": global_step, "train_loss": train_loss, "lr": trainer.lr(global_step),
-                                  "clips_per_sec": global_step * B * accelerator.num_processes / (time.time() - t0)}), flush=True)
+                done = global_step - first_step + 1
+                rec = {"step": global_step, "train_loss": train_loss, "lr": trainer.lr(global_step),
+                       "clips_per_sec": done * K * B * accelerator.num_processes / (time.time() - t0)}
+                if trainer.last_grad_norm is not None:
+                    rec["grad_norm"] = float(trainer.last_grad_norm)      # device scalar, read at the logging cadence only
+                print(json.dumps(rec), flush=True)
         if global_step % args.checkpointing_steps == 0 and accelerator.is_main_process:
             accelerator.save_state(os.path.join(args.output_dir, f"checkpoint-{global_step}"), trainer)
     accelerator.wait_for_everyone()

@@ -320,6 +320,7 @@ class FlatLora:
         self.grads = torch.zeros(total + 1, dtype=torch.float32, device=device)     # last slot: loss (rides the all-reduce)
         self.m = torch.zeros(total, dtype=torch.float32, device=device)
         self.v = torch.zeros(total, dtype=torch.float32, device=device)
+        self.accum = None                 # gradient accumulation only (LoraTrainer gradient_accumulation_steps > 1): the window's sum
         self._off = {}
         self._plist = []
         self.on_change = None             # set by the owning trainer: called after any optimiser update of the buffer
@@ -382,7 +383,8 @@ def trainer_of(unet, create=True):
     if tr is None and create:
         if old is not None:
             tr = LoraTrainer(unet, old.scheduler, lr=old.lr0, betas=old.betas, weight_decay=old.wd, eps=old.eps,
-                             max_train_steps=old.max_train_steps, lr_end=old.lr_end, power=old.power, use_graph=old.use_graph)
+                             max_train_steps=old.max_train_steps, lr_end=old.lr_end, power=old.power, use_graph=old.use_graph,
+                             max_grad_norm=old.max_grad_norm, gradient_accumulation_steps=old.accum_steps, snr_gamma=old.snr_gamma)
             if tr.flat.names != old.flat.names or tr.flat.n != old.flat.n:
                 raise ops._lib.AldmError("trainer_of: the set of LoRA parameters changed under a live training engine -- its AdamW "
                                          "moments cannot be carried over; build a new LoraTrainer / optimizer explicitly")
@@ -390,6 +392,13 @@ def trainer_of(unet, create=True):
             tr.flat.m.copy_(old.flat.m.to(tr.flat.m.device))
             tr.flat.v.copy_(old.flat.v.to(tr.flat.v.device))
             tr.step_count = old.step_count
+            # ... and so does an open accumulation window: the micro-step counter and the gradients summed so far
+            tr.micro_step = old.micro_step
+            if old.keep_grads:                               # (the facade's window lives in the gradient buffer itself)
+                tr.keep_grads = True
+                tr.flat.grads.copy_(old.flat.grads.to(tr.flat.grads.device))
+            if old.window_open:
+                tr.flat.accum.copy_(old.flat.accum.to(tr.flat.accum.device))
         else:
             tr = LoraTrainer(unet, None, use_graph=False)
     elif tr is not None:
@@ -406,12 +415,26 @@ class LoraTrainer:
     """One process per GPU; `world`/`rank` follow torch.distributed when it is initialised (RCCL over xGMI)."""
 
     def __init__(self, unet: UNet2DConditionModel, scheduler=None, lr=1e-5, betas=(0.9, 0.999), weight_decay=1e-5, eps=1e-8,
-                 max_train_steps=97000, lr_end=1e-7, power=1.0, device="cuda", use_graph=True):
+                 max_train_steps=97000, lr_end=1e-7, power=1.0, device="cuda", use_graph=True, max_grad_norm=None,
+                 gradient_accumulation_steps=1, snr_gamma=None):
+        """max_grad_norm: clip the (all-rank mean, window-averaged) gradient's 2-norm like torch's clip_grad_norm_, on the device.
+        gradient_accumulation_steps = K: step() / step_from_batch() take one MICRO-batch per call and the optimiser runs on every
+        K-th.  snr_gamma: min-SNR-gamma loss weighting (diffusers' --snr_gamma, epsilon prediction).  All three default to off, and
+        then the launch sequence is the plain one."""
         self.unet, self.scheduler = unet, scheduler
         self.dev = torch.device(device)
         self.lr0, self.betas, self.wd, self.eps = lr, betas, weight_decay, eps
         self.max_train_steps, self.lr_end, self.power = max_train_steps, lr_end, power
         self.step_count = 0
+        if int(gradient_accumulation_steps) != gradient_accumulation_steps or gradient_accumulation_steps < 1:
+            raise ValueError(f"gradient_accumulation_steps must be a positive integer (got {gradient_accumulation_steps!r})")
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(f"max_grad_norm must be positive (got {max_grad_norm!r})")
+        if snr_gamma is not None and not snr_gamma > 0:
+            raise ValueError(f"snr_gamma must be positive (got {snr_gamma!r})")
+        self.max_grad_norm, self.accum_steps, self.snr_gamma = max_grad_norm, int(gradient_accumulation_steps), snr_gamma
+        self.micro_step = 0                                  # calls so far (optimiser steps: step_count)
+        self.keep_grads = False                              # autograd-shaped path: set by dp.Accelerator.accumulate inside a window
         self.dist = torch.distributed if (torch.distributed.is_available() and torch.distributed.is_initialized()) else None
         self.world = self.dist.get_world_size() if self.dist else 1
         if not any("lora_" in n for n, _ in unet.named_parameters()):
@@ -419,6 +442,12 @@ class LoraTrainer:
         _check_single_adapter(unet)
         self.flat = FlatLora(unet, self.dev)
         self.flat.on_change = unet.invalidate_packed         # an optimiser update makes the UNet's inference plan stale
+        if self.accum_steps > 1:
+            self.flat.accum = torch.zeros(self.flat.n + 1, dtype=torch.float32, device=self.dev)
+        self.last_grad_norm = self._partials = None
+        if max_grad_norm is not None:
+            self.last_grad_norm = torch.zeros(1, dtype=torch.float32, device=self.dev)    # pre-clip norm of the last optimiser step
+            self._partials = torch.zeros(ops.SUMSQ_PARTS, dtype=torch.float32, device=self.dev)
         self.use_graph, self.graph, self._static, self._eager_steps = use_graph, None, None, 0
         self._graph_tab, self._body_graphs, self._body_eager = None, {}, {}
         self.ac_dev = scheduler.alphas_cumprod.to(self.dev, torch.float32) if scheduler is not None else None
@@ -622,7 +651,8 @@ class LoraTrainer:
         f = self.flat
         b = sample.shape[0]
         self.repack()
-        f.grads.zero_()
+        if not self.keep_grads:                                  # (inside an Accelerator accumulation window the scatter keeps adding)
+            f.grads.zero_()
         t = timestep.to(device=self.dev, dtype=torch.float32).reshape(-1)
         if t.numel() == 1 and b > 1:
             t = t.expand(b)
@@ -674,7 +704,10 @@ class LoraTrainer:
         cls = ops.f32_to_bf16(prompt_embeds)
         tape = Tape(self.tnb)
         pred = self.forward(tape, x_in, t_dev, cls)
-        pred.g = ops.mse_grad(pred.t, tgt, f.grads[f.n:])
+        if self.snr_gamma is not None:
+            pred.g = ops.mse_grad_snr(pred.t, tgt, f.grads[f.n:], self.ac_dev, timesteps, self.snr_gamma)
+        else:
+            pred.g = ops.mse_grad(pred.t, tgt, f.grads[f.n:])
         tape.backward()
         self.tnb.launch()                                        # every dA / dB of the step: one launch (two if Rp differs)
 
@@ -787,14 +820,75 @@ class LoraTrainer:
         return self._apply_update(self.loss_and_grads(latents, noise, timesteps, prompt_embeds))
 
     def _apply_update(self, loss):
+        """What follows a micro-batch's forward / backward.  Plain (K = 1, no clip): the flat all-reduce and ONE AdamW launch.
+        K > 1: one accum_flat launch adds the micro-batch's gradients and loss slot into flat.accum (the graphs zero flat.grads at
+        their head and stay as they are); only the K-th call runs the collective and the optimiser, on accum, with
+        grad_scale = 1 / (world K).  max_grad_norm: sumsq_flat over the gradients WITHOUT the loss slot, after the all-reduce, then
+        adamw_flat_clip -- two launches where there was one, and nothing of it is visible to the host."""
         f = self.flat
+        K = self.accum_steps
+        src = f.grads
+        self.micro_step += 1
+        if K > 1:
+            ops.accum_flat(f.accum, f.grads, first=(self.micro_step - 1) % K == 0)
+            if self.window_open:
+                return loss.clone()                              # this rank's micro-batch loss (the slot is rewritten by the next call)
+            loss = loss.clone()
+            src = f.accum
         if self.dist and self.world > 1:
-            self.dist.all_reduce(f.grads)                         # ONE flat all-reduce: every LoRA grad + the loss slot
+            self.dist.all_reduce(src)                             # ONE flat all-reduce: every LoRA grad + the loss slot
         self.step_count += 1
-        ops.adamw_flat(f.params, f.grads, f.m, f.v, self.lr(self.step_count - 1), self.betas[0], self.betas[1], self.eps,
-                       self.wd, self.step_count, grad_scale=1.0 / self.world)
+        lr, scale = self.lr(self.step_count - 1), 1.0 / (self.world * K)
+        if self.max_grad_norm is not None:
+            ops.sumsq_flat(src[:f.n], self._partials)
+            ops.adamw_flat_clip(f.params, src[:f.n], f.m, f.v, lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count,
+                                self._partials, self.max_grad_norm, self.last_grad_norm, grad_scale=scale)
+        else:
+            ops.adamw_flat(f.params, src, f.m, f.v, lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, grad_scale=scale)
         # the adapter changed: the UNet's INFERENCE plan (bf16 A / B packed at plan time) is stale.  The trainer keeps its own
         # reference (self.P: frozen operands only; its LoRA operands are refreshed by repack()), so this only makes the next
         # pipe(unet=unet) / unet(...) call re-pack -- the in-training validation of [REF train:597-603] then sees the trained LoRA.
         self.unet.invalidate_packed()
-        return loss / self.world
+        return loss if K > 1 else loss / self.world
+
+    @property
+    def window_open(self):
+        """flat.accum holds the micro-batches of an unfinished accumulation window."""
+        return self.micro_step % self.accum_steps != 0
+
+    @property
+    def window_loss(self):
+        """All-rank mean loss of the last finished accumulation window (K > 1), as a device tensor."""
+        f = self.flat
+        return f.accum[f.n:] / (self.world * self.accum_steps)
+
+    # ---- checkpoint ----
+    def state_dict(self):
+        """What a resumed run needs besides the frozen base: the flat LoRA parameters, the AdamW moments, the optimiser-step count
+        and the micro-step counter (with the gradients of an unfinished accumulation window)."""
+        f = self.flat
+        sd = {"params": f.params.detach().cpu().clone(), "m": f.m.cpu().clone(), "v": f.v.cpu().clone(), "step": self.step_count,
+              "micro_step": self.micro_step, "names": list(f.names)}
+        if self.window_open:
+            sd["accum"] = f.accum.cpu().clone()
+        return sd
+
+    def load_state_dict(self, sd):
+        """Copies INTO the existing buffers (the parameters stay views of the flat buffer, captured graphs keep their pointers)."""
+        f = self.flat
+        if "names" in sd and list(sd["names"]) != list(f.names):
+            raise ops._lib.AldmError("LoraTrainer.load_state_dict: the checkpoint holds another set of LoRA parameters")
+        for k, dst in (("params", f.params), ("m", f.m), ("v", f.v)):
+            if k in sd:
+                if sd[k].numel() != f.n:
+                    raise ops._lib.AldmError(f"LoraTrainer.load_state_dict: {k!r} has {sd[k].numel()} elements, the adapter {f.n}")
+                dst.copy_(sd[k].reshape(-1).to(dst.device, torch.float32))
+        self.step_count = int(sd.get("step", self.step_count))
+        self.micro_step = int(sd.get("micro_step", self.step_count * self.accum_steps))
+        if self.window_open:
+            if sd.get("accum") is None or sd["accum"].numel() != f.n + 1:
+                raise ops._lib.AldmError("LoraTrainer.load_state_dict: the micro-step counter stands inside an accumulation window of "
+                                         f"{self.accum_steps} but the checkpoint holds no gradients for it (saved with another "
+                                         "gradient_accumulation_steps?)")
+            f.accum.copy_(sd["accum"].to(f.accum.device))
+        self.unet.invalidate_packed()                             # the adapter changed under the inference plan, as after a step

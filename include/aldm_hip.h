@@ -519,6 +519,12 @@ int aldm_lora_pack(const void* jobs_dev, int njobs, void* stream);
 int aldm_transpose_tokens(const void* in, int ld_in, int B, int N, int C, int Npad, void* out, void* stream);
 /* loss[0] += mean((pred-target)^2) ; dpred = 2 (pred-target)/n * grad_scale (bf16)  (F.mse_loss, [REF train:549]) */
 int aldm_mse_grad(const float* pred, const float* target, long long n, float grad_scale, void* dpred, float* loss, void* stream);
+/* the same with the min-SNR-gamma weight of diffusers' --snr_gamma (epsilon prediction) per sample b = i / per_sample, taken on the
+   device from the int64 timesteps t[B] and alphas_cumprod abar[n_train]:  snr = abar[t_b] / (1 - abar[t_b]),
+   w_b = min(snr, snr_gamma) / snr;  loss[0] += (1/n) sum w_b e_i^2;  dpred_i = 2 w_b e_i / n * grad_scale (bf16).
+   i.e. (mse(reduction="none").mean(dim=[1,2,3]) * w).mean().  n must be a multiple of per_sample. */
+int aldm_mse_grad_snr(const float* pred, const float* target, long long n, long long per_sample, const float* abar,
+                      const long long* t, int n_train, float snr_gamma, float grad_scale, void* dpred, float* loss, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training helpers (configs 3/4): fused AdamW over one flat fp32 LoRA buffer
@@ -526,6 +532,22 @@ int aldm_mse_grad(const float* pred, const float* target, long long n, float gra
  * ------------------------------------------------------------------------------------------ */
 int aldm_adamw_flat(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream);
+/* Gradient-norm clipping (torch.nn.utils.clip_grad_norm_, 2-norm, error_if_nonfinite=False) and gradient accumulation over the
+   same flat buffer.  No float atomics: the norm is bitwise reproducible from launch to launch.
+   sumsq_flat: partials[b] = sum of squares of the elements workgroup b of a fixed npart-workgroup grid-stride grid sees
+   (1 <= npart <= 1024; 256 is plenty for 1.8 M floats).  Consumers add the partials themselves, in index order:
+     total = sqrt(sum partials) * grad_scale      (the norm of g * grad_scale, the gradient the optimiser sees)
+     coef  = min(1, max_norm / (total + 1e-6))    (a non-finite total propagates as in torch)
+   adamw_flat_clip: aldm_adamw_flat on g * grad_scale * coef;  clip_flat: g *= coef in place (coef = 1 changes no bit).
+   Both store norm_out[0] = total (device memory: logging needs no host synchronisation). */
+int aldm_sumsq_flat(const float* g, long long n, float* partials, int npart, void* stream);
+int aldm_adamw_flat_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, int step, float grad_scale, const float* partials, int npart, float max_norm,
+                         float* norm_out, void* stream);
+int aldm_clip_flat(float* g, long long n, const float* partials, int npart, float max_norm, float grad_scale, float* norm_out,
+                   void* stream);
+/* acc[i] = first ? g[i] : acc[i] + g[i] over n floats (the micro-batch's gradients + loss slot into the accumulation window) */
+int aldm_accum_flat(float* acc, const float* g, long long n, int first, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Log-mel front end: the dataloader's mel_spectrogram_train + pad_spec
