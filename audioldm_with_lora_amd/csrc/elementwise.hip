@@ -583,6 +583,91 @@ __global__ void gaussian_sample_kernel(const float* __restrict__ params, const f
   out[idx] = mean + __expf(0.5f * lv) * nz[idx];
 }
 
+// The training step's batch noising as ONE launch (stream contract: philox.h).  It restates, term by term, what the host-noise path
+// runs as seven launches -- nhwc_to_nchw of the moments, gaussian_sample_kernel, the multiply by scaling_factor, add_noise_t_kernel and
+// the two nchw_to_nhwc of the noisy latents / the noise -- with all randomness drawn HERE from the Philox state:
+//   t_b   = __umulhi(word_b of draw d, T)
+//   lat   = (mean + exp(0.5 clamp(logvar, -30, 20)) e) scaling_factor      (moments: fp32 NHWC [B][HW][2C] = mean | logvar, e = draw d + 1)
+//         = latents[b][c][p]                                                (latents: fp32 NCHW; draw d + 1 is consumed unused)
+//   n'    = n + noise_offset o[b][c]                                        (n = draw d + 2, o = draw d + 3; two roundings, no fma)
+//   x_in  = bf16(sqrt(abar[t_b]) lat + sqrt(1 - abar[t_b]) n') ,  target = n'        both NHWC [B][HW][C]
+// A thread owns VEC consecutive NCHW elements (VEC = 4: one Philox block of e and of n; VEC = 1: the element's block, its lane) and
+// maps each to its NHWC slot on its own, so a block may straddle a channel or a sample.  The first B threads of the grid store
+// timesteps / t_f32.  The ordinal moves by 4 by the last-workgroup ticket of the fused sampler steps: every workgroup loads the state
+// when it starts, the last one through the agent-scope ticket stores d + 4.  ticket == NULL: the ordinal stays.
+template <int VEC>
+__global__ __launch_bounds__(256) void train_noise_fused_kernel(uint32_t* __restrict__ rng, const float* __restrict__ abar, int n_train,
+                                                                const float* __restrict__ moments, const float* __restrict__ latents,
+                                                                float sf, float noise_offset, unsigned B, unsigned C, unsigned HW,
+                                                                bf16* __restrict__ x_in, float* __restrict__ target,
+                                                                long long* __restrict__ t_out, float* __restrict__ t_f32,
+                                                                unsigned* __restrict__ ticket) {
+  const PhiloxState s0 = philox_load(rng);
+  const unsigned tix = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned chw = C * HW, total = B * chw;               // (the entry point checks total < 2^31)
+  if (tix < B) {
+    const unsigned t = __umulhi(philox_word1(s0, tix), (unsigned)n_train);
+    t_out[tix] = (long long)t;
+    t_f32[tix] = (float)t;
+  }
+  const unsigned idx = tix * VEC;
+  if (tix < (total + VEC - 1) / VEC) {
+    const PhiloxState s1 = philox_at(s0, 1), s2 = philox_at(s0, 2), s3 = philox_at(s0, 3);
+    const f32x4 n4 = philox_normal4(s2, (unsigned long long)(idx >> 2));
+    f32x4 e4 = {0.f, 0.f, 0.f, 0.f};
+    if (moments) e4 = philox_normal4(s1, (unsigned long long)(idx >> 2));
+    unsigned pb = ~0u, pbc = ~0u;
+    float ca = 0.f, cs = 0.f, o = 0.f;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const unsigned i = idx + k;
+      const int lane = VEC == 4 ? k : (int)(idx & 3);
+      const unsigned b = i / chw, r = i - b * chw, c = r / HW, p = r - c * HW;
+      if (b != pb) {                                          // (sample boundary inside the thread's elements: look the coefficients up again)
+        const float a = abar[__umulhi(philox_word1(s0, b), (unsigned)n_train)];
+        ca = sqrtf(a);
+        cs = sqrtf(1.f - a);
+        pb = b;
+      }
+      float nz = lane == 0 ? n4[0] : lane == 1 ? n4[1] : lane == 2 ? n4[2] : n4[3];
+      if (noise_offset != 0.f) {                              // (uniform over the grid)
+        const unsigned bc = b * C + c;
+        if (bc != pbc) {
+          o = philox_normal1(s3, bc);
+          pbc = bc;
+        }
+        {
+#pragma clang fp contract(off)                                  // two roundings, as the two torch ops of the host recipe: no fma
+          const float od = noise_offset * o;
+          nz = nz + od;
+        }
+      }
+      const unsigned long long pix = (unsigned long long)b * HW + p;
+      float lat;
+      if (moments) {
+        const float* m = moments + pix * 2 * C;
+        const float lv = fminf(fmaxf(m[C + c], -30.f), 20.f);
+        const float e = lane == 0 ? e4[0] : lane == 1 ? e4[1] : lane == 2 ? e4[2] : e4[3];
+        lat = (m[c] + __expf(0.5f * lv) * e) * sf;
+      } else {
+        lat = latents[i];
+      }
+      x_in[pix * C + c] = (bf16)(ca * lat + cs * nz);
+      target[pix * C + c] = nz;
+    }
+  }
+  if (!ticket) return;                                        // (uniform over the grid)
+  __syncthreads();                                            // every thread of this workgroup has read the RNG state
+  if (threadIdx.x == 0) {
+    // acq_rel at agent scope, as in ddim_step_fused_kernel
+    const unsigned done = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (done == gridDim.x - 1) {
+      ticket[0] = 0;
+      philox_store_ordinal(rng, philox_at(s0, 4));
+    }
+  }
+}
+
 // Holds the stream busy for ~us microseconds (one wave polling the 100 MHz real-time counter).  Measurement aid: lets a
 // host that enqueues slower than the GPU executes build up a queue, so per-kernel event pairs time kernels, not host gaps.
 __global__ void sleep_kernel(unsigned long long ticks) {
@@ -793,6 +878,27 @@ extern "C" int aldm_gaussian_sample(const float* params, const float* noise, int
   hipLaunchKernelGGL(gaussian_sample_kernel, dim3(blocks_for((long long)B * chw, 256)), dim3(256), 0, (hipStream_t)stream, params, noise,
                      B, chw, out);
   return aldm_launch_status("gaussian_sample");
+}
+
+extern "C" int aldm_train_noise_fused(unsigned* rng_state, const float* alphas_cumprod, int n_train, const float* moments,
+                                      const float* latents, float scaling_factor, float noise_offset, int B, int C, int H, int W,
+                                      void* x_in_bf16, float* target, long long* timesteps, float* t_f32, unsigned* ticket, void* stream) {
+  ALDM_CHECK_ARG(rng_state && alphas_cumprod && x_in_bf16 && target && timesteps && t_f32 && n_train > 0, "train_noise_fused: bad args");
+  ALDM_CHECK_ARG((moments != nullptr) != (latents != nullptr), "train_noise_fused: give the moments or the latents, not both");
+  ALDM_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && (long long)B * C * H * W < (1ll << 31), "train_noise_fused: bad geometry");
+  const long long total = (long long)B * C * H * W;
+  const int vec = total % 4 == 0 ? 4 : 1;
+  const long long work = (total + vec - 1) / vec;
+  const unsigned nblk = blocks_for(work > B ? work : (long long)B, 256);     // (the first B threads store the timesteps)
+  if (vec == 4)
+    hipLaunchKernelGGL(train_noise_fused_kernel<4>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, rng_state, alphas_cumprod, n_train, moments,
+                       latents, scaling_factor, noise_offset, (unsigned)B, (unsigned)C, (unsigned)(H * W), (bf16*)x_in_bf16, target, timesteps,
+                       t_f32, ticket);
+  else
+    hipLaunchKernelGGL(train_noise_fused_kernel<1>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, rng_state, alphas_cumprod, n_train, moments,
+                       latents, scaling_factor, noise_offset, (unsigned)B, (unsigned)C, (unsigned)(H * W), (bf16*)x_in_bf16, target, timesteps,
+                       t_f32, ticket);
+  return aldm_launch_status("train_noise_fused");
 }
 
 extern "C" int aldm_sleep_us(int us, void* stream) {

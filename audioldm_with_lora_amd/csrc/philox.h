@@ -6,6 +6,15 @@
 // block = element_index / 4 and draw the 64-bit ordinal of the tensor-sized draw within the stream.  Element e of draw d is lane
 // e % 4 of block e / 4, so a one-element-per-thread kernel and a four-wide one read the same words.
 // The state is four 32-bit words in DEVICE memory: {seed_lo, seed_hi, draw_lo, draw_hi}.
+//
+// Training-step stream contract (aldm_train_noise_fused, elementwise.hip).  A step that finds the ordinal at d uses FOUR draws and
+// leaves the ordinal at d + 4 -- always four, whether or not the noise offset is on and whether the latents come from the VAE moments
+// or ready-made, so streams stay aligned across option changes:
+//   d      B raw words        t_b = __umulhi(word_b, T)                    the timestep of sample b, uniform on [0, T)
+//   d + 1  B*C*H*W normals    e, the posterior noise of latent_dist.sample()   (element index = the flat NCHW index)
+//   d + 2  B*C*H*W normals    n, the diffusion noise                           (the same indexing)
+//   d + 3  B*C normals        o, the noise offset's per-(sample, channel) normal
+// Element i of each draw is element i of aldm_philox_u32 / aldm_randn for the same state with the ordinal set to that draw.
 #pragma once
 #include "common.h"
 
@@ -20,6 +29,18 @@ __device__ __forceinline__ void philox_store_next(uint32_t* state, const PhiloxS
   const uint32_t lo = s.draw_lo + 1u;
   state[2] = lo;
   state[3] = s.draw_hi + (lo == 0u ? 1u : 0u);
+}
+
+// the state `k` draws further on: {draw_lo, draw_hi} + k as one 64-bit ordinal
+__device__ __forceinline__ PhiloxState philox_at(const PhiloxState& s, uint32_t k) {
+  const uint32_t lo = s.draw_lo + k;
+  return PhiloxState{s.seed_lo, s.seed_hi, lo, s.draw_hi + (lo < k ? 1u : 0u)};
+}
+
+// stores the ordinal of `s` (philox_at of what was loaded): two ordinary global stores by the one thread that owns the advance
+__device__ __forceinline__ void philox_store_ordinal(uint32_t* state, const PhiloxState& s) {
+  state[2] = s.draw_lo;
+  state[3] = s.draw_hi;
 }
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
@@ -68,4 +89,18 @@ __device__ __forceinline__ f32x4 philox_normal4(const PhiloxState& s, unsigned l
   box_muller(w[2], w[3], a, b);
   z[2] = a; z[3] = b;
   return z;
+}
+
+// one element of the current draw: its whole block, then its lane -- the bits a four-wide reader of the same block sees
+__device__ __forceinline__ uint32_t philox_word1(const PhiloxState& s, unsigned long long e) {
+  uint32_t w[4];
+  philox_block(s, e >> 2, w);
+  const int lane = (int)(e & 3);
+  return lane == 0 ? w[0] : lane == 1 ? w[1] : lane == 2 ? w[2] : w[3];
+}
+
+__device__ __forceinline__ float philox_normal1(const PhiloxState& s, unsigned long long e) {
+  const f32x4 z = philox_normal4(s, e >> 2);
+  const int lane = (int)(e & 3);
+  return lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3];
 }

@@ -1327,6 +1327,17 @@ def philox_state_values(state):
     return w[0] | (w[1] << 32), w[2] | (w[3] << 32)
 
 
+def philox_set(state, seed=None, draw=None):
+    """Sets the seed and / or the draw ordinal of a philox_state IN PLACE (the tensor keeps its address, so a captured graph that
+    reads it goes on from the new values)."""
+    _check_state(state)
+    if seed is not None:
+        state[:2].copy_(torch.tensor(_u32_words(seed), dtype=torch.int32))
+    if draw is not None:
+        state[2:].copy_(torch.tensor(_u32_words(draw), dtype=torch.int32))
+    return state
+
+
 def _check_state(state):
     _require_gpu(state)
     assert state.dtype == torch.int32 and state.numel() == 4 and state.is_contiguous(), "philox state: int32 [4] (ops.philox_state)"
@@ -1423,6 +1434,46 @@ def gaussian_sample(params_nchw, noise):
     out = torch.empty_like(nf)
     check(_lib.load().aldm_gaussian_sample(_p(pf), _p(nf), B, nf.numel() // B, _p(out), _stream()), "aldm_gaussian_sample")
     return out
+
+
+def train_noise_fused(state, alphas_cumprod, moments=None, latents=None, scaling_factor=1.0, noise_offset=0.0, ticket=None,
+                      timesteps_out=None):
+    """The training step's batch noising with on-device randomness as one launch (aldm_train_noise_fused; stream contract in
+    csrc/philox.h): timesteps, the posterior noise, the diffusion noise and the noise offset's normals are draws d .. d + 3 of `state`.
+    Exactly one source: moments fp32 channels-last [B, H, W, 2C] (mean | logvar, what vae.encode_nhwc returns; the sample is scaled by
+    scaling_factor) or latents fp32 NCHW [B, C, H, W].  alphas_cumprod fp32 [T].  ticket: int32 [1], zero (the kernel leaves it zero) --
+    the ordinal then moves by 4 on the device; None leaves the state alone.  timesteps_out: int64 [B] to write the timesteps into.
+    Returns (x_in bf16 [B, H, W, C], target fp32 [B, H, W, C], timesteps int64 [B], t_f32 fp32 [B])."""
+    _check_state(state)
+    if (moments is None) == (latents is None):
+        raise _lib.AldmError("train_noise_fused: give either moments= or latents=")
+    src = moments if moments is not None else latents
+    _require_gpu(src)
+    _require_gpu(alphas_cumprod)
+    assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 4, "train_noise_fused: fp32 contiguous 4-d source"
+    assert alphas_cumprod.dtype == torch.float32 and alphas_cumprod.is_contiguous()
+    if moments is not None:
+        B, H, W, C2 = moments.shape
+        assert C2 % 2 == 0, "moments: channels-last mean | logvar"
+        Cc = C2 // 2
+    else:
+        B, Cc, H, W = latents.shape
+    assert ticket is None or (ticket.dtype == torch.int32 and ticket.numel() == 1 and ticket.is_cuda)
+    dev = src.device
+    x_in = torch.empty(B, H, W, Cc, dtype=torch.bfloat16, device=dev)
+    target = torch.empty(B, H, W, Cc, dtype=torch.float32, device=dev)
+    if timesteps_out is None:
+        timesteps_out = torch.empty(B, dtype=torch.int64, device=dev)
+    assert timesteps_out.dtype == torch.int64 and timesteps_out.numel() == B and timesteps_out.is_contiguous() and timesteps_out.is_cuda
+    t_f32 = torch.empty(B, dtype=torch.float32, device=dev)
+    n = x_in.numel()
+    # flops: ~100 per normal (ten Philox rounds + Box-Muller), two normals per element; bytes: the source, bf16 + fp32 out
+    check(_launch("train_noise_fused", 220.0 * n, ((8.0 if moments is not None else 4.0) + 6.0) * n,
+                  lambda: _lib.load().aldm_train_noise_fused(_p(state), _p(alphas_cumprod), alphas_cumprod.numel(), _p(moments), _p(latents),
+                                                             float(scaling_factor), float(noise_offset), B, Cc, H, W, _p(x_in), _p(target),
+                                                             _p(timesteps_out), _p(t_f32), _p(ticket), _stream())),
+          "aldm_train_noise_fused")
+    return x_in, target, timesteps_out, t_f32
 
 
 def sleep_us(us):

@@ -23,6 +23,11 @@ offline).  The dataset classes, the librosa mel front end and the CLAP / KAD met
 Beyond the reference's literals (all off by default): `--gradient-accumulation-steps K` (the optimiser runs on every K-th
 micro-batch; `--max-train-steps` counts OPTIMISER steps), `--max-grad-norm` (the clip at 1.0 the reference means to apply, SURVEY
 quirk Q1), `--snr-gamma` (min-SNR loss weighting) and `--resume-from-checkpoint DIR` (a `checkpoint-<optimiser step>` directory).
+`--device-noise` draws every step's timesteps, diffusion noise and posterior noise on the device from the trainer's Philox stream
+(seeded by `--seed`; rank r reads the counters from r * 2^48 on) instead of on the host, inside the step's captured graph; with
+`--input mel` the whole loop body then runs as LoraTrainer.step_from_batch.  `--noise-offset X` (diffusers' --noise_offset) needs it.
+The checkpoint carries that stream's position, so a resumed `--device-noise` run draws exactly what the uninterrupted run would
+have; the host-drawn stream of a resumed run is a fresh one, keyed by the step it resumes from.
 """
 import argparse
 import json
@@ -88,12 +93,17 @@ def build_parser():
     ap.add_argument("--gradient-accumulation-steps", type=int, default=1, help="micro-batches per optimiser step")
     ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the gradient 2-norm (off by default)")
     ap.add_argument("--snr-gamma", type=float, default=None, help="min-SNR-gamma loss weighting (5.0 is the usual value)")
+    ap.add_argument("--device-noise", action="store_true", help="draw noise and timesteps on the device (Philox stream seeded by --seed)")
+    ap.add_argument("--noise-offset", type=float, default=0.0, help="diffusers' noise offset; needs --device-noise")
     ap.add_argument("--resume-from-checkpoint", default=None, metavar="DIR", help="a checkpoint-<step> directory written by this driver")
     return ap
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.noise_offset != 0.0 and not args.device_noise:
+        parser.error("--noise-offset applies to noise drawn on the device: add --device-noise")
 
     accelerator = dp.Accelerator(gradient_accumulation_steps=1, mixed_precision=None)     # (the trainer itself accumulates)
     device = accelerator.device
@@ -113,7 +123,8 @@ def main(argv=None):
     unet.to(device)
     trainer = LoraTrainer(unet, noise_scheduler, lr=args.learning_rate, betas=(0.9, 0.999), weight_decay=args.weight_decay,
                           eps=1e-08, max_train_steps=args.max_train_steps, device=device, max_grad_norm=args.max_grad_norm,
-                          gradient_accumulation_steps=args.gradient_accumulation_steps, snr_gamma=args.snr_gamma)
+                          gradient_accumulation_steps=args.gradient_accumulation_steps, snr_gamma=args.snr_gamma,
+                          noise_seed=(args.seed if args.device_noise else None), noise_offset=args.noise_offset)
     K = args.gradient_accumulation_steps
     if args.resume_from_checkpoint:
         accelerator.load_state(args.resume_from_checkpoint, trainer)
@@ -132,7 +143,9 @@ def main(argv=None):
         vae.requires_grad_(False).to(device)
         text_encoder.requires_grad_(False).to(device)
     data = torch.load(args.latents_file) if args.latents_file else (torch.load(args.batches_file) if args.batches_file else None)
-    # per-rank noise / timesteps; a resumed run draws a fresh stream, keyed by the step it resumes from
+    # per-rank noise / timesteps drawn on the host; a resumed run draws a fresh stream, keyed by the step it resumes from.  With
+    # --device-noise these generators only pick the data: noise and timesteps come from the trainer's Philox stream, whose position
+    # load_state has just restored, so the resumed run continues the saved stream.
     g = torch.Generator().manual_seed(args.seed + 1000 * accelerator.process_index + 7919 * trainer.step_count)
     g_dev = torch.Generator(device=device).manual_seed(args.seed + 1000 * accelerator.process_index + 7919 * trainer.step_count + 1)
     B = args.train_batch_size
@@ -144,16 +157,22 @@ def main(argv=None):
                 batch = {k: data[k][idx] for k in ("log_mel_spec", "input_ids", "attention_mask")}
             else:
                 batch = synthetic_batch(B, g, vocab=text_encoder.cfg["vocab_size"])
-            latents, prompt_embeds = encode_batch(vae, text_encoder, batch, g_dev)
+            if args.device_noise:
+                loss = trainer.step_from_batch(vae, text_encoder, batch, None, None, None)
+            else:
+                latents, prompt_embeds = encode_batch(vae, text_encoder, batch, g_dev)
         elif data is not None:
             idx = torch.randint(0, data["latents"].shape[0], (B,), generator=g)
             latents, prompt_embeds = data["latents"][idx], data["prompt_embeds"][idx]
         else:
             latents = torch.randn(B, 8, 256, 16, generator=g) * 0.9228
             prompt_embeds = torch.nn.functional.normalize(torch.randn(B, unet.cfg["class_embed_input_dim"], generator=g), dim=-1)
-        noise = torch.randn(latents.shape, generator=g)
-        timesteps = torch.randint(0, noise_scheduler.config.num_train_timesteps, (B,), generator=g).long()
-        loss = trainer.step(latents, noise, timesteps, prompt_embeds)
+        if not args.device_noise:
+            noise = torch.randn(latents.shape, generator=g)
+            timesteps = torch.randint(0, noise_scheduler.config.num_train_timesteps, (B,), generator=g).long()
+            loss = trainer.step(latents, noise, timesteps, prompt_embeds)
+        elif args.input != "mel":
+            loss = trainer.step(latents, None, None, prompt_embeds)
         if micro_step % K:
             continue                                              # inside an accumulation window: no optimiser step yet
         global_step = trainer.step_count

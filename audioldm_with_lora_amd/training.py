@@ -384,7 +384,8 @@ def trainer_of(unet, create=True):
         if old is not None:
             tr = LoraTrainer(unet, old.scheduler, lr=old.lr0, betas=old.betas, weight_decay=old.wd, eps=old.eps,
                              max_train_steps=old.max_train_steps, lr_end=old.lr_end, power=old.power, use_graph=old.use_graph,
-                             max_grad_norm=old.max_grad_norm, gradient_accumulation_steps=old.accum_steps, snr_gamma=old.snr_gamma)
+                             max_grad_norm=old.max_grad_norm, gradient_accumulation_steps=old.accum_steps, snr_gamma=old.snr_gamma,
+                             noise_seed=old.noise_seed, noise_offset=old.noise_offset)
             if tr.flat.names != old.flat.names or tr.flat.n != old.flat.n:
                 raise ops._lib.AldmError("trainer_of: the set of LoRA parameters changed under a live training engine -- its AdamW "
                                          "moments cannot be carried over; build a new LoraTrainer / optimizer explicitly")
@@ -399,6 +400,8 @@ def trainer_of(unet, create=True):
                 tr.flat.grads.copy_(old.flat.grads.to(tr.flat.grads.device))
             if old.window_open:
                 tr.flat.accum.copy_(old.flat.accum.to(tr.flat.accum.device))
+            if old.noise_state is not None:                  # ... and the noise stream goes on where it stood
+                ops.philox_set(tr.noise_state, *ops.philox_state_values(old.noise_state))
         else:
             tr = LoraTrainer(unet, None, use_graph=False)
     elif tr is not None:
@@ -409,6 +412,29 @@ def trainer_of(unet, create=True):
 
 FOLD_NORM3 = os.environ.get("ALDM_NO_FOLD_NORM3") is None             # training forward: norm3 folded into the GEGLU GEMM (A/B aid)
 SIDE_STREAM_H2D = os.environ.get("ALDM_NO_SIDE_STREAM_H2D") is None      # step_from_batch: batch copies on a side stream (A/B aid)
+RANK_ORDINAL_STRIDE = 2 ** 48     # device noise: rank r starts at draw ordinal r * 2^48 of the one key (2^46 steps before two ranks meet)
+
+
+def noise_ordinal_base(rank):
+    """The first draw ordinal of a rank's noise stream: ranks read disjoint counters of one key."""
+    return int(rank) * RANK_ORDINAL_STRIDE
+
+
+def check_noise_args(noise_seed, noise_offset, passed):
+    """Where a step's noise / timesteps come from.  passed: the noise tensors of the call (all tensors or all None).  Returns True
+    when the step draws them on the device, False when the host passed them; raises AldmError on a combination that has no meaning."""
+    given = [t is not None for t in passed]
+    if any(given) and not all(given):
+        raise ops._lib.AldmError("LoraTrainer: pass the noise tensors and the timesteps all together, or None for all of them")
+    if not any(given):
+        if noise_seed is None:
+            raise ops._lib.AldmError("LoraTrainer: no noise / timesteps were passed and the trainer has no noise_seed to draw them "
+                                     "on the device")
+        return True
+    if noise_offset != 0.0:
+        raise ops._lib.AldmError("LoraTrainer: noise_offset applies to noise drawn on the device; the host owns the noise it passes "
+                                 "(add the offset there, or pass None)")
+    return False
 
 
 class LoraTrainer:
@@ -416,8 +442,12 @@ class LoraTrainer:
 
     def __init__(self, unet: UNet2DConditionModel, scheduler=None, lr=1e-5, betas=(0.9, 0.999), weight_decay=1e-5, eps=1e-8,
                  max_train_steps=97000, lr_end=1e-7, power=1.0, device="cuda", use_graph=True, max_grad_norm=None,
-                 gradient_accumulation_steps=1, snr_gamma=None):
-        """max_grad_norm: clip the (all-rank mean, window-averaged) gradient's 2-norm like torch's clip_grad_norm_, on the device.
+                 gradient_accumulation_steps=1, snr_gamma=None, noise_seed=None, noise_offset=0.0):
+        """noise_seed: with a seed the trainer owns an on-device Philox stream (key = the seed, ordinal from rank * 2^48) and
+        step(latents, None, None, emb) / step_from_batch(..., None, None, None) draw the timesteps and both noises from it inside ONE
+        fused launch (four draw ordinals per call, csrc/philox.h); tensors passed in still run the host-noise launch sequence.
+        noise_offset: diffusers' --noise_offset on the device-drawn noise.  None / 0: exactly the host-noise trainer.
+        max_grad_norm: clip the (all-rank mean, window-averaged) gradient's 2-norm like torch's clip_grad_norm_, on the device.
         gradient_accumulation_steps = K: step() / step_from_batch() take one MICRO-batch per call and the optimiser runs on every
         K-th.  snr_gamma: min-SNR-gamma loss weighting (diffusers' --snr_gamma, epsilon prediction).  All three default to off, and
         then the launch sequence is the plain one."""
@@ -437,6 +467,7 @@ class LoraTrainer:
         self.keep_grads = False                              # autograd-shaped path: set by dp.Accelerator.accumulate inside a window
         self.dist = torch.distributed if (torch.distributed.is_available() and torch.distributed.is_initialized()) else None
         self.world = self.dist.get_world_size() if self.dist else 1
+        self.rank = self.dist.get_rank() if self.dist else 0
         if not any("lora_" in n for n, _ in unet.named_parameters()):
             raise ops._lib.AldmError("LoraTrainer: the UNet carries no LoRA parameters (call get_peft_model first)")
         _check_single_adapter(unet)
@@ -452,6 +483,13 @@ class LoraTrainer:
         self._graph_tab, self._body_graphs, self._body_eager = None, {}, {}
         self.ac_dev = scheduler.alphas_cumprod.to(self.dev, torch.float32) if scheduler is not None else None
         self._tape = None
+        self.noise_seed, self.noise_offset = (None if noise_seed is None else int(noise_seed)), float(noise_offset)
+        self.noise_state = self._noise_ticket = None
+        self.last_timesteps = None                           # device int64 [B]: the timesteps of the last forward / backward
+        self._ts_bufs = {}
+        if self.noise_seed is not None:
+            self.noise_state = ops.philox_state(self.noise_seed, noise_ordinal_base(self.rank), self.dev)
+            self._noise_ticket = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self._build_sites()
         self.weights_version = unet._weights_version
         unet.__dict__["_trainer"] = self                     # plain attribute (not a submodule): unet(...) in training mode finds it
@@ -690,17 +728,32 @@ class LoraTrainer:
             return self.lr_end
         return (self.lr0 - self.lr_end) * (1 - step / self.max_train_steps) ** self.power + self.lr_end
 
-    def _fwd_bwd(self, latents, noise, timesteps, prompt_embeds):
-        """Device-only launch sequence (capturable): repack LoRA -> add_noise -> forward tape -> MSE -> backward."""
+    def _timesteps_buf(self, B):
+        """The trainer-owned timestep buffer of a batch size (device noise): one address for the eager steps and every graph."""
+        if B not in self._ts_bufs:
+            self._ts_bufs[B] = torch.zeros(B, dtype=torch.int64, device=self.dev)
+        return self._ts_bufs[B]
+
+    def _fwd_bwd(self, latents, noise, timesteps, prompt_embeds, moments=None, scaling_factor=1.0):
+        """Device-only launch sequence (capturable): repack LoRA -> add_noise -> forward tape -> MSE -> backward.
+        noise None: the timesteps and the noise are drawn here, on the device -- one fused launch from the latents or from the VAE
+        `moments` (channels-last, then latents is None) to the UNet input, the loss target and the timesteps."""
         f = self.flat
         self.repack()
         f.grads.zero_()
         if self.ac_dev is None:
             raise ops._lib.AldmError("LoraTrainer.step needs the noise scheduler (pass scheduler= to the constructor)")
-        noisy = ops.add_noise_t(latents, noise, self.ac_dev, timesteps)      # coefficients looked up on the device: one launch
-        x_in = ops.nchw_to_nhwc(noisy)
-        tgt = ops.nchw_to_nhwc(noise, out_f32=True)
-        t_dev = timesteps.to(torch.float32)
+        if noise is None:
+            B = (latents if latents is not None else moments).shape[0]
+            x_in, tgt, timesteps, t_dev = ops.train_noise_fused(self.noise_state, self.ac_dev, moments=moments, latents=latents,
+                                                                scaling_factor=scaling_factor, noise_offset=self.noise_offset,
+                                                                ticket=self._noise_ticket, timesteps_out=self._timesteps_buf(B))
+        else:
+            noisy = ops.add_noise_t(latents, noise, self.ac_dev, timesteps)      # coefficients looked up on the device: one launch
+            x_in = ops.nchw_to_nhwc(noisy)
+            tgt = ops.nchw_to_nhwc(noise, out_f32=True)
+            t_dev = timesteps.to(torch.float32)
+        self.last_timesteps = timesteps
         cls = ops.f32_to_bf16(prompt_embeds)
         tape = Tape(self.tnb)
         pred = self.forward(tape, x_in, t_dev, cls)
@@ -721,25 +774,34 @@ class LoraTrainer:
         replayed from static input buffers -- the eager step is host-launch-bound."""
         self._ensure_fresh()
         f = self.flat
-        args = self._to_dev(latents, noise, timesteps, prompt_embeds)
+        run = self._fwd_bwd
+        if check_noise_args(self.noise_seed, self.noise_offset, (noise, timesteps)):
+            # drawn on the device: the graph's only staged inputs are the latents and the embeddings
+            args = (latents.to(self.dev, torch.float32).contiguous(), prompt_embeds.to(self.dev, torch.float32).contiguous())
+            run = lambda lat, emb: self._fwd_bwd(lat, None, None, emb)
+            self.last_timesteps = self._timesteps_buf(args[0].shape[0])     # (allocated outside any capture; a replay fills it)
+        else:
+            args = self._to_dev(latents, noise, timesteps, prompt_embeds)
         if not self.use_graph:
-            self._fwd_bwd(*args)
+            run(*args)
             return f.grads[f.n:]
-        if self.graph is not None and all(a.shape == b.shape for a, b in zip(args, self._static)):
+        if self.graph is not None and len(args) == len(self._static) and all(a.shape == b.shape for a, b in zip(args, self._static)):
             for dst, src in zip(self._static, args):
                 dst.copy_(src)
+            if len(args) == 4:
+                self.last_timesteps = self._static[2]
             self.tnb.restore(self._graph_tab)                  # the job table of THIS graph's addresses, if anything overwrote it
             self.graph.replay()
             return f.grads[f.n:]
         self._eager_steps += 1
         if self._eager_steps <= 2:
-            self._fwd_bwd(*args)
+            run(*args)
             return f.grads[f.n:]
         self._static = tuple(a.clone() for a in args)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):   # RCCL's watchdog thread must not void the capture
-            self._fwd_bwd(*self._static)
+            run(*self._static)
         self._graph_tab = self.tnb.snapshot()                    # job table of the captured addresses (H2D copies cannot be captured)
         self.tnb.restore(self._graph_tab)
         self.graph.replay()
@@ -751,9 +813,12 @@ class LoraTrainer:
             prompt_embeds = normalize(text_encoder(input_ids, attention_mask).text_embeds)
             noisy = add_noise(latents, noise, timesteps);  pred = unet(noisy, t, class_labels=prompt_embeds);  mse;  backward
         as ONE captured hipGraph per (batch shape, caption-length bucket), then the flat all-reduce and AdamW as in step().
-        sample_noise [B, 8, H/4, 16] is the N(0, 1) draw of latent_dist.sample() (passed in so that the graph has no RNG state)."""
+        sample_noise [B, 8, H/4, 16] is the N(0, 1) draw of latent_dist.sample() (passed in so that the graph has no RNG state).
+        noise = timesteps = sample_noise = None (a trainer with noise_seed): all three are drawn inside the graph from the trainer's
+        device-resident Philox state; the mel, the token ids and the lengths are then the graph's only staged inputs."""
         self._ensure_fresh()
         dev = self.dev
+        dev_noise = check_noise_args(self.noise_seed, self.noise_offset, (noise, timesteps, sample_noise))
         ids, mask = batch["input_ids"].squeeze(1), batch["attention_mask"].squeeze(1)
         lens = text_encoder._lengths(ids, mask)                  # host-side validation of the padding mask (CPU tensors)
         Le = min(ids.shape[1], (int(lens.max()) + 63) // 64 * 64)   # 64-token buckets: few distinct graphs
@@ -761,28 +826,39 @@ class LoraTrainer:
         # that means until the PREVIOUS step's graph has finished -- the host-side work of a step (~0.3 ms: slicing, six copies, the
         # replay call) then sits between two graphs instead of under the first.  The side stream is idle, so the host only waits for
         # the copies themselves; the step's stream picks the staged tensors up behind an event.
+        def stage():
+            a = (batch["log_mel_spec"].to(dev, torch.float32).contiguous(), ids[:, :Le].to(dev, torch.int64).contiguous(), lens.to(dev))
+            if dev_noise:
+                return a
+            return a + (sample_noise.to(dev, torch.float32).contiguous(), noise.to(dev, torch.float32).contiguous(),
+                        timesteps.to(dev, torch.int64).contiguous())
+
         if SIDE_STREAM_H2D:
             if getattr(self, "_h2d_stream", None) is None:
                 self._h2d_stream = torch.cuda.Stream(device=dev)
             main = torch.cuda.current_stream(dev)
             with torch.cuda.stream(self._h2d_stream):
-                args = (batch["log_mel_spec"].to(dev, torch.float32).contiguous(), ids[:, :Le].to(dev, torch.int64).contiguous(),
-                        lens.to(dev), sample_noise.to(dev, torch.float32).contiguous(), noise.to(dev, torch.float32).contiguous(),
-                        timesteps.to(dev, torch.int64).contiguous())
+                args = stage()
             main.wait_stream(self._h2d_stream)
             for a in args:
                 a.record_stream(main)
         else:
-            args = (batch["log_mel_spec"].to(dev, torch.float32).contiguous(), ids[:, :Le].to(dev, torch.int64).contiguous(),
-                    lens.to(dev), sample_noise.to(dev, torch.float32).contiguous(), noise.to(dev, torch.float32).contiguous(),
-                    timesteps.to(dev, torch.int64).contiguous())
+            args = stage()
         sf = float(vae.config.scaling_factor)
 
-        def body(mel, ids_d, kv_len, eps, nz, ts):
+        def body(mel, ids_d, kv_len, eps=None, nz=None, ts=None):
+            if eps is None:                                    # device noise: the moments go to the fused launch as the encoder leaves them
+                mom = vae.encode_nhwc(ops.nchw_to_nhwc(mel))
+                emb = torch.nn.functional.normalize(text_encoder.forward_device(ids_d, kv_len)[0], dim=-1)
+                self._fwd_bwd(None, None, None, emb, moments=mom, scaling_factor=sf)
+                return
             mom = ops.nhwc_to_nchw_f32(vae.encode_nhwc(ops.nchw_to_nhwc(mel)))
             lat = ops.gaussian_sample(mom, eps) * sf
             emb = torch.nn.functional.normalize(text_encoder.forward_device(ids_d, kv_len)[0], dim=-1)
             self._fwd_bwd(lat, nz, ts, emb)
+
+        if dev_noise:
+            self.last_timesteps = self._timesteps_buf(args[0].shape[0])     # (allocated outside any capture; a replay fills it)
 
         f = self.flat
         key = tuple(tuple(a.shape) for a in args)
@@ -811,6 +887,8 @@ class LoraTrainer:
                 g, static, tab = ent
                 for dst, src in zip(static, args):
                     dst.copy_(src)
+                if not dev_noise:
+                    self.last_timesteps = static[5]
                 self.tnb.restore(tab)
                 g.replay()
         return self._apply_update(f.grads[f.n:])
@@ -865,12 +943,17 @@ class LoraTrainer:
     # ---- checkpoint ----
     def state_dict(self):
         """What a resumed run needs besides the frozen base: the flat LoRA parameters, the AdamW moments, the optimiser-step count
-        and the micro-step counter (with the gradients of an unfinished accumulation window)."""
+        and the micro-step counter (with the gradients of an unfinished accumulation window); with device noise also the stream's
+        (seed, ordinal), so that the resumed run draws what the uninterrupted one would have (a checkpoint without it loads as before,
+        and the stream then stays where the constructor put it)."""
         f = self.flat
         sd = {"params": f.params.detach().cpu().clone(), "m": f.m.cpu().clone(), "v": f.v.cpu().clone(), "step": self.step_count,
               "micro_step": self.micro_step, "names": list(f.names)}
         if self.window_open:
             sd["accum"] = f.accum.cpu().clone()
+        if self.noise_state is not None:                         # the device noise stream: a resumed run continues it
+            seed, ordinal = ops.philox_state_values(self.noise_state)
+            sd["noise"] = {"seed": seed, "ordinal": ordinal, "rank": self.rank}
         return sd
 
     def load_state_dict(self, sd):
@@ -891,4 +974,11 @@ class LoraTrainer:
                                          f"{self.accum_steps} but the checkpoint holds no gradients for it (saved with another "
                                          "gradient_accumulation_steps?)")
             f.accum.copy_(sd["accum"].to(f.accum.device))
+        if self.noise_state is not None and sd.get("noise") is not None:
+            # the saving rank's position within its lane of the counter space, moved to this rank's lane (every rank has taken the
+            # same number of steps); written INTO the state tensor, which the captured graphs read
+            nz = sd["noise"]
+            ordinal = int(nz["ordinal"]) - noise_ordinal_base(nz.get("rank", 0)) + noise_ordinal_base(self.rank)
+            ops.philox_set(self.noise_state, seed=int(nz["seed"]), draw=ordinal)
+            self.noise_seed = int(nz["seed"])
         self.unet.invalidate_packed()                             # the adapter changed under the inference plan, as after a step

@@ -478,6 +478,20 @@ int aldm_add_noise_t(const float* x, const float* noise, const float* alphas_cum
 /* DiagonalGaussianDistribution.sample(): params fp32 NCHW [B][2C][HW] = (mean | logvar), noise / out fp32 [B][C][HW], chw = C*HW:
    out = mean + exp(0.5 clamp(logvar, -30, 20)) noise  -- `vae.encode(x).latent_dist.sample()` [REF train:495] */
 int aldm_gaussian_sample(const float* params, const float* noise, int B, long long chw, float* out, void* stream);
+/* The training step's batch noising as one launch, with the randomness drawn on the device from rng_state (4 words, see aldm_randn).
+   A call that finds the draw ordinal at d uses four draws and, with a ticket, leaves it at d + 4:
+     d      B raw words       t_b = umulhi(word_b, n_train)                         -> timesteps int64 [B], t_f32 fp32 [B]
+     d + 1  B*C*H*W normals   e: lat = (mean + exp(0.5 clamp(logvar, -30, 20)) e) scaling_factor   (element index = flat NCHW index)
+     d + 2  B*C*H*W normals   n (the same indexing)
+     d + 3  B*C normals       o: n' = n + noise_offset o[b][c]   (diffusers' noise offset; noise_offset == 0 switches it off)
+     x_in = bf16(sqrt(abar[t_b]) lat + sqrt(1 - abar[t_b]) n') ,  target = n'   both channels-last [B][H][W][C]
+   Element i of a draw is element i of aldm_philox_u32 / aldm_randn for the same state at that ordinal.  Exactly one source:
+   moments fp32 channels-last [B][H][W][2C] (mean | logvar, as the VAE encoder leaves them) or latents fp32 NCHW [B][C][H][W] (draw
+   d + 1 is then consumed unused; scaling_factor is ignored).  ticket: a zeroed device word; the last workgroup resets it and stores
+   the ordinal d + 4.  ticket == NULL leaves the state alone.  B*C*H*W < 2^31. */
+int aldm_train_noise_fused(unsigned* rng_state, const float* alphas_cumprod, int n_train, const float* moments, const float* latents,
+                           float scaling_factor, float noise_offset, int B, int C, int H, int W, void* x_in_bf16, float* target,
+                           long long* timesteps, float* t_f32, unsigned* ticket, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Backward kernels of the LoRA fine-tune step [REF script/train/train_audioldm_lora.py:499-565]: the base model
