@@ -181,25 +181,8 @@ PROTOTYPES = {
     "aldm_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_longlong, C.c_float, C.c_void_p, C.c_void_p]),
     "aldm_cfg_ddim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_float,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aldm_ddim_step_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aldm_dpm_step_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                      C.c_void_p]),
-    "aldm_ddim_step_fused_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "aldm_dpm_step_fused_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "aldm_philox_u32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_ulonglong, C.c_void_p]),
     "aldm_randn": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p]),
-    "aldm_euler_a_step_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                          C.c_void_p]),
-    "aldm_euler_a_step_fused_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "aldm_add_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "aldm_add_noise_t": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "aldm_gaussian_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
@@ -231,6 +214,16 @@ PROTOTYPES = {
     "aldm_patch_merge_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "aldm_token_mean": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+
+# The six fused scheduler steps share one argument frame (csrc/elementwise.hip launch_step_fused): eps, x, B, n_per_sample, cfg,
+# guidance, coef, step_idx, x_in | the solver's operand (DDIM: none, DPM: hist, Euler-ancestral: the Philox state) | table, row_elems,
+# rowbias, timesteps, n_steps, t_out, ticket | masked: x0, noise, mask, blend, channels | stream.
+_STEP_HEAD = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+_STEP_TAIL = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+_STEP_INPAINT = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+for _solver, _operand in (("ddim", []), ("dpm", [C.c_void_p]), ("euler_a", [C.c_void_p])):
+    PROTOTYPES[f"aldm_{_solver}_step_fused"] = (C.c_int, _STEP_HEAD + _operand + _STEP_TAIL + [C.c_void_p])
+    PROTOTYPES[f"aldm_{_solver}_step_fused_masked"] = (C.c_int, _STEP_HEAD + _operand + _STEP_TAIL + _STEP_INPAINT + [C.c_void_p])
 
 _lib = None
 

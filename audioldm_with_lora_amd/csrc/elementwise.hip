@@ -102,94 +102,6 @@ __device__ __forceinline__ float inpaint_blend(float xn, float x0, float nz, flo
   return fmaf(m, xn, (1.f - m) * known);
 }
 
-// The whole per-step bookkeeping of the replayed DDIM loop as ONE launch behind the UNet: classifier-free guidance + DDIM update
-// (as cfg_ddim_step_kernel), the NEXT step's row of the precomputed time-embedding table gathered into `rowbias`, and the
-// device-side step counter advanced.  Every workgroup reads the counter when it starts; the one that finishes LAST (an
-// agent-scope ticket) writes the new value, so no workgroup can see the counter move under it -- three launches become one.
-// VEC elements per thread (4 when B * n % 4 == 0): a quarter of the workgroups means a quarter of the same-address ticket atomics,
-// which were most of this launch's 8.4 us (500 workgroups at one thread per element).
-// The body is shared with ddim_step_fused_masked_kernel (MASKED = true: the inpainting blend after the update, see inpaint_blend);
-// this kernel instantiates MASKED = false and keeps its own parameter list and arithmetic: its results are what they were before the
-// blend (bench.py's dumped latents are bit-identical).  The disassembly is not identical: one scalar load and one wait are in a
-// different order, and the operands of one (commutative) multiply are swapped.
-template <int VEC, bool MASKED>
-__device__ __forceinline__ void ddim_step_fused_body(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg, float g,
-                                                     const float* __restrict__ coef, int* __restrict__ step_idx, bf16* __restrict__ x_in,
-                                                     const float* __restrict__ table, long long row_elems, float* __restrict__ rowbias,
-                                                     const float* __restrict__ timesteps, int n_steps, float* __restrict__ t_out,
-                                                     unsigned* __restrict__ ticket, long long tix, const Inpaint& ip) {
-  typedef float fvec __attribute__((ext_vector_type(VEC)));
-  typedef bf16 bvec __attribute__((ext_vector_type(VEC)));
-  const int cur = step_idx[0];
-  int nxt = cur + 1;
-  if (nxt >= n_steps) nxt = 0;                                // wrap: a replayed graph may run past the schedule (benchmarks)
-  const long long idx = tix * VEC;
-  const long long total = (long long)B * n;
-  if (idx < total) {
-    // (the operands do not depend on the counter: requested before the coefficient row, which does)
-    fvec eu = *reinterpret_cast<const fvec*>(eps + idx), et = eu;
-    if (cfg) et = *reinterpret_cast<const fvec*>(eps + total + idx);
-    const fvec xv = *reinterpret_cast<const fvec*>(x + idx);
-    fvec kx0, knz;
-    if constexpr (MASKED) {
-      kx0 = *reinterpret_cast<const fvec*>(ip.x0 + idx);
-      knz = *reinterpret_cast<const fvec*>(ip.noise + idx);
-    }
-    const float* cf = coef + 4 * cur;
-    const float sa = cf[0], sb = cf[1], sap = cf[2], sbp = cf[3];
-    fvec xn;
-    bvec xb;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      float r = ddim_update(eu[k], et[k], xv[k], cfg, g, sa, sb, sap, sbp);
-      if constexpr (MASKED)
-        r = inpaint_blend(r, kx0[k], knz[k], ip.mask[(unsigned)(idx + k) / (unsigned)ip.C], ip.blend[2 * cur], ip.blend[2 * cur + 1]);
-      xn[k] = r;
-      xb[k] = (bf16)r;
-    }
-    *reinterpret_cast<fvec*>(x + idx) = xn;
-    if (x_in) {
-      *reinterpret_cast<bvec*>(x_in + idx) = xb;
-      if (cfg) *reinterpret_cast<bvec*>(x_in + total + idx) = xb;
-    }
-  }
-  if (table && tix * 4 < row_elems)
-    *reinterpret_cast<f32x4*>(rowbias + tix * 4) = *reinterpret_cast<const f32x4*>(table + (long long)nxt * row_elems + tix * 4);
-  __syncthreads();                                            // every thread of this workgroup has read the counter
-  if (threadIdx.x == 0) {
-    // acq_rel at agent scope: the release half orders this workgroup's reads of step_idx[0] before its ticket, the acquire half orders
-    // the last workgroup's stores below after every other workgroup's ticket -- by the memory model, not by an incidental s_waitcnt
-    const unsigned done = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (done == gridDim.x - 1) {                              // last workgroup: nobody will read step_idx[0] again in this launch
-      ticket[0] = 0;
-      step_idx[0] = nxt;
-      t_out[0] = timesteps[nxt];
-    }
-  }
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void ddim_step_fused_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
-                                                              float g, const float* __restrict__ coef, int* __restrict__ step_idx,
-                                                              bf16* __restrict__ x_in, const float* __restrict__ table, long long row_elems,
-                                                              float* __restrict__ rowbias, const float* __restrict__ timesteps, int n_steps,
-                                                              float* __restrict__ t_out, unsigned* __restrict__ ticket) {
-  ddim_step_fused_body<VEC, false>(eps, x, B, n, cfg, g, coef, step_idx, x_in, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
-                                   (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{});
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void ddim_step_fused_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
-                                                                     int cfg, float g, const float* __restrict__ coef, int* __restrict__ step_idx,
-                                                                     bf16* __restrict__ x_in, const float* __restrict__ table, long long row_elems,
-                                                                     float* __restrict__ rowbias, const float* __restrict__ timesteps, int n_steps,
-                                                                     float* __restrict__ t_out, unsigned* __restrict__ ticket,
-                                                                     const float* __restrict__ x0, const float* __restrict__ noise,
-                                                                     const float* __restrict__ mask, const float* __restrict__ blend, int C) {
-  ddim_step_fused_body<VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
-                                  (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
-}
-
 // guidance + DPM-Solver(++) multistep update of one element from a coefficient row {alpha_s, sig_s, A, B, C, convert, reads_hist, -}
 // (scheduler.py DPMSolverMultistepScheduler.coefficient_table), every fused multiply-add spelled out as in ddim_update:
 //   m0 = convert ? (x - sig_s e) / alpha_s : e ;  x' = A x + B m0 + C (m0 - m1)      (m1 = hist; C == 0 and m1 unread on first-order rows)
@@ -202,26 +114,141 @@ __device__ __forceinline__ float dpm_update(float m0, float m1, float xv, float 
   return fmaf(A, xv, fmaf(Bc, m0, Cc * (m0 - m1)));
 }
 
-// The DPM-Solver multistep counterpart of ddim_step_fused_kernel: guidance, model-output conversion, the first- or second-order
-// update (history `hist` [B][n] fp32: the previous step's converted output, read only on rows that ask for it, then overwritten
-// with this step's), the bf16 next UNet input, the next step's time-embedding row and the counter advance, as ONE launch.  The
-// counter protocol (every workgroup reads step_idx[0] when it starts, the last one by the agent-scope ticket moves it) is
-// ddim_step_fused_kernel's unchanged.  ticket == NULL: the counter is left alone (eager scheduler.step; table is NULL there too).
-// The body is shared with dpm_step_fused_masked_kernel in the same way as the DDIM body.
-template <int VEC, bool MASKED>
-__device__ __forceinline__ void dpm_step_fused_body(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
-                                                             float g, const float* __restrict__ coef, int* __restrict__ step_idx,
-                                                             bf16* __restrict__ x_in, float* __restrict__ hist, const float* __restrict__ table,
-                                                             long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
-                                                             int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket, long long tix, const Inpaint& ip) {
-  typedef float fvec __attribute__((ext_vector_type(VEC)));
+// guidance + Euler-ancestral update of one element from a coefficient row {dt, sigma_up, in_scale_next, sigma_down}
+// (scheduler.py EulerAncestralDiscreteScheduler.coefficient_table; dt = sigma_down - sigma_from), every fused multiply-add spelled
+// out as in ddim_update:   x' = x + e dt + sigma_up z      (z ~ N(0, 1) from the Philox stream; sigma_up == 0 on the last row)
+__device__ __forceinline__ float euler_a_update(float eu, float et, float xv, int cfg, float g, float dt, float sigma_up, float z) {
+  const float e = cfg ? fmaf(g, et - eu, eu) : eu;
+  return fmaf(sigma_up, z, fmaf(e, dt, xv));
+}
+
+// ---- the fused scheduler step: one frame (step_fused_body), three solvers --------------------------------------------------------
+// What the frame asks of a scheduler.  ROW: the floats per row of its coefficient table.  TICKET_OPTIONAL: whether its entry points
+// take ticket == NULL (the eager scheduler.step: the counter is left alone, and table is NULL there too).  Its one extra kernel
+// operand, if any, as the first member (the kernels build the solver from it; every other member starts at zero).  And six hooks,
+// which every thread calls in this order:
+//   begin()             before the bounds test: the state that the last workgroup moves, read where the counter is read
+//   load<VEC>(cf, idx)  the coefficient row `cf` and whatever else the update of elements [idx, idx + VEC) reads
+//   update<VEC>(k, ..)  element k's new latent, through the solver's one-element function above
+//   unet_input(r)       the value whose bf16 rounding is the next UNet input
+//   store<VEC>(idx)     what is stored beside x
+//   advance()           what the last workgroup stores beside the counter
+template <int VEC>
+using fvec_t = float __attribute__((ext_vector_type(VEC)));
+
+struct DdimSolver {
+  static constexpr int ROW = 4;
+  static constexpr bool TICKET_OPTIONAL = false;
+  float sa, sb, sap, sbp;
+  __device__ __forceinline__ void begin() {}
+  template <int VEC>
+  __device__ __forceinline__ void load(const float* __restrict__ cf, long long) {
+    sa = cf[0], sb = cf[1], sap = cf[2], sbp = cf[3];
+  }
+  template <int VEC>
+  __device__ __forceinline__ float update(int, float eu, float et, float xv, int cfg, float g) {
+    return ddim_update(eu, et, xv, cfg, g, sa, sb, sap, sbp);
+  }
+  __device__ __forceinline__ float unet_input(float r) const { return r; }
+  template <int VEC> __device__ __forceinline__ void store(long long) {}
+  __device__ __forceinline__ void advance() {}
+};
+
+// history `hist` [B][n] fp32: the previous step's converted model output, read only on rows that ask for it (a first-order row, row 0
+// among them, never loads it), then overwritten with this step's -- the unblended m0, as diffusers stores the model output before the
+// caller blends
+struct DpmSolver {
+  static constexpr int ROW = 8;
+  static constexpr bool TICKET_OPTIONAL = true;
+  float* __restrict__ hist;
+  float alpha_s, sig_s, A, Bc, Cc;
+  bool convert, second;
+  f32x4 m0, m1;                                               // lanes [0, VEC)
+  __device__ __forceinline__ void begin() {}
+  template <int VEC>
+  __device__ __forceinline__ void load(const float* __restrict__ cf, long long idx) {
+    alpha_s = cf[0], sig_s = cf[1], A = cf[2], Bc = cf[3], Cc = cf[4];
+    convert = cf[5] != 0.f, second = cf[6] != 0.f;
+    if (second) {
+      const fvec_t<VEC> h = *reinterpret_cast<const fvec_t<VEC>*>(hist + idx);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) m1[k] = h[k];
+    }
+  }
+  template <int VEC>
+  __device__ __forceinline__ float update(int k, float eu, float et, float xv, int cfg, float g) {
+    m0[k] = dpm_model_output(eu, et, xv, cfg, g, alpha_s, sig_s, convert);
+    return dpm_update(m0[k], second ? m1[k] : m0[k], xv, A, Bc, Cc);
+  }
+  __device__ __forceinline__ float unet_input(float r) const { return r; }
+  template <int VEC>
+  __device__ __forceinline__ void store(long long idx) {
+    fvec_t<VEC> v;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) v[k] = m0[k];
+    *reinterpret_cast<fvec_t<VEC>*>(hist + idx) = v;
+  }
+  __device__ __forceinline__ void advance() {}
+};
+
+// the noise is generated HERE: element i of the [B][n] latents is element i of the current draw of the Philox state `rng` (philox.h:
+// no noise tensor in memory, and the same bits as aldm_randn for the same state).  VEC = 4 maps one thread to one Philox block; VEC = 1
+// evaluates the element's whole block and keeps its lane.  The latents stay in sigma space (unscaled); the UNet input is
+// x' * in_scale_next.  The counter advance moves the DRAW ORDINAL of the state as well, by the same last-workgroup ticket: every
+// workgroup reads state[2..3] when it starts, the last one stores ordinal + 1.
+struct EulerASolver {
+  static constexpr int ROW = 4;
+  static constexpr bool TICKET_OPTIONAL = true;
+  uint32_t* __restrict__ rng;
+  PhiloxState rs;
+  float dt, sigma_up, in_scale;
+  f32x4 z;                                                    // lanes [0, VEC): the normals of elements idx + k
+  __device__ __forceinline__ void begin() { rs = philox_load(rng); }
+  template <int VEC>
+  __device__ __forceinline__ void load(const float* __restrict__ cf, long long idx) {
+    dt = cf[0], sigma_up = cf[1], in_scale = cf[2];
+    z = philox_normal4(rs, (unsigned long long)(idx >> 2));
+    if constexpr (VEC == 1) {
+      const int lane = (int)(idx & 3);
+      z[0] = lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3];
+    }
+  }
+  template <int VEC>
+  __device__ __forceinline__ float update(int k, float eu, float et, float xv, int cfg, float g) {
+    return euler_a_update(eu, et, xv, cfg, g, dt, sigma_up, z[k]);
+  }
+  __device__ __forceinline__ float unet_input(float r) const { return r * in_scale; }
+  template <int VEC> __device__ __forceinline__ void store(long long) {}
+  __device__ __forceinline__ void advance() { philox_store_next(rng, rs); }
+};
+
+// The whole per-step bookkeeping of the replayed denoise loop as ONE launch behind the UNet: classifier-free guidance + the solver's
+// update (DDIM: as cfg_ddim_step_kernel), the inpainting blend after it (MASKED, see inpaint_blend), the bf16 input of the next UNet
+// call, the NEXT step's row of the precomputed time-embedding table gathered into `rowbias`, and the device-side step counter
+// advanced.  Every workgroup reads the counter when it starts; the one that finishes LAST (an agent-scope ticket) writes the new
+// value, so no workgroup can see the counter move under it -- three launches become one.
+// VEC elements per thread (4 when B * n % 4 == 0): a quarter of the workgroups means a quarter of the same-address ticket atomics,
+// which were most of this launch's 8.4 us (500 workgroups at one thread per element).
+// The six kernels below keep their own parameter lists (the first 64 bytes, preloaded into SGPRs, hold coef and step_idx, which the
+// first dependent load needs; the unmasked ones carry no inpainting operand) and instantiate this frame with their solver.  They form
+// the thread index `tix` themselves: read in here, blockDim.x is not folded to the uniform workgroup size, and every wave starts with
+// one more dependent load.
+template <class Solver, int VEC, bool MASKED>
+__device__ __forceinline__ void step_fused_body(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg, float g,
+                                                const float* __restrict__ coef, int* __restrict__ step_idx, bf16* __restrict__ x_in,
+                                                Solver s, const float* __restrict__ table, long long row_elems, float* __restrict__ rowbias,
+                                                const float* __restrict__ timesteps, int n_steps, float* __restrict__ t_out,
+                                                unsigned* __restrict__ ticket, long long tix, const Inpaint& ip) {
+  typedef fvec_t<VEC> fvec;
   typedef bf16 bvec __attribute__((ext_vector_type(VEC)));
   const int cur = step_idx[0];
   int nxt = cur + 1;
   if (nxt >= n_steps) nxt = 0;                                // wrap: a replayed graph may run past the schedule (benchmarks)
+  s.begin();
   const long long idx = tix * VEC;
   const long long total = (long long)B * n;
   if (idx < total) {
+    // (the operands do not depend on the counter: requested before the coefficient row, which does)
     fvec eu = *reinterpret_cast<const fvec*>(eps + idx), et = eu;
     if (cfg) et = *reinterpret_cast<const fvec*>(eps + total + idx);
     const fvec xv = *reinterpret_cast<const fvec*>(x + idx);
@@ -230,25 +257,19 @@ __device__ __forceinline__ void dpm_step_fused_body(const float* __restrict__ ep
       kx0 = *reinterpret_cast<const fvec*>(ip.x0 + idx);
       knz = *reinterpret_cast<const fvec*>(ip.noise + idx);
     }
-    const float* cf = coef + 8 * cur;
-    const float alpha_s = cf[0], sig_s = cf[1], A = cf[2], Bc = cf[3], Cc = cf[4];
-    const bool convert = cf[5] != 0.f, second = cf[6] != 0.f;
-    fvec m1 = (fvec)0.f;
-    if (second) m1 = *reinterpret_cast<const fvec*>(hist + idx);   // a first-order row (row 0 among them) never loads the history
-    fvec xn, m0;
+    s.template load<VEC>(coef + Solver::ROW * cur, idx);
+    fvec xn;
     bvec xb;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-      m0[k] = dpm_model_output(eu[k], et[k], xv[k], cfg, g, alpha_s, sig_s, convert);
-      float r = dpm_update(m0[k], second ? m1[k] : m0[k], xv[k], A, Bc, Cc);
-      // (the history keeps the unblended m0, as diffusers stores the model output before the caller blends)
+      float r = s.template update<VEC>(k, eu[k], et[k], xv[k], cfg, g);
       if constexpr (MASKED)
         r = inpaint_blend(r, kx0[k], knz[k], ip.mask[(unsigned)(idx + k) / (unsigned)ip.C], ip.blend[2 * cur], ip.blend[2 * cur + 1]);
       xn[k] = r;
-      xb[k] = (bf16)r;
+      xb[k] = (bf16)s.unet_input(r);
     }
     *reinterpret_cast<fvec*>(x + idx) = xn;
-    *reinterpret_cast<fvec*>(hist + idx) = m0;
+    s.template store<VEC>(idx);
     if (x_in) {
       *reinterpret_cast<bvec*>(x_in + idx) = xb;
       if (cfg) *reinterpret_cast<bvec*>(x_in + total + idx) = xb;
@@ -256,17 +277,43 @@ __device__ __forceinline__ void dpm_step_fused_body(const float* __restrict__ ep
   }
   if (table && tix * 4 < row_elems)
     *reinterpret_cast<f32x4*>(rowbias + tix * 4) = *reinterpret_cast<const f32x4*>(table + (long long)nxt * row_elems + tix * 4);
-  if (!ticket) return;                                        // (uniform over the grid)
-  __syncthreads();                                            // every thread of this workgroup has read the counter
+  if constexpr (Solver::TICKET_OPTIONAL)
+    if (!ticket) return;                                      // (uniform over the grid)
+  __syncthreads();                                            // every thread of this workgroup has read the counter and the solver's state
   if (threadIdx.x == 0) {
-    // acq_rel at agent scope, as in ddim_step_fused_kernel
+    // acq_rel at agent scope: the release half orders this workgroup's reads of step_idx[0] before its ticket, the acquire half orders
+    // the last workgroup's stores below after every other workgroup's ticket -- by the memory model, not by an incidental s_waitcnt
     const unsigned done = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (done == gridDim.x - 1) {
+    if (done == gridDim.x - 1) {                              // last workgroup: nobody will read step_idx[0] again in this launch
       ticket[0] = 0;
       step_idx[0] = nxt;
       t_out[0] = timesteps[nxt];
+      s.advance();
     }
   }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void ddim_step_fused_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
+                                                              float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                              bf16* __restrict__ x_in, const float* __restrict__ table, long long row_elems,
+                                                              float* __restrict__ rowbias, const float* __restrict__ timesteps, int n_steps,
+                                                              float* __restrict__ t_out, unsigned* __restrict__ ticket) {
+  step_fused_body<DdimSolver, VEC, false>(eps, x, B, n, cfg, g, coef, step_idx, x_in, DdimSolver{}, table, row_elems, rowbias, timesteps,
+                                          n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void ddim_step_fused_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                     int cfg, float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                                     bf16* __restrict__ x_in, const float* __restrict__ table, long long row_elems,
+                                                                     float* __restrict__ rowbias, const float* __restrict__ timesteps, int n_steps,
+                                                                     float* __restrict__ t_out, unsigned* __restrict__ ticket,
+                                                                     const float* __restrict__ x0, const float* __restrict__ noise,
+                                                                     const float* __restrict__ mask, const float* __restrict__ blend, int C) {
+  step_fused_body<DdimSolver, VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, DdimSolver{}, table, row_elems, rowbias, timesteps,
+                                         n_steps, t_out, ticket,
+                                         (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
 }
 
 template <int VEC>
@@ -275,8 +322,8 @@ __global__ __launch_bounds__(256) void dpm_step_fused_kernel(const float* __rest
                                                              bf16* __restrict__ x_in, float* __restrict__ hist, const float* __restrict__ table,
                                                              long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
                                                              int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket) {
-  dpm_step_fused_body<VEC, false>(eps, x, B, n, cfg, g, coef, step_idx, x_in, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
-                                  (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{});
+  step_fused_body<DpmSolver, VEC, false>(eps, x, B, n, cfg, g, coef, step_idx, x_in, DpmSolver{hist}, table, row_elems, rowbias, timesteps,
+                                         n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{});
 }
 
 template <int VEC>
@@ -288,88 +335,8 @@ __global__ __launch_bounds__(256) void dpm_step_fused_masked_kernel(const float*
                                                                     unsigned* __restrict__ ticket, const float* __restrict__ x0,
                                                                     const float* __restrict__ noise, const float* __restrict__ mask,
                                                                     const float* __restrict__ blend, int C) {
-  dpm_step_fused_body<VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
-                                 (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
-}
-
-// guidance + Euler-ancestral update of one element from a coefficient row {dt, sigma_up, in_scale_next, sigma_down}
-// (scheduler.py EulerAncestralDiscreteScheduler.coefficient_table; dt = sigma_down - sigma_from), every fused multiply-add spelled
-// out as in ddim_update:   x' = x + e dt + sigma_up z      (z ~ N(0, 1) from the Philox stream; sigma_up == 0 on the last row)
-__device__ __forceinline__ float euler_a_update(float eu, float et, float xv, int cfg, float g, float dt, float sigma_up, float z) {
-  const float e = cfg ? fmaf(g, et - eu, eu) : eu;
-  return fmaf(sigma_up, z, fmaf(e, dt, xv));
-}
-
-// The Euler-ancestral counterpart of ddim_step_fused_kernel: guidance, the update above with its noise generated HERE (element i of
-// the [B][n] latents is element i of the current draw of the Philox state, philox.h: no noise tensor in memory, and the same bits
-// as aldm_randn for the same state), the fp32 latents (sigma space: unscaled), the bf16 next UNet input x' * in_scale_next, the
-// next step's time-embedding row, and the counter advance -- which here moves the DRAW ORDINAL of the state as well, by the same
-// last-workgroup ticket: every workgroup reads state[2..3] when it starts, the last one stores ordinal + 1.  VEC = 4 maps one thread
-// to one Philox block; VEC = 1 evaluates the element's whole block and keeps its lane.  ticket == NULL: counter and ordinal stay.
-template <int VEC, bool MASKED>
-__device__ __forceinline__ void euler_a_step_fused_body(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
-                                                        float g, const float* __restrict__ coef, int* __restrict__ step_idx,
-                                                        bf16* __restrict__ x_in, uint32_t* __restrict__ rng, const float* __restrict__ table,
-                                                        long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
-                                                        int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket, long long tix,
-                                                        const Inpaint& ip) {
-  typedef float fvec __attribute__((ext_vector_type(VEC)));
-  typedef bf16 bvec __attribute__((ext_vector_type(VEC)));
-  const int cur = step_idx[0];
-  int nxt = cur + 1;
-  if (nxt >= n_steps) nxt = 0;                                // wrap: a replayed graph may run past the schedule (benchmarks)
-  const PhiloxState rs = philox_load(rng);
-  const long long idx = tix * VEC;
-  const long long total = (long long)B * n;
-  if (idx < total) {
-    fvec eu = *reinterpret_cast<const fvec*>(eps + idx), et = eu;
-    if (cfg) et = *reinterpret_cast<const fvec*>(eps + total + idx);
-    const fvec xv = *reinterpret_cast<const fvec*>(x + idx);
-    fvec kx0, knz;
-    if constexpr (MASKED) {
-      kx0 = *reinterpret_cast<const fvec*>(ip.x0 + idx);
-      knz = *reinterpret_cast<const fvec*>(ip.noise + idx);
-    }
-    const float* cf = coef + 4 * cur;
-    const float dt = cf[0], sigma_up = cf[1], in_scale = cf[2];
-    const f32x4 z4 = philox_normal4(rs, (unsigned long long)(idx >> 2));
-    fvec xn;
-    bvec xb;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      float z;
-      if constexpr (VEC == 4) {
-        z = z4[k];
-      } else {
-        const int lane = (int)(idx & 3);
-        z = lane == 0 ? z4[0] : lane == 1 ? z4[1] : lane == 2 ? z4[2] : z4[3];
-      }
-      float r = euler_a_update(eu[k], et[k], xv[k], cfg, g, dt, sigma_up, z);
-      if constexpr (MASKED)
-        r = inpaint_blend(r, kx0[k], knz[k], ip.mask[(unsigned)(idx + k) / (unsigned)ip.C], ip.blend[2 * cur], ip.blend[2 * cur + 1]);
-      xn[k] = r;
-      xb[k] = (bf16)(r * in_scale);
-    }
-    *reinterpret_cast<fvec*>(x + idx) = xn;
-    if (x_in) {
-      *reinterpret_cast<bvec*>(x_in + idx) = xb;
-      if (cfg) *reinterpret_cast<bvec*>(x_in + total + idx) = xb;
-    }
-  }
-  if (table && tix * 4 < row_elems)
-    *reinterpret_cast<f32x4*>(rowbias + tix * 4) = *reinterpret_cast<const f32x4*>(table + (long long)nxt * row_elems + tix * 4);
-  if (!ticket) return;                                        // (uniform over the grid)
-  __syncthreads();                                            // every thread of this workgroup has read the counter and the RNG state
-  if (threadIdx.x == 0) {
-    // acq_rel at agent scope, as in ddim_step_fused_kernel
-    const unsigned done = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (done == gridDim.x - 1) {
-      ticket[0] = 0;
-      step_idx[0] = nxt;
-      t_out[0] = timesteps[nxt];
-      philox_store_next(rng, rs);
-    }
-  }
+  step_fused_body<DpmSolver, VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, DpmSolver{hist}, table, row_elems, rowbias, timesteps,
+                                        n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
 }
 
 template <int VEC>
@@ -379,8 +346,8 @@ __global__ __launch_bounds__(256) void euler_a_step_fused_kernel(const float* __
                                                                  const float* __restrict__ table, long long row_elems, float* __restrict__ rowbias,
                                                                  const float* __restrict__ timesteps, int n_steps, float* __restrict__ t_out,
                                                                  unsigned* __restrict__ ticket) {
-  euler_a_step_fused_body<VEC, false>(eps, x, B, n, cfg, g, coef, step_idx, x_in, rng, table, row_elems, rowbias, timesteps, n_steps, t_out,
-                                      ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{});
+  step_fused_body<EulerASolver, VEC, false>(eps, x, B, n, cfg, g, coef, step_idx, x_in, EulerASolver{rng}, table, row_elems, rowbias,
+                                            timesteps, n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{});
 }
 
 template <int VEC>
@@ -393,8 +360,9 @@ __global__ __launch_bounds__(256) void euler_a_step_fused_masked_kernel(const fl
                                                                         unsigned* __restrict__ ticket, const float* __restrict__ x0,
                                                                         const float* __restrict__ noise, const float* __restrict__ mask,
                                                                         const float* __restrict__ blend, int C) {
-  euler_a_step_fused_body<VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, rng, table, row_elems, rowbias, timesteps, n_steps, t_out,
-                                     ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
+  step_fused_body<EulerASolver, VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, EulerASolver{rng}, table, row_elems, rowbias,
+                                           timesteps, n_steps, t_out, ticket,
+                                           (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
 }
 
 __global__ void advance_step_kernel(int* step_idx, const float* __restrict__ timesteps, int n_steps, float* t_out) {
@@ -659,7 +627,7 @@ __global__ __launch_bounds__(256) void train_noise_fused_kernel(uint32_t* __rest
   if (!ticket) return;                                        // (uniform over the grid)
   __syncthreads();                                            // every thread of this workgroup has read the RNG state
   if (threadIdx.x == 0) {
-    // acq_rel at agent scope, as in ddim_step_fused_kernel
+    // acq_rel at agent scope, as in step_fused_body
     const unsigned done = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     if (done == gridDim.x - 1) {
       ticket[0] = 0;
@@ -716,96 +684,72 @@ extern "C" int aldm_cfg_ddim_step(const float* eps, float* x, int B, long long n
   return aldm_launch_status("cfg_ddim_step");
 }
 
-extern "C" int aldm_ddim_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
-                                    int* step_idx, void* x_in_bf16, const float* table, long long row_elems, float* rowbias,
-                                    const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream) {
-  ALDM_CHECK_ARG(eps && x && coef && step_idx && timesteps && t_out && ticket && B > 0 && n_per_sample > 0 && n_steps > 0, "ddim_step_fused: bad args");
-  ALDM_CHECK_ARG(!table || (rowbias && row_elems > 0 && row_elems % 4 == 0), "ddim_step_fused: table needs rowbias and row_elems %% 4 == 0");
+// The host half of the fused step's frame (step_fused_body): the argument checks, one thread per VEC elements or per four floats of the
+// table row (whichever asks for more), and the VEC dispatch.  `k4` / `k1` are the entry's kernel at VEC = 4 and 1; `op` is the
+// solver's extra operand (none for DDIM), which the kernels take between x_in and table; the masked kernels end with the inpainting
+// operands (Inpaint above).  The mask is indexed by element / C in 32 bits, so B * n_per_sample must stay below 2^31 there.
+template <class Solver, bool MASKED, class Kernel, class... Op>
+static int launch_step_fused(const char* name, Kernel k4, Kernel k1, const float* eps, float* x, int B, long long n_per_sample, int cfg,
+                             float guidance, const float* coef, int* step_idx, void* x_in_bf16, const float* table, long long row_elems,
+                             float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const Inpaint& ip,
+                             void* stream, Op... op) {
+  ALDM_CHECK_ARG(eps && x && coef && step_idx && (... && op) && B > 0 && n_per_sample > 0 && n_steps > 0, "%s: bad args", name);
+  ALDM_CHECK_ARG(Solver::TICKET_OPTIONAL || ticket, "%s: bad args", name);
+  ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "%s: the counter advance needs timesteps and t_out", name);
+  ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
+                 "%s: table needs ticket, rowbias and row_elems %% 4 == 0", name);
+  if constexpr (MASKED)
+    ALDM_CHECK_ARG(ip.x0 && ip.noise && ip.mask && ip.blend && ip.C > 0 && n_per_sample % ip.C == 0 && (long long)B * n_per_sample < (1ll << 31),
+                   "%s: bad inpainting args", name);
+  if (!table) row_elems = 0;
   const long long total = (long long)B * n_per_sample;
   const bool v4 = total % 4 == 0;                       // (torch allocations are 16-byte aligned; CFG's second half starts at `total`)
   const long long items = v4 ? total / 4 : total;
   const long long work = items > row_elems / 4 ? items : row_elems / 4;
-  if (v4)
-    hipLaunchKernelGGL(ddim_step_fused_kernel<4>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample, cfg,
-                       guidance, coef, step_idx, (bf16*)x_in_bf16, table, table ? row_elems : 0, rowbias, timesteps, n_steps, t_out, ticket);
+  auto launch = [&](auto... inpaint) {
+    hipLaunchKernelGGL(v4 ? k4 : k1, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample, cfg, guidance,
+                       coef, step_idx, (bf16*)x_in_bf16, op..., table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, inpaint...);
+  };
+  if constexpr (MASKED)
+    launch(ip.x0, ip.noise, ip.mask, ip.blend, ip.C);
   else
-    hipLaunchKernelGGL(ddim_step_fused_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample, cfg,
-                       guidance, coef, step_idx, (bf16*)x_in_bf16, table, table ? row_elems : 0, rowbias, timesteps, n_steps, t_out, ticket);
-  return aldm_launch_status("ddim_step_fused");
+    launch();
+  return aldm_launch_status(name);
+}
+
+extern "C" int aldm_ddim_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                    int* step_idx, void* x_in_bf16, const float* table, long long row_elems, float* rowbias,
+                                    const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream) {
+  return launch_step_fused<DdimSolver, false>("ddim_step_fused", ddim_step_fused_kernel<4>, ddim_step_fused_kernel<1>, eps, x, B, n_per_sample,
+                                              cfg, guidance, coef, step_idx, x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out,
+                                              ticket, Inpaint{}, stream);
 }
 
 extern "C" int aldm_dpm_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
                                    int* step_idx, void* x_in_bf16, float* hist, const float* table, long long row_elems, float* rowbias,
                                    const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream) {
-  ALDM_CHECK_ARG(eps && x && coef && step_idx && hist && B > 0 && n_per_sample > 0 && n_steps > 0, "dpm_step_fused: bad args");
-  ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "dpm_step_fused: the counter advance needs timesteps and t_out");
-  ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
-                 "dpm_step_fused: table needs ticket, rowbias and row_elems %% 4 == 0");
-  if (!table) row_elems = 0;
-  const long long total = (long long)B * n_per_sample;
-  const bool v4 = total % 4 == 0;                       // (torch allocations are 16-byte aligned; CFG's second half starts at `total`)
-  const long long items = v4 ? total / 4 : total;
-  const long long work = items > row_elems / 4 ? items : row_elems / 4;
-  if (v4)
-    hipLaunchKernelGGL(dpm_step_fused_kernel<4>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample, cfg,
-                       guidance, coef, step_idx, (bf16*)x_in_bf16, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket);
-  else
-    hipLaunchKernelGGL(dpm_step_fused_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample, cfg,
-                       guidance, coef, step_idx, (bf16*)x_in_bf16, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket);
-  return aldm_launch_status("dpm_step_fused");
+  return launch_step_fused<DpmSolver, false>("dpm_step_fused", dpm_step_fused_kernel<4>, dpm_step_fused_kernel<1>, eps, x, B, n_per_sample,
+                                             cfg, guidance, coef, step_idx, x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out,
+                                             ticket, Inpaint{}, stream, hist);
 }
 
-// the masked launches: the same arguments as their unmasked counterparts, then the inpainting operands (Inpaint above).  The mask is
-// indexed by element / C in 32 bits, so B * n_per_sample must stay below 2^31.
+// the masked launches: the same arguments as their unmasked counterparts, then the inpainting operands
 extern "C" int aldm_ddim_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
                                            int* step_idx, void* x_in_bf16, const float* table, long long row_elems, float* rowbias,
                                            const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0,
                                            const float* noise, const float* mask, const float* blend, int channels, void* stream) {
-  ALDM_CHECK_ARG(eps && x && coef && step_idx && timesteps && t_out && ticket && B > 0 && n_per_sample > 0 && n_steps > 0,
-                 "ddim_step_fused_masked: bad args");
-  ALDM_CHECK_ARG(!table || (rowbias && row_elems > 0 && row_elems % 4 == 0), "ddim_step_fused_masked: table needs rowbias and row_elems %% 4 == 0");
-  ALDM_CHECK_ARG(x0 && noise && mask && blend && channels > 0 && n_per_sample % channels == 0 && (long long)B * n_per_sample < (1ll << 31),
-                 "ddim_step_fused_masked: bad inpainting args");
-  if (!table) row_elems = 0;
-  const long long total = (long long)B * n_per_sample;
-  const bool v4 = total % 4 == 0;
-  const long long items = v4 ? total / 4 : total;
-  const long long work = items > row_elems / 4 ? items : row_elems / 4;
-  if (v4)
-    hipLaunchKernelGGL(ddim_step_fused_masked_kernel<4>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
-                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
-                       x0, noise, mask, blend, channels);
-  else
-    hipLaunchKernelGGL(ddim_step_fused_masked_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
-                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
-                       x0, noise, mask, blend, channels);
-  return aldm_launch_status("ddim_step_fused_masked");
+  return launch_step_fused<DdimSolver, true>("ddim_step_fused_masked", ddim_step_fused_masked_kernel<4>, ddim_step_fused_masked_kernel<1>, eps,
+                                             x, B, n_per_sample, cfg, guidance, coef, step_idx, x_in_bf16, table, row_elems, rowbias, timesteps,
+                                             n_steps, t_out, ticket, Inpaint{x0, noise, mask, blend, channels}, stream);
 }
 
 extern "C" int aldm_dpm_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
                                           int* step_idx, void* x_in_bf16, float* hist, const float* table, long long row_elems, float* rowbias,
                                           const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0,
                                           const float* noise, const float* mask, const float* blend, int channels, void* stream) {
-  ALDM_CHECK_ARG(eps && x && coef && step_idx && hist && B > 0 && n_per_sample > 0 && n_steps > 0, "dpm_step_fused_masked: bad args");
-  ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "dpm_step_fused_masked: the counter advance needs timesteps and t_out");
-  ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
-                 "dpm_step_fused_masked: table needs ticket, rowbias and row_elems %% 4 == 0");
-  ALDM_CHECK_ARG(x0 && noise && mask && blend && channels > 0 && n_per_sample % channels == 0 && (long long)B * n_per_sample < (1ll << 31),
-                 "dpm_step_fused_masked: bad inpainting args");
-  if (!table) row_elems = 0;
-  const long long total = (long long)B * n_per_sample;
-  const bool v4 = total % 4 == 0;
-  const long long items = v4 ? total / 4 : total;
-  const long long work = items > row_elems / 4 ? items : row_elems / 4;
-  if (v4)
-    hipLaunchKernelGGL(dpm_step_fused_masked_kernel<4>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
-                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
-                       x0, noise, mask, blend, channels);
-  else
-    hipLaunchKernelGGL(dpm_step_fused_masked_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
-                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, hist, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
-                       x0, noise, mask, blend, channels);
-  return aldm_launch_status("dpm_step_fused_masked");
+  return launch_step_fused<DpmSolver, true>("dpm_step_fused_masked", dpm_step_fused_masked_kernel<4>, dpm_step_fused_masked_kernel<1>, eps, x,
+                                            B, n_per_sample, cfg, guidance, coef, step_idx, x_in_bf16, table, row_elems, rowbias, timesteps,
+                                            n_steps, t_out, ticket, Inpaint{x0, noise, mask, blend, channels}, stream, hist);
 }
 
 // the Euler-ancestral fused steps: aldm_dpm_step_fused's argument list with the Philox state {seed_lo, seed_hi, draw_lo, draw_hi} in the
@@ -813,22 +757,9 @@ extern "C" int aldm_dpm_step_fused_masked(const float* eps, float* x, int B, lon
 extern "C" int aldm_euler_a_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
                                        int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table, long long row_elems,
                                        float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream) {
-  ALDM_CHECK_ARG(eps && x && coef && step_idx && rng_state && B > 0 && n_per_sample > 0 && n_steps > 0, "euler_a_step_fused: bad args");
-  ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "euler_a_step_fused: the counter advance needs timesteps and t_out");
-  ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
-                 "euler_a_step_fused: table needs ticket, rowbias and row_elems %% 4 == 0");
-  if (!table) row_elems = 0;
-  const long long total = (long long)B * n_per_sample;
-  const bool v4 = total % 4 == 0;
-  const long long items = v4 ? total / 4 : total;
-  const long long work = items > row_elems / 4 ? items : row_elems / 4;
-  if (v4)
-    hipLaunchKernelGGL(euler_a_step_fused_kernel<4>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
-                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, rng_state, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket);
-  else
-    hipLaunchKernelGGL(euler_a_step_fused_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample,
-                       cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, rng_state, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket);
-  return aldm_launch_status("euler_a_step_fused");
+  return launch_step_fused<EulerASolver, false>("euler_a_step_fused", euler_a_step_fused_kernel<4>, euler_a_step_fused_kernel<1>, eps, x, B,
+                                                n_per_sample, cfg, guidance, coef, step_idx, x_in_bf16, table, row_elems, rowbias, timesteps,
+                                                n_steps, t_out, ticket, Inpaint{}, stream, rng_state);
 }
 
 extern "C" int aldm_euler_a_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
@@ -836,26 +767,10 @@ extern "C" int aldm_euler_a_step_fused_masked(const float* eps, float* x, int B,
                                               long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
                                               unsigned* ticket, const float* x0, const float* noise, const float* mask, const float* blend,
                                               int channels, void* stream) {
-  ALDM_CHECK_ARG(eps && x && coef && step_idx && rng_state && B > 0 && n_per_sample > 0 && n_steps > 0, "euler_a_step_fused_masked: bad args");
-  ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "euler_a_step_fused_masked: the counter advance needs timesteps and t_out");
-  ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
-                 "euler_a_step_fused_masked: table needs ticket, rowbias and row_elems %% 4 == 0");
-  ALDM_CHECK_ARG(x0 && noise && mask && blend && channels > 0 && n_per_sample % channels == 0 && (long long)B * n_per_sample < (1ll << 31),
-                 "euler_a_step_fused_masked: bad inpainting args");
-  if (!table) row_elems = 0;
-  const long long total = (long long)B * n_per_sample;
-  const bool v4 = total % 4 == 0;
-  const long long items = v4 ? total / 4 : total;
-  const long long work = items > row_elems / 4 ? items : row_elems / 4;
-  if (v4)
-    hipLaunchKernelGGL(euler_a_step_fused_masked_kernel<4>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B,
-                       n_per_sample, cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, rng_state, table, row_elems, rowbias, timesteps, n_steps,
-                       t_out, ticket, x0, noise, mask, blend, channels);
-  else
-    hipLaunchKernelGGL(euler_a_step_fused_masked_kernel<1>, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B,
-                       n_per_sample, cfg, guidance, coef, step_idx, (bf16*)x_in_bf16, rng_state, table, row_elems, rowbias, timesteps, n_steps,
-                       t_out, ticket, x0, noise, mask, blend, channels);
-  return aldm_launch_status("euler_a_step_fused_masked");
+  return launch_step_fused<EulerASolver, true>("euler_a_step_fused_masked", euler_a_step_fused_masked_kernel<4>,
+                                               euler_a_step_fused_masked_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef, step_idx,
+                                               x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                                               Inpaint{x0, noise, mask, blend, channels}, stream, rng_state);
 }
 
 extern "C" int aldm_add_noise(const float* x, const float* noise, const float* coef, int B, long long n_per_sample,

@@ -76,6 +76,10 @@ class DenoiseEngine:
             self.x0, self.noise = torch.zeros_like(self.x), torch.zeros_like(self.x)
             self.mask = torch.ones(batch, height, width, dtype=torch.float32, device=dev)
             self.blend = scheduler.blend_table(self.begin_index).contiguous().to(dev)
+        # the single-chain step's last launch (ops.{ddim,dpm,euler_a}_step_fused[_masked]) and what it takes beside the frame's operands
+        self._step = getattr(ops, ("euler_a" if self.euler else "dpm" if self.dpm else "ddim") + "_step_fused" + ("_masked" if self.masked else ""))
+        self._solver_args = (self.rng,) if self.euler else (self.hist,) if self.dpm else ()
+        self._inpaint_args = (self.x0, self.noise, self.mask, self.blend) if self.masked else ()
         self.t_buf = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)      # the fused step's last-workgroup ticket (rests at 0)
@@ -225,28 +229,8 @@ class DenoiseEngine:
         if self.chains == 1:
             # one chain: guidance + the scheduler's update, the next step's time-embedding row and the step counter in ONE launch behind the UNet
             eps = self.unet.forward_nhwc(self.x_in[0], self.t_buf, self.cls[0], rowbias=self.rowbias[0], gate=self._gate(0))
-            if self.masked:
-                ip = (self.x0, self.noise, self.mask, self.blend)
-                if self.euler:
-                    ops.euler_a_step_fused_masked(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.rng, self.temb[0],
-                                                  self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket, *ip)
-                elif self.dpm:
-                    ops.dpm_step_fused_masked(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.hist, self.temb[0],
-                                              self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket, *ip)
-                else:
-                    ops.ddim_step_fused_masked(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.temb[0],
-                                               self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket, *ip)
-                return
-            if self.euler:
-                ops.euler_a_step_fused(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.rng, self.temb[0],
-                                       self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket)
-                return
-            if self.dpm:
-                ops.dpm_step_fused(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.hist, self.temb[0],
-                                   self.rowbias[0], self.timesteps_f32, self.t_buf, self.ticket)
-                return
-            ops.ddim_step_fused(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], self.temb[0], self.rowbias[0],
-                                self.timesteps_f32, self.t_buf, self.ticket)
+            self._step(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], *self._solver_args, self.temb[0], self.rowbias[0],
+                       self.timesteps_f32, self.t_buf, self.ticket, *self._inpaint_args)
             return
         else:                                   # fork / join: under capture these become parallel graph branches
             cur = torch.cuda.current_stream()

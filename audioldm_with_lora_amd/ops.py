@@ -1224,38 +1224,6 @@ def cfg_ddim_step(eps, x, cfg, guidance, coef, step_idx, x_in):
                                                           _stream())), "aldm_cfg_ddim_step")
 
 
-def ddim_step_fused(eps, x, cfg, guidance, coef, step_idx, x_in, table, rowbias, timesteps_f32, t_out, ticket):
-    """cfg_ddim_step + gather_row(next step) + advance_step as one launch (aldm_ddim_step_fused)."""
-    B = x.shape[0]
-    n = x.numel() // B
-    row = table[0].numel() if table is not None else 0
-    assert ticket.dtype == torch.int32 and step_idx.dtype == torch.int32
-    check(_launch("ddim_step_fused", 6.0 * x.numel(), (4.0 * (2 if cfg else 1) + 8.0 + 2.0 * (2 if cfg else 1)) * x.numel() + 8.0 * row,
-                  lambda: _lib.load().aldm_ddim_step_fused(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in), _p(table),
-                                                           row, _p(rowbias), _p(timesteps_f32), timesteps_f32.numel(), _p(t_out), _p(ticket),
-                                                           _stream())), "aldm_ddim_step_fused")
-
-
-def dpm_step_fused(eps, x, cfg, guidance, coef, step_idx, x_in, hist, table=None, rowbias=None, timesteps_f32=None, t_out=None,
-                   ticket=None):
-    """CFG + DPM-Solver(++) multistep update (+ gather_row(next step) + advance_step when `ticket` is given) as one launch
-    (aldm_dpm_step_fused).  coef fp32 [n_steps, 8] (DPMSolverMultistepScheduler.coefficient_table); hist fp32, x's shape: the
-    previous step's converted model output, read by second-order rows and overwritten.  ticket None: eager, the counter stays."""
-    _require_gpu(x)
-    B = x.shape[0]
-    n = x.numel() // B
-    row = table[0].numel() if table is not None else 0
-    assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.shape[1] == 8 and step_idx.dtype == torch.int32
-    assert hist.dtype == torch.float32 and hist.numel() == x.numel() and eps.numel() == x.numel() * (2 if cfg else 1)
-    assert ticket is None or (ticket.dtype == torch.int32 and timesteps_f32 is not None and t_out is not None)
-    n_steps = timesteps_f32.numel() if timesteps_f32 is not None else coef.shape[0]
-    # bytes: eps (1 or 2 halves) + x read/write + hist read/write (upper bound: second-order rows) + bf16 UNet input (1 or 2 halves)
-    check(_launch("dpm_step_fused", 10.0 * x.numel(), (4.0 * (2 if cfg else 1) + 8.0 + 8.0 + 2.0 * (2 if cfg else 1)) * x.numel() + 8.0 * row,
-                  lambda: _lib.load().aldm_dpm_step_fused(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in), _p(hist),
-                                                          _p(table), row, _p(rowbias), _p(timesteps_f32), n_steps, _p(t_out), _p(ticket),
-                                                          _stream())), "aldm_dpm_step_fused")
-
-
 def _inpaint_args(x, x0, noise, mask, blend, n_steps):
     """checks the masked steps' extra operands; returns the channel count (x is channels-last [B, h, w, C])"""
     C = x.shape[-1]
@@ -1266,43 +1234,67 @@ def _inpaint_args(x, x0, noise, mask, blend, n_steps):
     return C
 
 
-def ddim_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, table, rowbias, timesteps_f32, t_out, ticket, x0, noise, mask, blend):
-    """ddim_step_fused followed by the inpainting blend (aldm_ddim_step_fused_masked): x' = (1 - m) (a x0 + s noise) + m x_ddim with
-    (a, s) = blend[step_idx].  x, x0, noise fp32 [B, h, w, C]; mask fp32 [B, h, w] (1 = regenerate); blend fp32 [n_steps, 2]."""
+# solver -> (columns of its coefficient table, flops per element, bytes per element beside the frame's, ticket may be None)
+#   dpm: hist read/write (upper bound: second-order rows); euler_a: ~100 flops for ten Philox rounds and a Box-Muller, no noise tensor
+_STEP_SOLVERS = {"ddim": (4, 6.0, 0.0, False), "dpm": (8, 10.0, 8.0, True), "euler_a": (4, 110.0, 0.0, True)}
+
+
+def _step_fused(solver, eps, x, cfg, guidance, coef, step_idx, x_in, operand, table, rowbias, timesteps_f32, t_out, ticket, inpaint=None):
+    """The frame the six fused scheduler steps share (csrc/elementwise.hip step_fused_body / launch_step_fused): the checks, the
+    flops / bytes model and the launch of aldm_<solver>_step_fused[_masked].  operand: the solver's extra tensors, () or a 1-tuple;
+    inpaint: None or (x0, noise, mask, blend)."""
+    coef_cols, flops, solver_bytes, ticket_optional = _STEP_SOLVERS[solver]
     _require_gpu(x)
     B = x.shape[0]
     n = x.numel() // B
+    halves = 2 if cfg else 1
     row = table[0].numel() if table is not None else 0
-    assert ticket.dtype == torch.int32 and step_idx.dtype == torch.int32
-    C = _inpaint_args(x, x0, noise, mask, blend, timesteps_f32.numel())
-    # bytes: the unmasked step's, plus x0 and noise (4 B each) and the mask (4 B per pixel)
-    check(_launch("ddim_step_fused_masked", 10.0 * x.numel(),
-                  (4.0 * (2 if cfg else 1) + 8.0 + 8.0 + 4.0 / C + 2.0 * (2 if cfg else 1)) * x.numel() + 8.0 * row,
-                  lambda: _lib.load().aldm_ddim_step_fused_masked(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in),
-                                                                  _p(table), row, _p(rowbias), _p(timesteps_f32), timesteps_f32.numel(), _p(t_out),
-                                                                  _p(ticket), _p(x0), _p(noise), _p(mask), _p(blend), C, _stream())),
-          "aldm_ddim_step_fused_masked")
+    assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.shape[1] == coef_cols and step_idx.dtype == torch.int32
+    assert eps.numel() == x.numel() * halves
+    assert (ticket_optional and ticket is None) or (ticket.dtype == torch.int32 and timesteps_f32 is not None and t_out is not None)
+    n_steps = timesteps_f32.numel() if timesteps_f32 is not None else coef.shape[0]
+    name = f"{solver}_step_fused"
+    # bytes per element: eps (1 or 2 halves) + x read/write + the solver's, + bf16 UNet input (1 or 2 halves) at the end
+    per_elem = 4.0 * halves + 8.0 + solver_bytes
+    tail = ()
+    if inpaint is not None:
+        C = _inpaint_args(x, *inpaint, n_steps)
+        name, flops = name + "_masked", flops + 4.0
+        per_elem = per_elem + 8.0 + 4.0 / C                  # x0 and noise (4 B each) and the mask (4 B per pixel)
+        tail = (*map(_p, inpaint), C)
+    fn = getattr(_lib.load(), "aldm_" + name)
+    check(_launch(name, flops * x.numel(), (per_elem + 2.0 * halves) * x.numel() + 8.0 * row,
+                  lambda: fn(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in), *map(_p, operand), _p(table), row,
+                             _p(rowbias), _p(timesteps_f32), n_steps, _p(t_out), _p(ticket), *tail, _stream())), "aldm_" + name)
+
+
+def ddim_step_fused(eps, x, cfg, guidance, coef, step_idx, x_in, table, rowbias, timesteps_f32, t_out, ticket):
+    """cfg_ddim_step + gather_row(next step) + advance_step as one launch (aldm_ddim_step_fused)."""
+    _step_fused("ddim", eps, x, cfg, guidance, coef, step_idx, x_in, (), table, rowbias, timesteps_f32, t_out, ticket)
+
+
+def dpm_step_fused(eps, x, cfg, guidance, coef, step_idx, x_in, hist, table=None, rowbias=None, timesteps_f32=None, t_out=None,
+                   ticket=None):
+    """CFG + DPM-Solver(++) multistep update (+ gather_row(next step) + advance_step when `ticket` is given) as one launch
+    (aldm_dpm_step_fused).  coef fp32 [n_steps, 8] (DPMSolverMultistepScheduler.coefficient_table); hist fp32, x's shape: the
+    previous step's converted model output, read by second-order rows and overwritten.  ticket None: eager, the counter stays."""
+    assert hist.dtype == torch.float32 and hist.numel() == x.numel()
+    _step_fused("dpm", eps, x, cfg, guidance, coef, step_idx, x_in, (hist,), table, rowbias, timesteps_f32, t_out, ticket)
+
+
+def ddim_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, table, rowbias, timesteps_f32, t_out, ticket, x0, noise, mask, blend):
+    """ddim_step_fused followed by the inpainting blend (aldm_ddim_step_fused_masked): x' = (1 - m) (a x0 + s noise) + m x_ddim with
+    (a, s) = blend[step_idx].  x, x0, noise fp32 [B, h, w, C]; mask fp32 [B, h, w] (1 = regenerate); blend fp32 [n_steps, 2]."""
+    _step_fused("ddim", eps, x, cfg, guidance, coef, step_idx, x_in, (), table, rowbias, timesteps_f32, t_out, ticket, (x0, noise, mask, blend))
 
 
 def dpm_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, hist, table, rowbias, timesteps_f32, t_out, ticket, x0, noise, mask,
                           blend):
     """dpm_step_fused followed by the inpainting blend (aldm_dpm_step_fused_masked); operands as ddim_step_fused_masked.  hist
     receives the unblended converted model output.  ticket None: eager, the counter stays (table must be None then)."""
-    _require_gpu(x)
-    B = x.shape[0]
-    n = x.numel() // B
-    row = table[0].numel() if table is not None else 0
-    assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.shape[1] == 8 and step_idx.dtype == torch.int32
-    assert hist.dtype == torch.float32 and hist.numel() == x.numel() and eps.numel() == x.numel() * (2 if cfg else 1)
-    assert ticket is None or (ticket.dtype == torch.int32 and timesteps_f32 is not None and t_out is not None)
-    n_steps = timesteps_f32.numel() if timesteps_f32 is not None else coef.shape[0]
-    C = _inpaint_args(x, x0, noise, mask, blend, n_steps)
-    check(_launch("dpm_step_fused_masked", 14.0 * x.numel(),
-                  (4.0 * (2 if cfg else 1) + 16.0 + 8.0 + 4.0 / C + 2.0 * (2 if cfg else 1)) * x.numel() + 8.0 * row,
-                  lambda: _lib.load().aldm_dpm_step_fused_masked(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in),
-                                                                 _p(hist), _p(table), row, _p(rowbias), _p(timesteps_f32), n_steps, _p(t_out),
-                                                                 _p(ticket), _p(x0), _p(noise), _p(mask), _p(blend), C, _stream())),
-          "aldm_dpm_step_fused_masked")
+    assert hist.dtype == torch.float32 and hist.numel() == x.numel()
+    _step_fused("dpm", eps, x, cfg, guidance, coef, step_idx, x_in, (hist,), table, rowbias, timesteps_f32, t_out, ticket,
+                (x0, noise, mask, blend))
 
 
 # ---- on-device RNG (csrc/rng.hip, csrc/philox.h) -----------------------------------------------------------------------------
@@ -1367,42 +1359,17 @@ def euler_a_step_fused(eps, x, cfg, guidance, coef, step_idx, x_in, rng_state, t
     draw ordinal's advance when `ticket` is given) as one launch (aldm_euler_a_step_fused).  coef fp32 [n_steps, 4]
     (EulerAncestralDiscreteScheduler.coefficient_table); x fp32, unscaled (sigma space); x_in receives bf16(x' * in_scale_next).
     ticket None: the counter and the ordinal stay."""
-    _require_gpu(x)
     _check_state(rng_state)
-    B = x.shape[0]
-    n = x.numel() // B
-    row = table[0].numel() if table is not None else 0
-    assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.shape[1] == 4 and step_idx.dtype == torch.int32
-    assert eps.numel() == x.numel() * (2 if cfg else 1)
-    assert ticket is None or (ticket.dtype == torch.int32 and timesteps_f32 is not None and t_out is not None)
-    n_steps = timesteps_f32.numel() if timesteps_f32 is not None else coef.shape[0]
-    # flops: guidance + update + ~100 for ten Philox rounds and a Box-Muller per element; bytes: the DDIM step's (no noise tensor)
-    check(_launch("euler_a_step_fused", 110.0 * x.numel(), (4.0 * (2 if cfg else 1) + 8.0 + 2.0 * (2 if cfg else 1)) * x.numel() + 8.0 * row,
-                  lambda: _lib.load().aldm_euler_a_step_fused(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in),
-                                                              _p(rng_state), _p(table), row, _p(rowbias), _p(timesteps_f32), n_steps,
-                                                              _p(t_out), _p(ticket), _stream())), "aldm_euler_a_step_fused")
+    _step_fused("euler_a", eps, x, cfg, guidance, coef, step_idx, x_in, (rng_state,), table, rowbias, timesteps_f32, t_out, ticket)
 
 
 def euler_a_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, rng_state, table, rowbias, timesteps_f32, t_out, ticket, x0, noise,
                               mask, blend):
     """euler_a_step_fused followed by the inpainting blend (aldm_euler_a_step_fused_masked); operands as ddim_step_fused_masked, blend
     rows (1, sigma_next).  ticket None: the counter and the ordinal stay (table must be None then)."""
-    _require_gpu(x)
     _check_state(rng_state)
-    B = x.shape[0]
-    n = x.numel() // B
-    row = table[0].numel() if table is not None else 0
-    assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.shape[1] == 4 and step_idx.dtype == torch.int32
-    assert eps.numel() == x.numel() * (2 if cfg else 1)
-    assert ticket is None or (ticket.dtype == torch.int32 and timesteps_f32 is not None and t_out is not None)
-    n_steps = timesteps_f32.numel() if timesteps_f32 is not None else coef.shape[0]
-    C = _inpaint_args(x, x0, noise, mask, blend, n_steps)
-    check(_launch("euler_a_step_fused_masked", 114.0 * x.numel(),
-                  (4.0 * (2 if cfg else 1) + 8.0 + 8.0 + 4.0 / C + 2.0 * (2 if cfg else 1)) * x.numel() + 8.0 * row,
-                  lambda: _lib.load().aldm_euler_a_step_fused_masked(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx),
-                                                                     _p(x_in), _p(rng_state), _p(table), row, _p(rowbias), _p(timesteps_f32),
-                                                                     n_steps, _p(t_out), _p(ticket), _p(x0), _p(noise), _p(mask), _p(blend),
-                                                                     C, _stream())), "aldm_euler_a_step_fused_masked")
+    _step_fused("euler_a", eps, x, cfg, guidance, coef, step_idx, x_in, (rng_state,), table, rowbias, timesteps_f32, t_out, ticket,
+                (x0, noise, mask, blend))
 
 
 def add_noise(x, noise, coef):
