@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("ALDM_LIB") or os.path.join(_HERE, "libaldm_hip.so")  
 ACT_NONE, ACT_SILU, ACT_LRELU, ACT_TANH, ACT_GELU = 0, 1, 2, 3, 4
 OUT_BF16, OUT_F32 = 0, 1
 TILE_AUTO, TILE_128x128, TILE_64x64, TILE_128x64, TILE_64x128 = 0, 1, 2, 3, 4
+EPI_AUTO, EPI_LDS, EPI_DIRECT = 0, 0x10, 0x20                    # aldm_igemm_t.xcd_map bits 4-5: form of the standard epilogue
 DEFER_ROWMAJOR, DEFER_PLANAR, DEFER_WRITE_THROUGH = 1, 2, 4     # aldm_igemm_t.defer_reduce flags
 SLAB_ROWMAJOR, SLAB_PLANAR = 0, 1                               # slab layout as aldm_groupnorm_partials_layout is told it
 
@@ -90,6 +91,7 @@ PROTOTYPES = {
     "aldm_igemm": (C.c_int, [C.POINTER(IgemmArgs), C.c_void_p]),
     "aldm_igemm_workspace_bytes": (C.c_size_t, [C.POINTER(IgemmArgs)]),
     "aldm_igemm_effective_splits": (C.c_int, [C.POINTER(IgemmArgs)]),
+    "aldm_igemm_epilogue_form": (C.c_int, [C.POINTER(IgemmArgs)]),
     "aldm_pgemm_supported": (C.c_int, [C.c_int]),
     "aldm_pgemm_plan": (C.c_int, [C.POINTER(PgemmArgs)]),
     "aldm_pgemm": (C.c_int, [C.POINTER(PgemmArgs), C.c_void_p]),

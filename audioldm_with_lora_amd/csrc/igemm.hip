@@ -53,6 +53,35 @@ static void plan_splits(int want, int nkt, int nch, int taps, bool halo, int& sp
   }
 }
 
+// Launches that leave through the register-direct epilogue (igemm_epilogue_direct): the plain bf16 standard path -- what the LEAN non-V^T
+// instantiations of the LDS-DMA kernels serve -- without a second residual, second output or LayerNorm hand-over, whole quads everywhere
+// (8-byte loads / stores), with a row bias at most one image boundary per M-tile, and a tile whose instantiation has the form compiled
+// in (the DIRECT argument of igemm_epilogue: fewer than 16 accumulator blocks a lane, no LoRA side channel).
+// The kernels check none of this.
+static bool epilogue_direct(const aldm_igemm_t* p, int tile, int splits) {
+  //                            tile:  -  128x128 64x64 128x64 64x128 32x64 128x128w8 h128 h64 256x128w8 64x128w8 128x64w8 256x128ws 64x128ws 128x64ws h128ws h64ws
+  static const int bm_of[17]     = {0, 128,    64,   128,   64,    0,    128,      0,   0,  256,      64,      128,     256,      64,      128,     0,     0};
+  static const int blocks_of[17] = {0, 16,     4,    8,     8,     0,    8,        8,   4,  16,       4,       4,       16,       8,       8,       8,     4};
+  if (tile < 1 || tile > 16 || blocks_of[tile] == 0) return false;
+  const bool fast = p->in_act == ALDM_ACT_NONE && p->Cin % 64 == 0 && p->Cin2 % 64 == 0 && 2ull * p->B * p->IH * p->IW * p->Cin < 0x80000000ull &&
+                    2ull * p->B * p->IH * p->IW * p->Cin2 < 0x80000000ull;
+  return fast && splits <= 1 && !p->vt && !p->geglu && !p->ln_s && p->out_act == ALDM_ACT_NONE && p->post_act == ALDM_ACT_NONE && !p->out2 &&
+         p->out_dtype == ALDM_OUT_BF16 && !p->res2 && !p->rowstat_out && p->Cout % 8 == 0 && p->out_ld % 4 == 0 && p->out_batch_stride % 4 == 0 &&
+         (!p->rowbias || (p->rowbias_ld % 4 == 0 && p->OH * p->OW >= bm_of[tile])) &&
+         blocks_of[tile] < 16 && p->Rp == 0;
+}
+
+// 1: aldm_igemm would run this launch with the register-direct epilogue, 0: with the LDS walk (tests, tools)
+extern "C" int aldm_igemm_epilogue_form(const aldm_igemm_t* p) {
+  if (!p || (p->xcd_map & ALDM_EPI_MASK) == ALDM_EPI_LDS) return 0;
+  const int tile = p->tile ? p->tile : pick_tile(p->B * p->OH * p->OW, p->Cout);
+  const int Ctot = p->Cin + p->Cin2;
+  const int nkt = cdiv(p->KH * p->KW * Ctot, BK) + (p->x3 ? (p->Cin3 + (p->x4 ? p->Cin4 : 0)) / BK : 0);
+  int splits, per;
+  plan_splits(p->splits, nkt, Ctot / BK, p->KH * p->KW, is_halo_tile(tile), splits, per);
+  return epilogue_direct(p, tile, splits) ? 1 : 0;
+}
+
 extern "C" int aldm_igemm_effective_splits(const aldm_igemm_t* p) {
   if (!p || p->splits <= 1) return 1;
   const int nkt = cdiv(p->KH * p->KW * (p->Cin + p->Cin2), BK) + (p->x3 ? (p->Cin3 + (p->x4 ? p->Cin4 : 0)) / BK : 0);
@@ -147,9 +176,21 @@ extern "C" int aldm_igemm(const aldm_igemm_t* p, void* stream) {
   // slab layout / store policy of a deferred reduce (the in-library reduce reads row-major slabs: flags only with defer_reduce)
   d.ws_mode = (d.splits > 1 && p->defer_reduce) ? (p->defer_reduce >> 1) & 3 : 0;
   if ((long long)p->B * p->OH * p->OW * p->Cout * 4 >= 0x80000000ll) d.ws_mode &= ~2;   // write-through stores take 32-bit byte offsets into a slab
+  {
+    // epilogue form (aldm_igemm_t.xcd_map bits 4-5, epilogue_direct above): the register-direct store where the launch can take it
+    const int form = p->xcd_map & ALDM_EPI_MASK;
+    ALDM_CHECK_ARG(form == ALDM_EPI_AUTO || form == ALDM_EPI_LDS || form == ALDM_EPI_DIRECT, "igemm: bad epilogue form in xcd_map");
+    const bool direct = epilogue_direct(p, tile, d.splits);
+    if (form == ALDM_EPI_DIRECT && !direct) {
+      aldm_set_error("igemm: ALDM_EPI_DIRECT asked for a launch the register-direct epilogue cannot take (aldm_igemm_epilogue_form)");
+      return ALDM_E_UNSUPPORTED;
+    }
+    if (form != ALDM_EPI_LDS && direct) d.ws_mode |= 4;
+  }
   d.lora_gate = p->lora_gate; d.fd_gate = make_fastdiv((unsigned)(p->lora_gate ? p->gate_rows : 1)); d.gate_m1 = d.M - 1;
   d.tiles_n = 0; d.tiles_m = 0; d.nwg = 0;
-  ALDM_CHECK_ARG(p->xcd_map >= 0 && p->xcd_map <= 2, "igemm: xcd_map must be 0 (auto), 1 (activation-stationary) or 2 (weight-stationary)");
+  const int xcd_map = p->xcd_map & ~ALDM_EPI_MASK;
+  ALDM_CHECK_ARG(xcd_map >= 0 && xcd_map <= 2, "igemm: xcd_map must be 0 (auto), 1 (activation-stationary) or 2 (weight-stationary)");
   {
     // which operand an XCD's L2 keeps (igemm_work_item).  Measured (round 4, profiles/r04_fetch_xcd_*.json + r04_step_table_xcd_*.txt):
     // weight-stationary more than halves the fabric fetches of the 252- / 64-token levels' launches (21.6 -> 9.8 MiB per launch on the
@@ -159,7 +200,7 @@ extern "C" int aldm_igemm(const aldm_igemm_t* p, void* stream) {
     // only for an unsplit launch whose weight matrix is the larger operand.
     const unsigned long long act = 2ull * p->B * p->IH * p->IW * Ctot + 2ull * p->B * p->OH * p->OW * Cext;
     const unsigned long long wgt = 2ull * p->Cout * p->Kpad;
-    d.xmap = p->xcd_map ? p->xcd_map - 1 : ((wgt > act && p->splits <= 1) ? 1 : 0);
+    d.xmap = xcd_map ? xcd_map - 1 : ((wgt > act && p->splits <= 1) ? 1 : 0);
   }
   {
     const unsigned long long xb = 2ull * p->B * p->IH * p->IW * p->Cin, x2b = 2ull * p->B * p->IH * p->IW * p->Cin2;

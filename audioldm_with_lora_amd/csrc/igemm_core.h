@@ -77,8 +77,9 @@ struct IgemmDev {
   const float* lora_gate;     // multi-adapter routing: fp32 [M / gate_rows][RP] per-sample gates of the T columns; null = ungated
   FastDiv fd_gate;            // / gate_rows (rows of the GEMM per sample)
   int gate_m1;                // M - 1 of the launch: rows past the end (never stored) read the last sample's gates
-  // (split-K epilogue only)
-  int ws_mode;                // bit 0: quad-planar slabs (igemm_slab_index) for a deferred reduce; bit 1: write-through slab stores
+  // (epilogue only)
+  int ws_mode;                // split-K: bit 0: quad-planar slabs (igemm_slab_index) for a deferred reduce; bit 1: write-through slab stores
+                              // unsplit: bit 2: register-direct standard epilogue (igemm_epilogue_direct; LEAN non-V^T instantiations read it)
 };
 
 // ---- split-K slab layouts ----------------------------------------------------------------------------------------
@@ -224,6 +225,7 @@ __device__ __forceinline__ void add_bias4(const IgemmDev& p, int m, int n, float
 }
 
 // ---- shared epilogue ---------------------------------------------------------------------------------------------
+// (The plain unsplit launches leave through igemm_epilogue_direct below instead: DESIGN.md 5.8.)
 // The accumulators go through LDS (the K-loop buffers are free by then): every wave drops its 16x16 tiles into one
 // fp32 [BM][BN+4] image (or its transpose for V^T tiles), then the whole workgroup walks that image in 8-column groups.
 // One compact copy of the bias / GEGLU / activation / residual / store code serves all tiles (the fully unrolled
@@ -301,11 +303,131 @@ struct EpiCfg {
   static constexpr int BYTES = (BM * LD > BN * LDT ? BM * LD : BN * LDT) * 4;
 };
 
+// ---- register-direct standard epilogue (ws_mode bit 2) -------------------------------------------------------------
+// With the swapped MFMA a lane (lrow = pixel row, lq = quad) already holds 4 consecutive output channels of one pixel, so the plain
+// launches -- LEAN instantiations, bf16 output, no out2 / res2 / row statistics, N % 8 == 0, quad-aligned strides: epilogue_direct() in igemm.hip on the
+// host -- store straight from the accumulators: no fp32 [BM][BN + 4] LDS image, no barrier.  Per element the SAME operations in the
+// SAME order as the LDS walk (v + (bias + rowbias), + res, * alpha), so `out` is bit-identical; only the summation order of the
+// GroupNorm hand-over differs (fixed: 4 channels of a row, the lane's MI rows, the 16 lrow lanes by DPP, the WM waves in order).
+// A row's time-embedding bias is its image's: a lane keeps the vectors of its first and of its last row's image (host-checked
+// OH * OW >= BM: a tile crosses at most one image boundary) already summed with the bias, and selects per row.
+// A few hundred instructions per instantiation: no activation code, row address once per i, no bound beyond m < M and n < N.
+__device__ __forceinline__ float igemm_row16_sum(float v) {
+  // sum over the 16 lanes of a DPP row (same lq), every lane gets the total: xor 1, xor 2, half-row mirror, row mirror
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
+  return v;
+}
+
+template <int BM, int BN, int MI, int NI, bool QS>
+__device__ __forceinline__ void igemm_epilogue_direct(const IgemmDev& p, f32x4 (&acc)[MI][NI], char* smem, int m0, int n0, int wm_off,
+                                                      int wn_off, int lrow, int lq, int tid) {
+  const int nb = n0 + wn_off + lq * 4;
+  long long rowo[MI];
+  bool ok[MI];
+  int img[MI];
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int m = m0 + wm_off + i * 16 + lrow;
+    ok[i] = m < p.M;
+    const int mm = min(m, p.M - 1);                          // rows past the end: a valid address, never stored
+    const int b = fdiv(mm, p.fd_ohw);
+    const int pix = mm - b * p.OHW;
+    img[i] = b;
+    rowo[i] = (long long)b * p.out_bs + (long long)(pix * p.out_ps + p.out_po) * p.out_ld;
+  }
+  // column vectors, once per j: bias + row bias of the first / last row's image
+  f32x4 cA[NI], cB[NI];
+#pragma unroll
+  for (int j = 0; j < NI; ++j) {
+    const int n = nb + j * 16;
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f}, ra = bv, rb = bv;
+    if (n < p.N) {
+      if (p.bias) bv = *reinterpret_cast<const f32x4*>(p.bias + n);
+      if (p.rowbias) {
+        ra = *reinterpret_cast<const f32x4*>(p.rowbias + (long long)img[0] * p.rowbias_ld + n);
+        rb = *reinterpret_cast<const f32x4*>(p.rowbias + (long long)img[MI - 1] * p.rowbias_ld + n);
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { cA[j][e] = bv[e] + ra[e]; cB[j][e] = bv[e] + rb[e]; }
+  }
+  // every residual read before the arithmetic: one memory round trip for the tile
+  bf16x4 r1[MI][NI];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      r1[i][j] = bf16x4{0, 0, 0, 0};
+      if (p.res && nb + j * 16 < p.N) r1[i][j] = *reinterpret_cast<const bf16x4*>(p.res + rowo[i] + nb + j * 16);
+    }
+  const int qb0 = (QS && p.qstat) ? fdiv(min(m0, p.M - 1), p.fd_ohw) : 0;
+  float qa[NI][4];                                           // per quad column: slot 0 (sum, sum of squares), slot 1 (sum, sum of squares)
+#pragma unroll
+  for (int j = 0; j < NI; ++j) qa[j][0] = qa[j][1] = qa[j][2] = qa[j][3] = 0.f;
+  bf16* const outp = reinterpret_cast<bf16*>(p.out);
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const bool first = img[i] == img[0];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      const int n = nb + j * 16;
+      float v[4];
+      bf16x4 t;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[e] = acc[i][j][e];
+        v[e] += first ? cA[j][e] : cB[j][e];
+        v[e] = (v[e] + (float)r1[i][j][e]) * p.alpha + 0.f;   // (+ 0: the LDS walk's absent second residual, so that -0 rounds the same)
+        t[e] = (bf16)v[e];
+      }
+      if (ok[i] && n < p.N) *reinterpret_cast<bf16x4*>(outp + rowo[i] + n) = t;
+      if (QS && p.qstat) {
+        float s1 = 0.f, s2 = 0.f;                            // of the values AS STORED
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const float f = (float)t[e]; s1 += f; s2 = fmaf(f, f, s2); }
+        if (!ok[i]) s1 = s2 = 0.f;
+        const bool sl = img[i] != qb0;
+        qa[j][0] += sl ? 0.f : s1; qa[j][1] += sl ? 0.f : s2;
+        qa[j][2] += sl ? s1 : 0.f; qa[j][3] += sl ? s2 : 0.f;
+      }
+    }
+  }
+  if (QS && p.qstat) {
+    // GroupNorm hand-over: the 16 pixel rows of a quad column by DPP, then the WM waves that share the column range through a small
+    // LDS table at the start of the K loop's LDS and one barrier.  That LDS must be free on entry: the halo and loader-wave kernels pass
+    // a barrier after their last fragment read; igemm_pipe_kernel does so after its main loop, but NOT after the LoRA tail's extra
+    // K-step (which reads stage 0) -- the statistics instantiations (EPI 4) are RP == 0 only (static_assert at the call).  Host-checked
+    // N % BN == 0, so every thread is here.  Table layout as the LDS walk's:  qstat[(tile * 2 + slot) * (N / 4) + quad][2]
+    constexpr int WMW = BM / (MI * 16), QN = BN / 4;
+    float* red = reinterpret_cast<float*>(smem);             // [WMW][QN][4]
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) qa[j][e] = igemm_row16_sum(qa[j][e]);
+      if (lrow == 0)
+        *reinterpret_cast<f32x4*>(red + ((wm_off / (MI * 16)) * QN + ((wn_off + j * 16) >> 2) + lq) * 4) = f32x4{qa[j][0], qa[j][1], qa[j][2], qa[j][3]};
+    }
+    __syncthreads();
+    if (tid < QN * 4) {
+      float v = 0.f;
+#pragma unroll
+      for (int w = 0; w < WMW; ++w) v += red[w * QN * 4 + tid];
+      const int tile = p.qtile >= 0 ? p.qtile : m0 / BM;
+      const int quad = (n0 >> 2) + (tid >> 2), se = tid & 3;  // se: slot * 2 + (sum | sum of squares)
+      p.qstat[(((long long)tile * 2 + (se >> 1)) * (p.N >> 2) + quad) * 2 + (se & 1)] = v;
+    }
+  }
+}
+
 // LEAN = true: the launch is known (host-checked) to take the standard path without an activation -- no V^T tile, no split-K,
 // no GEGLU -- and every other path is compiled out: the kernel's instruction footprint shrinks from ~16k to a few thousand
 // instructions, which is what its instruction-cache behaviour needs.
 // EPI = 2 (GEGLU launches without residual / activation / second output): only the GEGLU path with a plain bf16 store.
-template <int BM, int BN, int MI, int NI, bool VT, int NT = 256, int EPI = 0>
+// DIRECT = false: an instantiation whose register budget the direct form does not fit (it would spill) keeps the LDS walk only.
+template <int BM, int BN, int MI, int NI, bool VT, int NT = 256, int EPI = 0, bool DIRECT = true>
 __device__ __forceinline__ void igemm_epilogue(const IgemmDev& p, f32x4 (&acc)[MI][NI], char* smem, bool vt_wg, int m0,
                                                int n0, int wm_off, int wn_off, int lrow, int lq, int split, int tid,
                                                const float* lnst = nullptr) {
@@ -339,6 +461,12 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmDev& p, f32x4 (&acc)[M
       }
     }
     return;
+  }
+  if constexpr (LEAN && !VT && DIRECT) {
+    if (p.ws_mode & 4) {                                     // register-direct form (host: epilogue_direct() in igemm.hip + the launch's epilogue choice)
+      igemm_epilogue_direct<BM, BN, MI, NI, EPI == 4>(p, acc, smem, m0, n0, wm_off, wn_off, lrow, lq, tid);
+      return;
+    }
   }
   float* Cs = reinterpret_cast<float*>(smem);
   if constexpr (LEAN && !VT) lnst = nullptr;               // LEAN keeps the V^T tile and the LayerNorm fold only in VT kernels
@@ -1330,7 +1458,11 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_pipe_kernel(const IgemmDev
       else mma_step(std::false_type{}, smem, LBs, ks, false);
     }
   }
-  igemm_epilogue<BM, BN, MI, NI, VT, NT, EPI>(p, acc, smem, vt_wg, m0, n0, wm * (BM / WM), wn * (BN / WN), lrow, lq, split, tid, lnst);
+  // direct form: tiles of fewer than 16 accumulator blocks a lane (the 128x128 / 256x128 tiles would need 15 - 20 more VGPRs and grow by
+  // 1.4 - 2.9k instructions), and no LoRA side channel (+ 0.9 - 1.8k instructions on the larger tiles; on the 64x64 tile the short-K
+  // projections measured 9.56 -> 9.79 us with it: DESIGN.md 5.8)
+  static_assert(EPI != 4 || RP == 0, "the statistics epilogue's LDS table needs the LoRA tail's LDS reads behind a barrier");
+  igemm_epilogue<BM, BN, MI, NI, VT, NT, EPI, (MI * NI < 16 && RP == 0)>(p, acc, smem, vt_wg, m0, n0, wm * (BM / WM), wn * (BN / WN), lrow, lq, split, tid, lnst);
 #ifdef ALDM_DIAG
   if (p.diag && lane == 0) {
     unsigned long long dg_t_end; asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(dg_t_end) :: "memory");

@@ -8,7 +8,8 @@
 // the activation is fetched ONCE per chunk and only the weight tiles stream (S-deep LDS-DMA ring, counted vmcnt, one raw
 // barrier per tap) -- 2.6x fewer bytes through the texture path at level 0.
 // Measured (MI355X, in a replayed graph, level-0 conv 128->128 on 8 x 250 x 16): 21.0 us per launch = 2.5 launch floor
-// + 3.3 tap-loop skeleton (waits / barriers) + 9.3 DMA + MFMA + 5.8 epilogue; the generic 128x64 tile takes 24 us.  The
+// + 3.3 tap-loop skeleton (waits / barriers) + 9.3 DMA + MFMA + 5.8 epilogue (the LDS walk; plain launches now store straight from the
+// accumulators, igemm_epilogue_direct: DESIGN.md 5.8, not re-measured per launch); the generic 128x64 tile takes 24 us.  The
 // in-context tuner (tools/autotune.py) picks this kernel where it wins (the 256..384-wide level-0 / training convs).
 //
 //   * 8 wave64s; v_mfma_f32_16x16x32_bf16, issued "swapped" like the generic kernel so that the shared epilogue

@@ -246,7 +246,8 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void igemm_ws_kernel(const Ige
   }
   __builtin_amdgcn_s_waitcnt(0xC07F);                   // lgkmcnt(0): this wave's last fragment reads
   __builtin_amdgcn_s_barrier();                         // every DMA has landed and every fragment is read: the ring's LDS is free
-  igemm_epilogue<BM, BN, MI, NI, false, NTC, EPI>(p, acc, smem, false, m0, n0, wm * (BM / WM), wn * (BN / WN), lrow, lq, split, tid, nullptr);
+  // (256x128: twelve waves leave 168 VGPRs a lane, the 64 accumulators + the direct form's residual quads spill -- LDS walk only)
+  igemm_epilogue<BM, BN, MI, NI, false, NTC, EPI, (MI * NI < 16)>(p, acc, smem, false, m0, n0, wm * (BM / WM), wn * (BN / WN), lrow, lq, split, tid, nullptr);
 #endif
 }
 

@@ -463,6 +463,13 @@ QSTATS_MIN_HW = 2048
 XCD_MAP = int(os.environ.get("ALDM_XCD_MAP", "0"))
 
 
+# Form of the standard bf16 epilogue of the unsplit igemm launches (aldm_igemm_t.xcd_map bits 4-5): the plain ones store straight from
+# the accumulator registers (no fp32 LDS image, no barrier) unless ALDM_NO_DIRECT_EPI=1 (every launch walks the LDS image, as before).
+# `out` is bit-identical either way; the GroupNorm hand-over table differs in the order of its fp32 sums.  conv(epi=) overrides per launch.
+EPI_FORM = _lib.EPI_LDS if os.environ.get("ALDM_NO_DIRECT_EPI") == "1" else _lib.EPI_AUTO
+EPI_TRACE = None                    # tests / tools: a list that receives aldm_igemm_epilogue_form (1 direct, 0 LDS walk) of every conv() launch
+
+
 # Layout of the fp32 slabs a split-K launch leaves for a deferred reduce: quad-planar ([split][image][C / 4][HW][4]: what one
 # (image, group) workgroup of the consuming GroupNorm reads is contiguous) unless ALDM_NO_SLAB_PLANAR=1 (row-major [split][M][C], the
 # layout of every non-deferred split-K launch).  The slab stores of a deferred launch are write-through (the partials drain to memory
@@ -538,7 +545,7 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
          out_slope=0.0, res=None, res2=None, alpha=1.0, post_act=ACT_NONE, post_slope=0.0, out2=None, out=None, out_f32=False, out_ld=None, out_batch_stride=None,
          out_pix_stride=1, out_pix_offset=0, vt=None, vt_col0=0, vt_ld=0, vt_batch_stride=0, lora_t_out=None,
          splits=None, tile=0, ring=0, gn=None, gn_keep=False, defer=False, rowstats=False, ln_parts=None, x3=None, x4=None,
-         vt_dual=False, qstats=False, gn_in=None, lora_gate=None, slab_layout=None, slab_wt=None):
+         vt_dual=False, qstats=False, gn_in=None, lora_gate=None, slab_layout=None, slab_wt=None, epi=None):
     """Implicit-GEMM convolution over channels-last x [B, IH, IW, C1] (+ x2 [B, IH, IW, C2]).
 
     gn=(gamma, beta, groups, eps, act) returns GroupNorm(+act) of the convolution instead of the convolution: when the launch
@@ -559,6 +566,9 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
     gn= (the consumer is this call's own groupnorm) takes ops.SLAB_LAYOUT; a defer= caller names the layout its consumer reads --
     groupnorm() reads either (the UNet forward passes ops.SLAB_LAYOUT), groupnorm_bwd() reads row-major only, which is the default.
     slab_wt defaults to ops.SLAB_WT.
+
+    epi (default: ops.EPI_FORM): _lib.EPI_AUTO / EPI_LDS / EPI_DIRECT, the form of the standard epilogue (EPI_DIRECT is an error for a
+    launch the direct form cannot take; EPI_AUTO walks the LDS image there).
 
     lora_gate (default: ops.LORA_GATE): fp32 [samples][Rp] per-sample gates of the LoRA side channel's columns (multi-adapter routing)."""
     _require_gpu(x)
@@ -753,7 +763,7 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
         a.workspace = _workspace(splits * M * pw.N * 4, x.device).data_ptr()
     a.tile = tile
     a.ring = ring
-    a.xcd_map = XCD_MAP
+    a.xcd_map = XCD_MAP | (EPI_FORM if epi is None else epi)
     lib = _lib.load()
     eff = lib.aldm_igemm_effective_splits(C.byref(a)) if (gn_defer and splits > 1) else 1
     layout = _lib.SLAB_ROWMAJOR
@@ -761,6 +771,8 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
         layout = slab_layout if slab_layout is not None else (SLAB_LAYOUT if gn is not None else _lib.SLAB_ROWMAJOR)
     a.defer_reduce = ((_lib.DEFER_ROWMAJOR | (_lib.DEFER_PLANAR if layout == _lib.SLAB_PLANAR else 0)
                        | (_lib.DEFER_WRITE_THROUGH if (SLAB_WT if slab_wt is None else slab_wt) else 0)) if eff > 1 else 0)
+    if EPI_TRACE is not None:
+        EPI_TRACE.append(lib.aldm_igemm_epilogue_form(C.byref(a)))
     ktot = KH * KW * pw.Cin + pw.Cext
     flops = 2.0 * M * pw.N * ktot + (2.0 * M * pw.Rp * (ktot + pw.N) if pw.Rp else 0.0)
     nbytes = 2.0 * (B * IH * IW * pw.Cin + M * pw.Cext + pw.N * ktot + M * ncols)

@@ -131,7 +131,14 @@ typedef struct {
      of output rows: right when activations >> weights), 2 = weight-stationary (an XCD owns a (K-slice, N-tile) range of the weights for
      every row: right at the UNet's 252- / 64-token levels, where every L2 would otherwise stream the whole weight matrix),
      0 = auto: weight-stationary iff the launch is not split-K and the weight matrix is larger than the activation image (measured:
-     csrc/igemm.hip).  Speed only; results are identical. */
+     csrc/igemm.hip).  Speed only; results are identical.
+     Bits 4-5 (ALDM_EPI_*): the form of the standard bf16 epilogue.  ALDM_EPI_AUTO: a plain launch stores straight from the accumulator
+     registers, every other launch walks the fp32 LDS image as before.  Plain = LDS-DMA path (Cin, Cin2 % 64 == 0, no in_act), unsplit, no
+     activation / GEGLU / V^T / out2 / res2 / fp32 output / rowstat_out / folded LayerNorm (ln_s), Cout % 8 == 0, out_ld and
+     out_batch_stride % 4 == 0, with rowbias: rowbias_ld % 4 == 0 and OH * OW >= the tile's rows; tiles other than 128x128, 256x128_W8 and
+     256x128_WS, and no LoRA side channel (Rp == 0).  aldm_igemm_epilogue_form() tells.  ALDM_EPI_LDS: always the LDS walk.
+     ALDM_EPI_DIRECT: the direct form or an error (ALDM_E_UNSUPPORTED) -- for tests.  `out` is bit-identical either way; qstat_out differs in
+     the order of its fp32 sums only. */
   int xcd_map;
   /* Multi-adapter routing (LAST: no existing offset moves).  lora_a / lora_b hold several adapters side by side (adapter a owns a block
      of the Rp columns of T = x A_cat^T); lora_gate is fp32 [M / gate_rows][Rp], one row per sample, and T[m][j] is multiplied by
@@ -158,6 +165,7 @@ enum { ALDM_TILE_AUTO = 0, ALDM_TILE_128x128 = 1, ALDM_TILE_64x64 = 2, ALDM_TILE
        ALDM_TILE_64x128_W8 = 10, ALDM_TILE_128x64_W8 = 11 /* 8-wave forms of the small tiles: two waves per SIMD where the grid is ~one
           workgroup per CU (split-K convolutions of the low-resolution levels); LDS-DMA path, no LoRA / V^T */ };
 
+enum { ALDM_EPI_AUTO = 0, ALDM_EPI_LDS = 0x10, ALDM_EPI_DIRECT = 0x20, ALDM_EPI_MASK = 0x30 };   /* aldm_igemm_t.xcd_map bits 4-5 */
 enum { ALDM_DEFER_ROWMAJOR = 1, ALDM_DEFER_PLANAR = 2, ALDM_DEFER_WRITE_THROUGH = 4 };   /* aldm_igemm_t.defer_reduce */
 enum { ALDM_SLAB_ROWMAJOR = 0, ALDM_SLAB_PLANAR = 1 };                                    /* slab layout as a consumer is told it */
 
@@ -165,6 +173,7 @@ int aldm_igemm(const aldm_igemm_t* p, void* stream);
 size_t aldm_igemm_workspace_bytes(const aldm_igemm_t* p);
 /* the split count the launch will really use (splits is clamped so that every split gets whole 64-wide K-tiles) */
 int aldm_igemm_effective_splits(const aldm_igemm_t* p);
+int aldm_igemm_epilogue_form(const aldm_igemm_t* p);   /* 1: register-direct epilogue, 0: LDS walk (see xcd_map) */
 /* Host-side restatement of the kernels' slab store address: element offset, in the workspace of a split-K launch over B images of HW
    pixels and C channels, of channel n of output row m (= b * HW + pix) in slab `split`, for layout ALDM_SLAB_*.  Needs no GPU (layout
    checks); -1 for an argument out of range. */
