@@ -86,7 +86,12 @@ struct AttnCfg {
 // before its conversion (p <= 1 would sit in e4m3's subnormal range for long sequences; l carries the same factor, so it cancels).
 // Until round 4 this was a separate, older kernel (4 waves, no deferred rescale, predicated loads) and 4.6 us slower than bf16 at
 // N = 1000; as a variant of this one it inherits every structural improvement.
-template <int DP, int NW, int SP, bool PRESCALED, bool FP8 = false>
+// LSE (the training forward, aldm_attention_lse): where l rides in the P V product as the row of ones (!VL) it is the sum of the
+// bf16-ROUNDED probabilities -- right for normalising O, which multiplies the same rounded P, but up to 3.5e-3 log2 units off the
+// log-sum-exp the backward recomputes P from (p = exp2(s c - lse) then carries a per-row factor of up to 0.25 %).  The LSE form of
+// those head dims therefore ALSO adds the fp32 probabilities up on the VALU (as VL does) and takes the stored lse from that sum;
+// O is normalised exactly as before.  Without LSE nothing changes.
+template <int DP, int NW, int SP, bool PRESCALED, bool FP8 = false, bool LSE = false>
 __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restrict__ q, int ldq,
                                                             const bf16* __restrict__ k, int ldk,
                                                             const bf16* __restrict__ vt, int vt_ld, long long vt_bs,
@@ -278,6 +283,8 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
   // stream pinned by inline asm) shows they do not: an MFMA costs its wave 8 issue cycles, its 32 pipe cycles run under the next five
   // VALU instructions (and under the SIMD's other wave), and this loop is VALU-issue-bound -- 4 x 8 issue cycles replace 16 packed adds.
   constexpr bool ML = Cfg::VL && ATTN_ML;
+  constexpr bool LSUM = LSE && !Cfg::VL;          // the fp32 row sum for the stored lse, next to the row of ones
+  static_assert(!(LSE && (FP8 || PRESCALED)), "the lse form is the plain bf16 kernel");
   float l_run = 0.f;                            // VL without ML: this lane's share of l (its 32 keys of every tile), VALU adds
   f32x2 l_pk = {0.f, 0.f};                      // ... accumulated as a PAIR (v_pk_add_f32: one instruction per two probabilities), folded into l_run per tile
   f32x16 lacc;
@@ -364,7 +371,7 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
         if constexpr (ML) {
 #pragma unroll
           for (int i = 0; i < 16; ++i) lacc[i] *= alpha;
-        } else if constexpr (Cfg::VL) {
+        } else if constexpr (Cfg::VL || LSUM) {
           l_pk *= alpha;
         }
       }
@@ -423,7 +430,7 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
 #define P0 p0
 #define P1 p1
 #endif
-        if constexpr (Cfg::VL && !ML) l_pk += f32x2{p0, p1};
+        if constexpr ((Cfg::VL && !ML) || LSUM) l_pk += f32x2{p0, p1};
         if constexpr (FP8) {
           pw8[i >> 2] = (i & 2) ? __builtin_amdgcn_cvt_pk_fp8_f32(P0, P1, pw8[i >> 2], true) : __builtin_amdgcn_cvt_pk_fp8_f32(P0, P1, pw8[i >> 2], false);
         } else {
@@ -490,7 +497,7 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
     iteration(it, Set0{});
     if (it + 1 < niter) iteration(it + 1, Set1{});
   }
-  if constexpr (Cfg::VL && !ML) l_run = l_pk[0] + l_pk[1];
+  if constexpr ((Cfg::VL && !ML) || LSUM) l_run = l_pk[0] + l_pk[1];
 
   if constexpr (SP > 1) {
     // ---- merge the key groups: groups 1.. leave (m, l, O^T) in LDS (the staging buffers are dead after the last barrier),
@@ -531,8 +538,9 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
   const float l_half = (Cfg::VL && !ML) ? l_run : o[Cfg::ONES_T][Cfg::ONES_I];   // (VALU form: this lane's 32 keys per tile; the other 32 sit in lane ^ 32)
   const float l_tot = ML ? lacc[0] : l_half + __shfl_xor(l_half, 32, 64);
   const float inv = 1.0f / l_tot;
+  const float l_lse = LSUM ? l_run + __shfl_xor(l_run, 32, 64) : l_tot;   // (LSUM: this lane's 32 keys per tile, like l_half)
   if (lse && hh == 0 && q0 + r < N)   // log2-domain log-sum-exp of the scaled scores: p = exp2(s*c - lse)
-    lse[((long long)b * gridDim.y + head) * N + q0 + r] = m_run + __log2f(l_tot);
+    lse[((long long)b * gridDim.y + head) * N + q0 + r] = m_run + __log2f(l_lse);
   if (q0 + r < N) {
     bf16* orow = out + ((long long)b * N + q0 + r) * out_ld + head * D;
 #pragma unroll
@@ -548,11 +556,11 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
   }
 }
 
-template <int DP, int NW, int SP, bool PS, bool FP8 = false>
+template <int DP, int NW, int SP, bool PS, bool FP8 = false, bool LSE = false>
 int launch_attn(const void* q, int ldq, const void* k, int ldk, const void* vt, int vt_ld, long long vt_bs, int B, int N,
                 int H, int D, float scale, void* out, int out_ld, float* lse, const int* kv_len, hipStream_t st) {
   using Cfg = AttnCfg<DP, FP8>;
-  auto kern = attention_kernel<DP, NW, SP, PS, FP8>;
+  auto kern = attention_kernel<DP, NW, SP, PS, FP8, LSE>;
   constexpr int MERGE = SP == 1 ? 0 : (SP - 1) * (NW / SP) * (Cfg::DT * 16 + 2) * 256;   // the key groups' (m, O^T, l) exchange re-uses the staging area
   constexpr int LDS = 2 * SP * Cfg::TILE > MERGE ? 2 * SP * Cfg::TILE : MERGE;             // (one-byte images can be smaller than it)
   static unsigned long long attr_done = 0;   // per-device bit mask (aldm_set_max_lds)
@@ -583,22 +591,31 @@ int launch_attn_d(const void* q, int ldq, const void* k, int ldk, const void* vt
     if (N >= 64) return launch_attn<DP, 4, 1, PS, true>(ALDM_ATTN_ARGS);
     return launch_attn<DP, 1, 1, PS, true>(ALDM_ATTN_ARGS);
   }
+  // the lse form of the head dims whose l is the row of ones sums the fp32 probabilities for the stored lse (attention_kernel, LSE)
+#define ALDM_ATTN_GO(NWV, SPV)                                                              \
+  do {                                                                                      \
+    if constexpr (!PS && DP % 32 != 0) {                                                    \
+      if (lse) return launch_attn<DP, NWV, SPV, PS, false, true>(ALDM_ATTN_ARGS);           \
+    }                                                                                       \
+    return launch_attn<DP, NWV, SPV, PS>(ALDM_ATTN_ARGS);                                   \
+  } while (0)
   static const int force = getenv("ALDM_ATTN_CFG") ? atoi(getenv("ALDM_ATTN_CFG")) : 0;   // tuning aid: 10 * waves + key split
-  if (force == 81) return launch_attn<DP, 8, 1, PS>(ALDM_ATTN_ARGS);
-  if (force == 82) return launch_attn<DP, 8, 2, PS>(ALDM_ATTN_ARGS);
-  if (force == 41) return launch_attn<DP, 4, 1, PS>(ALDM_ATTN_ARGS);
-  if (force == 42) return launch_attn<DP, 4, 2, PS>(ALDM_ATTN_ARGS);
-  if (force == 21) return launch_attn<DP, 2, 1, PS>(ALDM_ATTN_ARGS);
+  if (force == 81) ALDM_ATTN_GO(8, 1);
+  if (force == 82) ALDM_ATTN_GO(8, 2);
+  if (force == 41) ALDM_ATTN_GO(4, 1);
+  if (force == 42) ALDM_ATTN_GO(4, 2);
+  if (force == 21) ALDM_ATTN_GO(2, 1);
   if constexpr (DP == 32) {
     if (force == 162) return launch_attn<DP, 16, 2, PS>(ALDM_ATTN_ARGS);   // 16 waves = 4 per SIMD, keys split over two wave groups
   }
   if (N >= 768) {
-    if ((long long)cdiv(N, 256) * H * B >= 256) return launch_attn<DP, 8, 1, PS>(ALDM_ATTN_ARGS);
-    return launch_attn<DP, 8, 2, PS>(ALDM_ATTN_ARGS);
+    if ((long long)cdiv(N, 256) * H * B >= 256) ALDM_ATTN_GO(8, 1);
+    ALDM_ATTN_GO(8, 2);
   }
-  if (N >= 192) return launch_attn<DP, 4, 2, PS>(ALDM_ATTN_ARGS);
-  if (N >= 64) return launch_attn<DP, 4, 1, PS>(ALDM_ATTN_ARGS);   // N = 64 x 64 (batch, head) pairs: 4 waves 5.2 us vs 2 waves 5.7 us
-  return launch_attn<DP, 1, 1, PS>(ALDM_ATTN_ARGS);
+  if (N >= 192) ALDM_ATTN_GO(4, 2);
+  if (N >= 64) ALDM_ATTN_GO(4, 1);   // N = 64 x 64 (batch, head) pairs: 4 waves 5.2 us vs 2 waves 5.7 us
+  ALDM_ATTN_GO(1, 1);
+#undef ALDM_ATTN_GO
 #undef ALDM_ATTN_ARGS
 }
 
