@@ -2,7 +2,7 @@
 
 Drop-in surface for the reference's entry points:
 AudioLDMPipeline / UNet2DConditionModel / AutoencoderKL / SpeechT5HifiGan / DDIMScheduler / DPMSolverMultistepScheduler /
-EulerAncestralDiscreteScheduler (all three in scheduler.py; the last one exported here on first use as well) and the peft-shaped LoraConfig / get_peft_model helpers; AudioLDMAudioToAudioPipeline (audio2audio.py,
+UniPCMultistepScheduler / EulerAncestralDiscreteScheduler (all four in scheduler.py; the last two exported here on first use as well) and the peft-shaped LoraConfig / get_peft_model helpers; AudioLDMAudioToAudioPipeline (audio2audio.py,
 exported here on first use) starts from a recording.  No CPU fallback: ops raise if libaldm_hip.so is missing.
 """
 __version__ = "0.1.0"
@@ -12,6 +12,9 @@ def __getattr__(name):
     if name == "AudioLDMAudioToAudioPipeline":
         from .audio2audio import AudioLDMAudioToAudioPipeline
         return AudioLDMAudioToAudioPipeline
+    if name == "UniPCMultistepScheduler":
+        from .scheduler import UniPCMultistepScheduler
+        return UniPCMultistepScheduler
     if name == "EulerAncestralDiscreteScheduler":
         from .scheduler import EulerAncestralDiscreteScheduler
         return EulerAncestralDiscreteScheduler

@@ -217,13 +217,13 @@ PROTOTYPES = {
     "aldm_token_mean": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
-# The six fused scheduler steps share one argument frame (csrc/elementwise.hip launch_step_fused): eps, x, B, n_per_sample, cfg,
-# guidance, coef, step_idx, x_in | the solver's operand (DDIM: none, DPM: hist, Euler-ancestral: the Philox state) | table, row_elems,
+# The eight fused scheduler steps share one argument frame (csrc/elementwise.hip launch_step_fused): eps, x, B, n_per_sample, cfg,
+# guidance, coef, step_idx, x_in | the solver's operand (DDIM: none, DPM: hist, Euler-ancestral: the Philox state, UniPC: state) | table, row_elems,
 # rowbias, timesteps, n_steps, t_out, ticket | masked: x0, noise, mask, blend, channels | stream.
 _STEP_HEAD = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
 _STEP_TAIL = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
 _STEP_INPAINT = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-for _solver, _operand in (("ddim", []), ("dpm", [C.c_void_p]), ("euler_a", [C.c_void_p])):
+for _solver, _operand in (("ddim", []), ("dpm", [C.c_void_p]), ("euler_a", [C.c_void_p]), ("unipc", [C.c_void_p])):
     PROTOTYPES[f"aldm_{_solver}_step_fused"] = (C.c_int, _STEP_HEAD + _operand + _STEP_TAIL + [C.c_void_p])
     PROTOTYPES[f"aldm_{_solver}_step_fused_masked"] = (C.c_int, _STEP_HEAD + _operand + _STEP_TAIL + _STEP_INPAINT + [C.c_void_p])
 

@@ -3,7 +3,7 @@
 `AudioLDMAudioToAudioPipeline.from_pipe(pipe)(prompt, audio=wav, strength=0.5)` partly noises the encoded clip and denoises it
 toward the prompt over the suffix timesteps[begin:] of the schedule (diffusers' get_timesteps rule).  With `mask=` the loop is
 diffusers' legacy inpaint loop: after every step the known latents, noised to the next timestep, are blended back in where the mask
-keeps them, inside the fused step launch (aldm_{ddim,dpm}_step_fused_masked), so the loop stays one captured graph.
+keeps them, inside the fused step launch (aldm_{ddim,dpm,unipc}_step_fused_masked), so the loop stays one captured graph.
 
 With an EulerAncestralDiscreteScheduler every step re-draws part of the noise on the device (aldm_euler_a_step_fused[_masked]); the
 rows are then in sigma space, (a, s) = (1, sigma).

@@ -122,10 +122,24 @@ __device__ __forceinline__ float euler_a_update(float eu, float et, float xv, in
   return fmaf(sigma_up, z, fmaf(e, dt, xv));
 }
 
-// ---- the fused scheduler step: one frame (step_fused_body), three solvers --------------------------------------------------------
+// UniPC (predictor-corrector) update of one element from a coefficient row {alpha_s, sig_s, Ac, Bc, Cc, Dc, Ap, Bp, Cp, convert, corr,
+// corr_reads_m1, pred_reads_m0, -, -, -} (scheduler.py UniPCMultistepScheduler.coefficient_table), every fused multiply-add spelled
+// out as in ddim_update; m_t is dpm_model_output of the UNCORRECTED sample:
+//   xc = corr ? Ac last + Bc m0 + Cc (m1 - m0) + Dc (m_t - m0) : x ;  x' = Ap xc + Bp m_t + Cp (m_t - m0)
+// (m0, m1: the previous two converted outputs; Cc == 0 / Cp == 0 and m1 / m0 unread where the corrector / the predictor is first order)
+__device__ __forceinline__ float unipc_correct(float last, float m0, float m1, float mt, float Ac, float Bc, float Cc, float Dc) {
+  return fmaf(Ac, last, fmaf(Bc, m0, fmaf(Cc, m1 - m0, Dc * (mt - m0))));
+}
+
+__device__ __forceinline__ float unipc_predict(float xc, float m0, float mt, float Ap, float Bp, float Cp) {
+  return fmaf(Ap, xc, fmaf(Bp, mt, Cp * (mt - m0)));
+}
+
+// ---- the fused scheduler step: one frame (step_fused_body), four solvers ---------------------------------------------------------
 // What the frame asks of a scheduler.  ROW: the floats per row of its coefficient table.  TICKET_OPTIONAL: whether its entry points
 // take ticket == NULL (the eager scheduler.step: the counter is left alone, and table is NULL there too).  Its one extra kernel
-// operand, if any, as the first member (the kernels build the solver from it; every other member starts at zero).  And six hooks,
+// operand, if any, as the first member (the kernels build the solver from it, UniPC's also from the counter and the element count that
+// they hold anyway; every other member starts at zero).  And six hooks,
 // which every thread calls in this order:
 //   begin()             before the bounds test: the state that the last workgroup moves, read where the counter is read
 //   load<VEC>(cf, idx)  the coefficient row `cf` and whatever else the update of elements [idx, idx + VEC) reads
@@ -222,6 +236,61 @@ struct EulerASolver {
   __device__ __forceinline__ void advance() { philox_store_next(rng, rs); }
 };
 
+// state [3][B][n] fp32: plane 0 the last corrected sample, planes 1 and 2 the previous two converted model outputs as a RING indexed by
+// the parity of the step counter, so that nothing is shifted: step `cur` reads m0 (step cur - 1's output) from slot (cur - 1) & 1 and m1
+// (step cur - 2's) from slot cur & 1, then writes m_t over m1's slot.  Every thread reads and writes its own elements only, so the
+// ring needs no synchronisation beyond the frame's.  A plane is loaded only where the row's flags ask for it: row 0 (no corrector,
+// first-order predictor) reads none, so a replay that wrapped to step 0, at either parity, starts clean.  last and the slots receive
+// unblended values (diffusers: the caller blends after scheduler.step); last is the corrected sample, or x itself without corrector.
+struct UniPCSolver {
+  static constexpr int ROW = 16;
+  static constexpr bool TICKET_OPTIONAL = true;
+  float* __restrict__ state;
+  const int* __restrict__ step_idx;
+  long long total;                                            // B * n: the stride between the planes of state
+  int slot;                                                   // cur & 1: m1's slot, and where m_t goes
+  float alpha_s, sig_s, Ac, Bc, Cc, Dc, Ap, Bp, Cp;
+  bool convert, corr, c2, p2;
+  f32x4 last, m0, m1, mt, xc;                                 // lanes [0, VEC)
+  __device__ __forceinline__ void begin() { slot = step_idx[0] & 1; }
+  template <int VEC>
+  __device__ __forceinline__ void load(const float* __restrict__ cf, long long idx) {
+    alpha_s = cf[0], sig_s = cf[1], Ac = cf[2], Bc = cf[3], Cc = cf[4], Dc = cf[5], Ap = cf[6], Bp = cf[7], Cp = cf[8];
+    convert = cf[9] != 0.f, corr = cf[10] != 0.f, c2 = cf[11] != 0.f, p2 = cf[12] != 0.f;
+    if (corr) {
+      const fvec_t<VEC> v = *reinterpret_cast<const fvec_t<VEC>*>(state + idx);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) last[k] = v[k];
+    }
+    if (corr || p2) {
+      const fvec_t<VEC> v = *reinterpret_cast<const fvec_t<VEC>*>(state + (2 - slot) * total + idx);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) m0[k] = v[k];
+    }
+    if (c2) {
+      const fvec_t<VEC> v = *reinterpret_cast<const fvec_t<VEC>*>(state + (1 + slot) * total + idx);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) m1[k] = v[k];
+    }
+  }
+  template <int VEC>
+  __device__ __forceinline__ float update(int k, float eu, float et, float xv, int cfg, float g) {
+    mt[k] = dpm_model_output(eu, et, xv, cfg, g, alpha_s, sig_s, convert);
+    xc[k] = corr ? unipc_correct(last[k], m0[k], c2 ? m1[k] : m0[k], mt[k], Ac, Bc, Cc, Dc) : xv;
+    return unipc_predict(xc[k], p2 ? m0[k] : mt[k], mt[k], Ap, Bp, Cp);
+  }
+  __device__ __forceinline__ float unet_input(float r) const { return r; }
+  template <int VEC>
+  __device__ __forceinline__ void store(long long idx) {
+    fvec_t<VEC> v, w;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) v[k] = xc[k], w[k] = mt[k];
+    *reinterpret_cast<fvec_t<VEC>*>(state + idx) = v;
+    *reinterpret_cast<fvec_t<VEC>*>(state + (1 + slot) * total + idx) = w;
+  }
+  __device__ __forceinline__ void advance() {}
+};
+
 // The whole per-step bookkeeping of the replayed denoise loop as ONE launch behind the UNet: classifier-free guidance + the solver's
 // update (DDIM: as cfg_ddim_step_kernel), the inpainting blend after it (MASKED, see inpaint_blend), the bf16 input of the next UNet
 // call, the NEXT step's row of the precomputed time-embedding table gathered into `rowbias`, and the device-side step counter
@@ -229,7 +298,7 @@ struct EulerASolver {
 // value, so no workgroup can see the counter move under it -- three launches become one.
 // VEC elements per thread (4 when B * n % 4 == 0): a quarter of the workgroups means a quarter of the same-address ticket atomics,
 // which were most of this launch's 8.4 us (500 workgroups at one thread per element).
-// The six kernels below keep their own parameter lists (the first 64 bytes, preloaded into SGPRs, hold coef and step_idx, which the
+// The eight kernels below keep their own parameter lists (the first 64 bytes, preloaded into SGPRs, hold coef and step_idx, which the
 // first dependent load needs; the unmasked ones carry no inpainting operand) and instantiate this frame with their solver.  They form
 // the thread index `tix` themselves: read in here, blockDim.x is not folded to the uniform workgroup size, and every wave starts with
 // one more dependent load.
@@ -363,6 +432,33 @@ __global__ __launch_bounds__(256) void euler_a_step_fused_masked_kernel(const fl
   step_fused_body<EulerASolver, VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, EulerASolver{rng}, table, row_elems, rowbias,
                                            timesteps, n_steps, t_out, ticket,
                                            (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void unipc_step_fused_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg,
+                                                               float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                               bf16* __restrict__ x_in, float* __restrict__ state,
+                                                               const float* __restrict__ table, long long row_elems, float* __restrict__ rowbias,
+                                                               const float* __restrict__ timesteps, int n_steps, float* __restrict__ t_out,
+                                                               unsigned* __restrict__ ticket) {
+  step_fused_body<UniPCSolver, VEC, false>(eps, x, B, n, cfg, g, coef, step_idx, x_in, UniPCSolver{state, step_idx, (long long)B * n}, table,
+                                           row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                                           (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void unipc_step_fused_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                      int cfg, float g, const float* __restrict__ coef,
+                                                                      int* __restrict__ step_idx, bf16* __restrict__ x_in,
+                                                                      float* __restrict__ state, const float* __restrict__ table,
+                                                                      long long row_elems, float* __restrict__ rowbias,
+                                                                      const float* __restrict__ timesteps, int n_steps, float* __restrict__ t_out,
+                                                                      unsigned* __restrict__ ticket, const float* __restrict__ x0,
+                                                                      const float* __restrict__ noise, const float* __restrict__ mask,
+                                                                      const float* __restrict__ blend, int C) {
+  step_fused_body<UniPCSolver, VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, UniPCSolver{state, step_idx, (long long)B * n}, table,
+                                          row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                                          (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
 }
 
 __global__ void advance_step_kernel(int* step_idx, const float* __restrict__ timesteps, int n_steps, float* t_out) {
@@ -771,6 +867,26 @@ extern "C" int aldm_euler_a_step_fused_masked(const float* eps, float* x, int B,
                                                euler_a_step_fused_masked_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef, step_idx,
                                                x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
                                                Inpaint{x0, noise, mask, blend, channels}, stream, rng_state);
+}
+
+// the UniPC fused steps: aldm_dpm_step_fused's argument list with the solver state [3][B][n] (UniPCSolver) in the place of the history
+// buffer
+extern "C" int aldm_unipc_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                     int* step_idx, void* x_in_bf16, float* state, const float* table, long long row_elems, float* rowbias,
+                                     const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream) {
+  return launch_step_fused<UniPCSolver, false>("unipc_step_fused", unipc_step_fused_kernel<4>, unipc_step_fused_kernel<1>, eps, x, B,
+                                               n_per_sample, cfg, guidance, coef, step_idx, x_in_bf16, table, row_elems, rowbias, timesteps,
+                                               n_steps, t_out, ticket, Inpaint{}, stream, state);
+}
+
+extern "C" int aldm_unipc_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                            const float* coef, int* step_idx, void* x_in_bf16, float* state, const float* table,
+                                            long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                            unsigned* ticket, const float* x0, const float* noise, const float* mask, const float* blend,
+                                            int channels, void* stream) {
+  return launch_step_fused<UniPCSolver, true>("unipc_step_fused_masked", unipc_step_fused_masked_kernel<4>, unipc_step_fused_masked_kernel<1>,
+                                              eps, x, B, n_per_sample, cfg, guidance, coef, step_idx, x_in_bf16, table, row_elems, rowbias,
+                                              timesteps, n_steps, t_out, ticket, Inpaint{x0, noise, mask, blend, channels}, stream, state);
 }
 
 extern "C" int aldm_add_noise(const float* x, const float* noise, const float* coef, int B, long long n_per_sample,

@@ -9,6 +9,9 @@ bf16 UNet input, the timestep scalar and a step counter that indexes the precomp
 table -- so ONE captured graph of a single step replays unchanged for all N steps with no host work
 in between.  With a DPMSolverMultistepScheduler the update is the multistep solver's (ops.dpm_step_fused): its coefficient rows
 come from the scheduler in the same way, and the previous step's model output lives in one more device buffer.
+With a UniPCMultistepScheduler the update is the predictor-corrector's (ops.unipc_step_fused): the last corrected
+sample and the previous two model outputs live in one device buffer `state` [3, B, H, W, C], whose two output slots the kernel uses as
+a ring turned by the parity of the step counter, so the captured graph stays one step for all N.
 Audio-to-audio and inpainting: `begin_index` runs the suffix timesteps[begin:] of the schedule, and `masked`
 swaps in the masked fused steps, which blend the known latents back in after every update (x0, noise, mask and the blend rows in
 four more device buffers, filled by set_inpaint) -- still one launch behind the UNet, so the loop stays one captured graph.
@@ -22,7 +25,7 @@ Multi-adapter LoRA: a gated engine's UNet launches read a
 import torch
 
 from . import ops
-from .scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, _fresh_seed
+from .scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, UniPCMultistepScheduler, _fresh_seed
 
 
 class DenoiseEngine:
@@ -39,6 +42,7 @@ class DenoiseEngine:
         scheduler.set_timesteps(num_inference_steps)
         self.dpm = isinstance(scheduler, DPMSolverMultistepScheduler)
         self.euler = isinstance(scheduler, EulerAncestralDiscreteScheduler)
+        self.unipc = isinstance(scheduler, UniPCMultistepScheduler)
         self.begin_index, self.masked = int(begin_index), bool(masked)
         if not 0 <= self.begin_index < len(scheduler.timesteps):
             raise ValueError(f"begin_index {begin_index} outside the schedule of {len(scheduler.timesteps)} steps")
@@ -54,7 +58,7 @@ class DenoiseEngine:
         # default stays a single chain.
         if chains is None:
             chains = 1
-        if chains > 1 and (self.dpm or self.euler):
+        if chains > 1 and (self.dpm or self.euler or self.unipc):
             raise NotImplementedError("chains > 1 runs the DDIM update only")
         if chains > 1 and self.masked:
             raise NotImplementedError("chains > 1 runs the unmasked update only")
@@ -65,6 +69,9 @@ class DenoiseEngine:
         self.x_in = [torch.zeros(nbc, height, width, self.C, dtype=torch.bfloat16, device=dev) for _ in range(chains)]
         # DPM-Solver: the previous step's converted model output (read by second-order rows, never by row 0)
         self.hist = torch.zeros_like(self.x) if self.dpm else None
+        # UniPC: the last corrected sample and the two previous converted model outputs (each read only by rows that ask for it, none
+        # by row 0)
+        self.state = torch.zeros(3, *self.x.shape, dtype=torch.float32, device=dev) if self.unipc else None
         # Euler-ancestral: the Philox state {seed_lo, seed_hi, draw_lo, draw_hi} of the in-loop noise (set_seed; set_latents puts the
         # draw ordinal back to 0) and the input scale of the first row, which set_latents applies (the later rows' are in the table)
         self.rng = ops.philox_state(_fresh_seed(), 0, dev) if self.euler else None
@@ -76,9 +83,9 @@ class DenoiseEngine:
             self.x0, self.noise = torch.zeros_like(self.x), torch.zeros_like(self.x)
             self.mask = torch.ones(batch, height, width, dtype=torch.float32, device=dev)
             self.blend = scheduler.blend_table(self.begin_index).contiguous().to(dev)
-        # the single-chain step's last launch (ops.{ddim,dpm,euler_a}_step_fused[_masked]) and what it takes beside the frame's operands
-        self._step = getattr(ops, ("euler_a" if self.euler else "dpm" if self.dpm else "ddim") + "_step_fused" + ("_masked" if self.masked else ""))
-        self._solver_args = (self.rng,) if self.euler else (self.hist,) if self.dpm else ()
+        # the single-chain step's last launch (ops.{ddim,dpm,unipc,euler_a}_step_fused[_masked]) and what it takes beside the frame's operands
+        self._step = getattr(ops, ("euler_a" if self.euler else "dpm" if self.dpm else "unipc" if self.unipc else "ddim") + "_step_fused" + ("_masked" if self.masked else ""))
+        self._solver_args = (self.rng,) if self.euler else (self.hist,) if self.dpm else (self.state,) if self.unipc else ()
         self._inpaint_args = (self.x0, self.noise, self.mask, self.blend) if self.masked else ()
         self.t_buf = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -181,7 +188,7 @@ class DenoiseEngine:
         self.rng.copy_(ops.philox_state(seed, 0, self.dev))
 
     def set_latents(self, latents_nchw):
-        """latents [B, C, H, W] fp32, already multiplied by init_noise_sigma (1 for DDIM / DPM-Solver).  Euler-ancestral: the unscaled
+        """latents [B, C, H, W] fp32, already multiplied by init_noise_sigma (1 for DDIM / DPM-Solver / UniPC).  Euler-ancestral: the unscaled
         sigma-space sample; the UNet input gets row 0's input scale here, and the noise stream's draw ordinal returns to 0."""
         x = ops.nchw_to_nhwc(latents_nchw.to(self.dev, torch.float32).contiguous(), out_f32=True)
         self.x.copy_(x)
@@ -195,6 +202,8 @@ class DenoiseEngine:
         self.t_buf.copy_(self.timesteps_f32[:1])
         if self.hist is not None:
             self.hist.zero_()
+        if self.state is not None:
+            self.state.zero_()
         if self.rng is not None:
             self.rng[2:].zero_()
         self._prime()
@@ -252,6 +261,7 @@ class DenoiseEngine:
         self._plan_ref, self.plan_version = self.unet.plan(), self.unet.plan_version
         saved = (self.x.clone(), [t.clone() for t in self.x_in], self.step_idx.clone(), self.t_buf.clone())
         saved_hist = self.hist.clone() if self.hist is not None else None
+        saved_state = self.state.clone() if self.state is not None else None
         saved_rng = self.rng.clone() if self.rng is not None else None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -268,6 +278,8 @@ class DenoiseEngine:
             dst.copy_(src)
         if saved_hist is not None:
             self.hist.copy_(saved_hist)
+        if saved_state is not None:
+            self.state.copy_(saved_state)
         if saved_rng is not None:
             self.rng.copy_(saved_rng)
         self._prime()

@@ -1247,12 +1247,14 @@ def _inpaint_args(x, x0, noise, mask, blend, n_steps):
 
 
 # solver -> (columns of its coefficient table, flops per element, bytes per element beside the frame's, ticket may be None)
-#   dpm: hist read/write (upper bound: second-order rows); euler_a: ~100 flops for ten Philox rounds and a Box-Muller, no noise tensor
-_STEP_SOLVERS = {"ddim": (4, 6.0, 0.0, False), "dpm": (8, 10.0, 8.0, True), "euler_a": (4, 110.0, 0.0, True)}
+#   dpm: hist read/write (upper bound: second-order rows); euler_a: ~100 flops for ten Philox rounds and a Box-Muller, no noise tensor;
+#   unipc: last, m0, m1 read and last, m_t written (upper bound: second-order corrector rows)
+_STEP_SOLVERS = {"ddim": (4, 6.0, 0.0, False), "dpm": (8, 10.0, 8.0, True), "euler_a": (4, 110.0, 0.0, True),
+                 "unipc": (16, 22.0, 20.0, True)}
 
 
 def _step_fused(solver, eps, x, cfg, guidance, coef, step_idx, x_in, operand, table, rowbias, timesteps_f32, t_out, ticket, inpaint=None):
-    """The frame the six fused scheduler steps share (csrc/elementwise.hip step_fused_body / launch_step_fused): the checks, the
+    """The frame the eight fused scheduler steps share (csrc/elementwise.hip step_fused_body / launch_step_fused): the checks, the
     flops / bytes model and the launch of aldm_<solver>_step_fused[_masked].  operand: the solver's extra tensors, () or a 1-tuple;
     inpaint: None or (x0, noise, mask, blend)."""
     coef_cols, flops, solver_bytes, ticket_optional = _STEP_SOLVERS[solver]
@@ -1306,6 +1308,30 @@ def dpm_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, hist, tab
     receives the unblended converted model output.  ticket None: eager, the counter stays (table must be None then)."""
     assert hist.dtype == torch.float32 and hist.numel() == x.numel()
     _step_fused("dpm", eps, x, cfg, guidance, coef, step_idx, x_in, (hist,), table, rowbias, timesteps_f32, t_out, ticket,
+                (x0, noise, mask, blend))
+
+
+def _check_unipc_state(state, x):
+    assert state.dtype == torch.float32 and state.is_contiguous() and state.device == x.device, "unipc state: contiguous fp32 on x's device"
+    assert state.dim() >= 1 and state.shape[0] == 3 and state.numel() == 3 * x.numel(), "unipc state: [3, *x.shape]"
+
+
+def unipc_step_fused(eps, x, cfg, guidance, coef, step_idx, x_in, state, table=None, rowbias=None, timesteps_f32=None, t_out=None,
+                     ticket=None):
+    """CFG + UniPC predictor-corrector update (+ gather_row(next step) + advance_step when `ticket` is given) as one launch
+    (aldm_unipc_step_fused).  coef fp32 [n_steps, 16] (UniPCMultistepScheduler.coefficient_table); state fp32 [3, *x.shape]: the last
+    corrected sample and the two previous converted model outputs, a ring turned by the parity of step_idx (include/aldm_hip.h).
+    ticket None: eager, the counter stays (the caller alternates it between 0 and 1)."""
+    _check_unipc_state(state, x)
+    _step_fused("unipc", eps, x, cfg, guidance, coef, step_idx, x_in, (state,), table, rowbias, timesteps_f32, t_out, ticket)
+
+
+def unipc_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, state, table, rowbias, timesteps_f32, t_out, ticket, x0, noise, mask,
+                            blend):
+    """unipc_step_fused followed by the inpainting blend (aldm_unipc_step_fused_masked); operands as ddim_step_fused_masked.  state
+    receives unblended values.  ticket None: eager, the counter stays (table must be None then)."""
+    _check_unipc_state(state, x)
+    _step_fused("unipc", eps, x, cfg, guidance, coef, step_idx, x_in, (state,), table, rowbias, timesteps_f32, t_out, ticket,
                 (x0, noise, mask, blend))
 
 

@@ -1,4 +1,4 @@
-"""DDIMScheduler, DPMSolverMultistepScheduler and EulerAncestralDiscreteScheduler for the HIP path (host-side integer logic + device step kernels).
+"""DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler and EulerAncestralDiscreteScheduler for the HIP path (host-side integer logic + device step kernels).
 
 Same surface the reference touches: `from_pretrained(id, subfolder="scheduler")`, `.config.num_train_timesteps`,
 `.add_noise` [REF script/train/train_audioldm_lora.py:367,503-504] and, through the pipeline,
@@ -7,6 +7,8 @@ Arithmetic spec: SURVEY.md Appendix B.1 (diffusers 0.32.2).  Timestep indices ar
 diffusers does ("leading" spacing, steps_offset); the fp32 alpha-bar table uses the same torch ops as diffusers.
 DPMSolverMultistepScheduler is diffusers 0.32.2's deterministic multistep solver, swapped in the way diffusers
 users do it: `pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)`.
+UniPCMultistepScheduler is diffusers 0.32.2's multistep predictor-corrector, swapped in the same way: the
+sampler for 5-10 steps.
 EulerAncestralDiscreteScheduler is diffusers 0.32.2's stochastic sampler, swapped in the same way; its per-step
 noise is drawn on the device by the step kernel itself (a Philox stream, ops.philox_state).
 """
@@ -161,18 +163,13 @@ DPM_CONFIG = dict(
 )
 
 
-class DPMSolverMultistepScheduler(_SuffixMixin):
-    """DPM-Solver / DPM-Solver++ (first or second order, deterministic), diffusers 0.32.2 arithmetic restated (DESIGN.md section 9).
+class _SigmaMultistepBase(_SuffixMixin):
+    """What DPMSolverMultistepScheduler and UniPCMultistepScheduler share, diffusers-identical between the two: the alpha-bar tables,
+    set_timesteps and the sigmas (three spacings, final sigma zero or sigma_min), index_for_timestep, add_noise and the begin index.
+    A subclass sets `self.config` and calls `_init_tables(cfg)`, and provides `_reset_solver()` (the multistep state a new schedule
+    drops)."""
 
-    `coefficient_table()` turns the whole schedule into fp32 rows {alpha_s, sig_s, A, B, C, convert, reads_hist, 0}; the device
-    update (aldm_dpm_step_fused) is then  m0 = convert ? (x - sig_s e) / alpha_s : e ;  x' = A x + B m0 + C (m0 - m1),  with m1 the
-    previous step's m0 (the history buffer) and 1 / r0 folded into C.  First-order rows have C = 0 and never read the history."""
-
-    def __init__(self, **over):
-        cfg = dict(DPM_CONFIG)
-        cfg.update({k: v for k, v in over.items() if k in DPM_CONFIG})
-        self.config = SimpleNamespace(**cfg)
-        self._check(cfg)
+    def _init_tables(self, cfg):
         n = cfg["num_train_timesteps"]
         self.betas = torch.linspace(cfg["beta_start"] ** 0.5, cfg["beta_end"] ** 0.5, n, dtype=torch.float32) ** 2
         self.alphas = 1.0 - self.betas
@@ -185,40 +182,8 @@ class DPMSolverMultistepScheduler(_SuffixMixin):
         self.num_inference_steps = None
         self.timesteps = torch.from_numpy(np.linspace(0, n - 1, n, dtype=np.float32)[::-1].copy().astype(np.int64))
         self._step_index = None
-        self._lower_order_nums = 0
-        self._hist = {}
+        self._reset_solver()
         self._dev = {}
-
-    @staticmethod
-    def _check(cfg):
-        alg = cfg["algorithm_type"]
-        if alg in ("sde-dpmsolver", "sde-dpmsolver++"):
-            raise NotImplementedError(f"algorithm_type={alg!r}: the SDE variants draw noise inside every step (not in the captured graph)")
-        if alg not in ("dpmsolver++", "dpmsolver"):
-            raise NotImplementedError(f"algorithm_type={alg!r}")
-        if cfg["solver_order"] not in (1, 2):
-            raise NotImplementedError(f"solver_order={cfg['solver_order']}: only first and second order are implemented")
-        if cfg["solver_type"] not in ("midpoint", "heun"):
-            raise NotImplementedError(f"solver_type={cfg['solver_type']!r}")
-        for k in ("thresholding", "use_karras_sigmas", "use_exponential_sigmas", "use_beta_sigmas", "use_lu_lambdas",
-                  "rescale_betas_zero_snr"):
-            if cfg[k]:
-                raise NotImplementedError(f"{k}=True")
-        if cfg["prediction_type"] != "epsilon":
-            raise NotImplementedError(f"prediction_type={cfg['prediction_type']!r}: only epsilon prediction is implemented")
-        if cfg["beta_schedule"] != "scaled_linear" or cfg["trained_betas"] is not None:
-            raise NotImplementedError(f"beta_schedule={cfg['beta_schedule']!r} / trained_betas: only scaled_linear is implemented")
-        if cfg["variance_type"] is not None:
-            raise NotImplementedError(f"variance_type={cfg['variance_type']!r}")
-        if cfg["lambda_min_clipped"] != -float("inf"):
-            raise NotImplementedError(f"lambda_min_clipped={cfg['lambda_min_clipped']}")
-        if cfg["timestep_spacing"] not in ("leading", "linspace", "trailing"):
-            raise NotImplementedError(f"timestep_spacing={cfg['timestep_spacing']!r}")
-        if cfg["final_sigmas_type"] not in ("zero", "sigma_min"):
-            raise NotImplementedError(f"final_sigmas_type={cfg['final_sigmas_type']!r}")
-        if alg == "dpmsolver" and cfg["final_sigmas_type"] == "zero":
-            raise ValueError(f"`final_sigmas_type` {cfg['final_sigmas_type']} is not supported for `algorithm_type` {alg}. "
-                             "Please choose `sigma_min` instead.")
 
     @classmethod
     def from_pretrained(cls, path, subfolder=None, **kw):
@@ -226,7 +191,7 @@ class DPMSolverMultistepScheduler(_SuffixMixin):
 
     @classmethod
     def from_config(cls, config, **over):
-        """dict or SimpleNamespace (e.g. DDIMScheduler's `.config`); keys this class does not know (clip_sample, ...) are ignored."""
+        """dict or SimpleNamespace (e.g. DDIMScheduler's `.config`); keys the class does not know (clip_sample, ...) are ignored."""
         return cls(**_config_dict(config, over))
 
     def scale_model_input(self, sample, *args, **kw):
@@ -261,13 +226,115 @@ class DPMSolverMultistepScheduler(_SuffixMixin):
         self.num_inference_steps = len(ts)
         self._step_index = None
         self._begin_index = None
-        self._lower_order_nums = 0
-        self._hist = {}
+        self._reset_solver()
 
     @staticmethod
     def _alpha_sigma(sigma):
         alpha_t = 1 / ((sigma ** 2 + 1) ** 0.5)
         return alpha_t, sigma * alpha_t
+
+    def add_noise_coefficients(self, i):
+        """fp32 (alpha, sigma) of sigmas[i]: what add_noise applies at schedule index i (diffusers' add_noise after set_begin_index(i))."""
+        return self._alpha_sigma(self.sigmas[i])
+
+    def set_begin_index(self, begin_index=0):
+        self._begin_index = begin_index
+
+    @property
+    def begin_index(self):
+        return getattr(self, "_begin_index", None)
+
+    def index_for_timestep(self, timestep):
+        """diffusers' index_for_timestep: the second match of `timestep` in the schedule when there are two, else the only one, else
+        the last index (a timestep outside the schedule)."""
+        cand = (self.timesteps.cpu() == int(timestep)).nonzero()
+        if len(cand) == 0:
+            return len(self.timesteps) - 1
+        return int(cand[1 if len(cand) > 1 else 0])
+
+    def add_noise_indices(self, timesteps):
+        """The schedule index add_noise uses for each timestep, in diffusers' order: with no begin index, index_for_timestep(t);
+        else, once a step has run, the current step index (add_noise after a step, the inpaint loop); else the begin index (the
+        initial latents of img2img).  Host-only."""
+        t = torch.as_tensor(timesteps).reshape(-1).cpu()
+        if self.begin_index is None:
+            return [self.index_for_timestep(tb) for tb in t.tolist()]
+        if self._step_index is not None:
+            return [self._step_index] * t.numel()
+        return [self.begin_index] * t.numel()
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' DPMSolverMultistepScheduler.add_noise (UniPCMultistepScheduler's is the same): alpha_t x + sigma_t noise, with
+        (alpha_t, sigma_t) the add_noise_coefficients of add_noise_indices(timesteps) -- one timestep per sample, or one for the whole batch.
+        Coefficients on the host, the multiply-add on the device (aldm_add_noise)."""
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() first")
+        B = original_samples.shape[0]
+        idx = self.add_noise_indices(timesteps)
+        if len(idx) == 1:
+            idx = idx * B
+        if len(idx) != B:
+            raise ValueError(f"add_noise: {len(idx)} timesteps for a batch of {B}")
+        coef = torch.stack([torch.stack(self.add_noise_coefficients(i)) for i in idx]).float().contiguous()
+        return ops.add_noise(original_samples, noise, coef.to(original_samples.device))
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def _init_step_index(self, timestep):
+        # diffusers: a schedule begun with set_begin_index starts there, else at the timestep's index
+        self._step_index = self.index_for_timestep(timestep) if self.begin_index is None else self.begin_index
+
+
+class DPMSolverMultistepScheduler(_SigmaMultistepBase):
+    """DPM-Solver / DPM-Solver++ (first or second order, deterministic), diffusers 0.32.2 arithmetic restated (DESIGN.md section 9).
+
+    `coefficient_table()` turns the whole schedule into fp32 rows {alpha_s, sig_s, A, B, C, convert, reads_hist, 0}; the device
+    update (aldm_dpm_step_fused) is then  m0 = convert ? (x - sig_s e) / alpha_s : e ;  x' = A x + B m0 + C (m0 - m1),  with m1 the
+    previous step's m0 (the history buffer) and 1 / r0 folded into C.  First-order rows have C = 0 and never read the history."""
+
+    def __init__(self, **over):
+        cfg = dict(DPM_CONFIG)
+        cfg.update({k: v for k, v in over.items() if k in DPM_CONFIG})
+        self.config = SimpleNamespace(**cfg)
+        self._check(cfg)
+        self._init_tables(cfg)
+
+    @staticmethod
+    def _check(cfg):
+        alg = cfg["algorithm_type"]
+        if alg in ("sde-dpmsolver", "sde-dpmsolver++"):
+            raise NotImplementedError(f"algorithm_type={alg!r}: the SDE variants draw noise inside every step (not in the captured graph)")
+        if alg not in ("dpmsolver++", "dpmsolver"):
+            raise NotImplementedError(f"algorithm_type={alg!r}")
+        if cfg["solver_order"] not in (1, 2):
+            raise NotImplementedError(f"solver_order={cfg['solver_order']}: only first and second order are implemented")
+        if cfg["solver_type"] not in ("midpoint", "heun"):
+            raise NotImplementedError(f"solver_type={cfg['solver_type']!r}")
+        for k in ("thresholding", "use_karras_sigmas", "use_exponential_sigmas", "use_beta_sigmas", "use_lu_lambdas",
+                  "rescale_betas_zero_snr"):
+            if cfg[k]:
+                raise NotImplementedError(f"{k}=True")
+        if cfg["prediction_type"] != "epsilon":
+            raise NotImplementedError(f"prediction_type={cfg['prediction_type']!r}: only epsilon prediction is implemented")
+        if cfg["beta_schedule"] != "scaled_linear" or cfg["trained_betas"] is not None:
+            raise NotImplementedError(f"beta_schedule={cfg['beta_schedule']!r} / trained_betas: only scaled_linear is implemented")
+        if cfg["variance_type"] is not None:
+            raise NotImplementedError(f"variance_type={cfg['variance_type']!r}")
+        if cfg["lambda_min_clipped"] != -float("inf"):
+            raise NotImplementedError(f"lambda_min_clipped={cfg['lambda_min_clipped']}")
+        if cfg["timestep_spacing"] not in ("leading", "linspace", "trailing"):
+            raise NotImplementedError(f"timestep_spacing={cfg['timestep_spacing']!r}")
+        if cfg["final_sigmas_type"] not in ("zero", "sigma_min"):
+            raise NotImplementedError(f"final_sigmas_type={cfg['final_sigmas_type']!r}")
+        if alg == "dpmsolver" and cfg["final_sigmas_type"] == "zero":
+            raise ValueError(f"`final_sigmas_type` {cfg['final_sigmas_type']} is not supported for `algorithm_type` {alg}. "
+                             "Please choose `sigma_min` instead.")
+
+    def _reset_solver(self):
+        self._lower_order_nums = 0
+        self._hist = {}
 
     def row_order(self, i):
         """Solver order of step i of the schedule (diffusers' step(): the first step and, under the final-step rules, the last one
@@ -317,59 +384,6 @@ class DPMSolverMultistepScheduler(_SuffixMixin):
             raise ValueError(f"begin_index {begin_index} outside the schedule of {N} steps")
         return torch.stack([self.step_coefficients(i, 1 if i == begin_index else None) for i in range(begin_index, N)])
 
-    def add_noise_coefficients(self, i):
-        """fp32 (alpha, sigma) of sigmas[i]: what add_noise applies at schedule index i (diffusers' add_noise after set_begin_index(i))."""
-        return self._alpha_sigma(self.sigmas[i])
-
-    def set_begin_index(self, begin_index=0):
-        self._begin_index = begin_index
-
-    @property
-    def begin_index(self):
-        return getattr(self, "_begin_index", None)
-
-    def index_for_timestep(self, timestep):
-        """diffusers' index_for_timestep: the second match of `timestep` in the schedule when there are two, else the only one, else
-        the last index (a timestep outside the schedule)."""
-        cand = (self.timesteps.cpu() == int(timestep)).nonzero()
-        if len(cand) == 0:
-            return len(self.timesteps) - 1
-        return int(cand[1 if len(cand) > 1 else 0])
-
-    def add_noise_indices(self, timesteps):
-        """The schedule index add_noise uses for each timestep, in diffusers' order: with no begin index, index_for_timestep(t);
-        else, once a step has run, the current step index (add_noise after a step, the inpaint loop); else the begin index (the
-        initial latents of img2img).  Host-only."""
-        t = torch.as_tensor(timesteps).reshape(-1).cpu()
-        if self.begin_index is None:
-            return [self.index_for_timestep(tb) for tb in t.tolist()]
-        if self._step_index is not None:
-            return [self._step_index] * t.numel()
-        return [self.begin_index] * t.numel()
-
-    def add_noise(self, original_samples, noise, timesteps):
-        """diffusers' DPMSolverMultistepScheduler.add_noise: alpha_t x + sigma_t noise, with (alpha_t, sigma_t) the
-        add_noise_coefficients of add_noise_indices(timesteps) -- one timestep per sample, or one for the whole batch.
-        Coefficients on the host, the multiply-add on the device (aldm_add_noise)."""
-        if self.num_inference_steps is None:
-            raise ValueError("call set_timesteps() first")
-        B = original_samples.shape[0]
-        idx = self.add_noise_indices(timesteps)
-        if len(idx) == 1:
-            idx = idx * B
-        if len(idx) != B:
-            raise ValueError(f"add_noise: {len(idx)} timesteps for a batch of {B}")
-        coef = torch.stack([torch.stack(self.add_noise_coefficients(i)) for i in idx]).float().contiguous()
-        return ops.add_noise(original_samples, noise, coef.to(original_samples.device))
-
-    @property
-    def step_index(self):
-        return self._step_index
-
-    def _init_step_index(self, timestep):
-        # diffusers: a schedule begun with set_begin_index starts there, else at the timestep's index
-        self._step_index = self.index_for_timestep(timestep) if self.begin_index is None else self.begin_index
-
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, **kw):
         """x at the next timestep from eps via the device kernel (aldm_dpm_step_fused, eager mode); fp32 tensors of any layout.
         The previous step's converted output stays on the device, one history tensor per sample shape."""
@@ -391,6 +405,204 @@ class DPMSolverMultistepScheduler(_SuffixMixin):
         idx = self._dev.setdefault(("zero", dev), torch.zeros(1, dtype=torch.int32, device=dev))
         ops.dpm_step_fused(model_output.detach().float().contiguous(), x, False, 0.0, coef, idx, None, hist)
         if self._lower_order_nums < self.config.solver_order:
+            self._lower_order_nums += 1
+        self._step_index += 1
+        prev = x.to(sample.dtype)
+        if not return_dict:
+            return (prev,)
+        return SimpleNamespace(prev_sample=prev)
+
+
+# diffusers 0.32.2 UniPCMultistepScheduler defaults for the solver keys; the keys it shares with DDIMScheduler default to the AudioLDM
+# scheduler configuration, as the other classes' do here
+UNIPC_CONFIG = dict(
+    num_train_timesteps=SCHEDULER["num_train_timesteps"], beta_start=SCHEDULER["beta_start"], beta_end=SCHEDULER["beta_end"],
+    beta_schedule=SCHEDULER["beta_schedule"], trained_betas=None, solver_order=2, prediction_type=SCHEDULER["prediction_type"],
+    thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0, predict_x0=True, solver_type="bh2",
+    lower_order_final=True, disable_corrector=[], solver_p=None, use_karras_sigmas=False, use_exponential_sigmas=False,
+    use_beta_sigmas=False, timestep_spacing=SCHEDULER["timestep_spacing"], steps_offset=SCHEDULER["steps_offset"],
+    final_sigmas_type="zero", rescale_betas_zero_snr=False,
+)
+UNIPC_ROW = 16
+
+
+class UniPCMultistepScheduler(_SigmaMultistepBase):
+    """UniPC (a multistep predictor plus a corrector that reuses the next step's model output; orders 1 and 2, bh1 / bh2), diffusers
+    0.32.2 arithmetic for epsilon prediction restated.  The sampler for 5-10 steps; at 20 and more it is within
+    a factor of about 1.5 of DPM-Solver++ 2M either way.
+
+    `coefficient_table()` turns the whole schedule into fp32 rows of UNIPC_ROW floats
+        {alpha_s, sig_s, Ac, Bc, Cc, Dc, Ap, Bp, Cp, convert, corr, corr_reads_m1, pred_reads_m0, 0, 0, 0}
+    and the device update (aldm_unipc_step_fused) is then
+        m_t = convert ? (x - sig_s e) / alpha_s : e
+        xc  = corr ? Ac last + Bc m0 + Cc (m1 - m0) + Dc (m_t - m0) : x
+        x'  = Ap xc + Bp m_t + Cp (m_t - m0)
+    with m0, m1 the previous two converted outputs and `last` the previous step's corrected sample; 1 / rk, rhos, B_h and h_phi_1 are
+    folded into the six coefficients.  The predictor's difference is written (m_t - m0), new minus old as in the DPM class's row, so
+    that with the corrector off {Ap, Bp, Cp} IS DPM-Solver++ 2M midpoint's {A, B, C}; diffusers writes -(Cp) (m0 - m_t).  As in
+    diffusers, m_t converts the UNCORRECTED sample, the corrector starts from `last` (not from the sample passed in), its result is
+    what the predictor starts from and what becomes the new `last`, and the output list receives m_t after the corrector read it."""
+
+    def __init__(self, **over):
+        cfg = dict(UNIPC_CONFIG)
+        cfg.update({k: v for k, v in over.items() if k in UNIPC_CONFIG})
+        cfg["disable_corrector"] = [int(v) for v in (cfg["disable_corrector"] or [])]
+        if cfg["solver_type"] in ("midpoint", "heun", "logrho"):      # diffusers: another solver's type (a DPM config) becomes bh2
+            cfg["solver_type"] = "bh2"
+        self.config = SimpleNamespace(**cfg)
+        self._check(cfg)
+        self._init_tables(cfg)
+
+    @staticmethod
+    def _check(cfg):
+        if cfg["solver_order"] not in (1, 2):
+            raise NotImplementedError(f"solver_order={cfg['solver_order']}: only first and second order are implemented")
+        if cfg["solver_type"] not in ("bh1", "bh2"):
+            raise NotImplementedError(f"solver_type={cfg['solver_type']!r}")
+        for k in ("thresholding", "use_karras_sigmas", "use_exponential_sigmas", "use_beta_sigmas", "rescale_betas_zero_snr"):
+            if cfg[k]:
+                raise NotImplementedError(f"{k}=True")
+        if cfg["solver_p"] is not None:
+            raise NotImplementedError("solver_p: another scheduler as the predictor is not implemented")
+        if cfg["prediction_type"] != "epsilon":
+            raise NotImplementedError(f"prediction_type={cfg['prediction_type']!r}: only epsilon prediction is implemented")
+        if cfg["beta_schedule"] != "scaled_linear" or cfg["trained_betas"] is not None:
+            raise NotImplementedError(f"beta_schedule={cfg['beta_schedule']!r} / trained_betas: only scaled_linear is implemented")
+        if cfg["timestep_spacing"] not in ("leading", "linspace", "trailing"):
+            raise NotImplementedError(f"timestep_spacing={cfg['timestep_spacing']!r}")
+        if cfg["final_sigmas_type"] not in ("zero", "sigma_min"):
+            raise NotImplementedError(f"final_sigmas_type={cfg['final_sigmas_type']!r}")
+        if cfg["final_sigmas_type"] == "zero":
+            if not cfg["predict_x0"]:
+                raise ValueError("`final_sigmas_type` zero is not supported for `predict_x0` False (the noise-prediction update of the "
+                                 "step to sigma 0 is 0 * inf). Please choose `sigma_min` instead.")
+            if cfg["solver_order"] == 2 and not cfg["lower_order_final"]:
+                raise ValueError("`lower_order_final` False with `solver_order` 2 and `final_sigmas_type` zero makes the step to sigma 0 "
+                                 "second order, which divides by rk = -0. Set `lower_order_final` or choose `sigma_min`.")
+
+    def _reset_solver(self):
+        self._lower_order_nums = 0
+        self._this_order = 0          # the predictor order of the step before (the corrector's order)
+        self._state = {}              # (shape, device) -> [state fp32 [3, *shape], steps taken]
+
+    def row_order(self, i, begin_index=0):
+        """Predictor order of step i of a schedule begun at begin_index: min(solver_order, N - i) under lower_order_final (judged on
+        the full N), capped by the warm-up (lower_order_nums + 1 = i - begin_index + 1).  The corrector of step i uses
+        row_order(i - 1)."""
+        cfg, N = self.config, len(self.timesteps)
+        order = min(cfg.solver_order, N - i) if cfg.lower_order_final else cfg.solver_order
+        return min(order, i - begin_index + 1)
+
+    def uses_corrector(self, i, begin_index=0):
+        """whether step i corrects the sample it is given: not on the first step of the loop (no previous sample), and not where
+        disable_corrector names the step before"""
+        return i > begin_index and (i - 1) not in self.config.disable_corrector
+
+    def _lambda(self, i):
+        alpha, sigma = self._alpha_sigma(self.sigmas[i])
+        return alpha, sigma, torch.log(alpha) - torch.log(sigma)
+
+    def _bh(self, h):
+        """(h_phi_1, B_h, hh) of a step of log-SNR length h"""
+        hh = -h if self.config.predict_x0 else h
+        h_phi_1 = torch.expm1(hh)
+        return h_phi_1, (hh if self.config.solver_type == "bh1" else torch.expm1(hh)), hh
+
+    def step_coefficients(self, i, order=None, corrector_order=None):
+        """fp32 row of step i, from diffusers' fp32 scalar torch ops.  order: the predictor's (default row_order(i));
+        corrector_order: 0 for none, else 1 or 2 (default: row_order(i - 1) where uses_corrector(i))."""
+        order = self.row_order(i) if order is None else order
+        if corrector_order is None:
+            corrector_order = self.row_order(i - 1) if self.uses_corrector(i) else 0
+        x0 = self.config.predict_x0
+        zero, one = torch.zeros((), dtype=torch.float32), torch.ones((), dtype=torch.float32)
+        alpha_s0, sigma_s0, lambda_s0 = self._lambda(i)
+        # ---- predictor: from sigmas[i] to sigmas[i + 1] ----
+        alpha_t, sigma_t, lambda_t = self._lambda(i + 1)
+        if float(self.sigmas[i + 1]) == 0.0:          # x' = m_t exactly (h = +inf: h_phi_1 = -1, alpha_t = 1); order 1 by _check
+            Ap, Bp, Cp = zero, one, zero
+        else:
+            h = lambda_t - lambda_s0
+            h_phi_1, B_h, _ = self._bh(h)
+            scale = alpha_t if x0 else sigma_t
+            Ap = sigma_t / sigma_s0 if x0 else alpha_t / alpha_s0
+            Bp = -(scale * h_phi_1)
+            Cp = zero
+            if order == 2:
+                rk = (self._lambda(i - 1)[2] - lambda_s0) / h
+                Cp = scale * B_h * 0.5 / rk           # rhos_p = 0.5; -(.) (m0 - m_t) / rk written as (.) (m_t - m0)
+        # ---- corrector: redoes the step from sigmas[i - 1] to sigmas[i] with this step's model output ----
+        Ac = Bc = Cc = Dc = zero
+        if corrector_order:
+            alpha_p, sigma_p, lambda_p = self._lambda(i - 1)
+            h = lambda_s0 - lambda_p
+            h_phi_1, B_h, hh = self._bh(h)
+            scale = alpha_s0 if x0 else sigma_s0
+            Ac = sigma_s0 / sigma_p if x0 else alpha_s0 / alpha_p
+            Bc = -(scale * h_phi_1)
+            if corrector_order == 1:
+                Dc = -(scale * B_h * 0.5)             # rhos_c = [0.5]
+            else:
+                rk = (self._lambda(i - 2)[2] - lambda_p) / h
+                rks = torch.stack([rk, one])
+                h_phi_k = h_phi_1 / hh - 1
+                b1 = h_phi_k / B_h
+                b2 = (h_phi_k / hh - 1 / 2) * 2 / B_h
+                rhos_c = torch.linalg.solve(torch.stack([torch.pow(rks, 0), torch.pow(rks, 1)]), torch.stack([b1, b2]))
+                Cc = -(scale * B_h * rhos_c[0] / rk)
+                Dc = -(scale * B_h * rhos_c[1])
+        flags = [one if x0 else zero, one if corrector_order else zero, one if corrector_order == 2 else zero, one if order == 2 else zero]
+        return torch.stack([alpha_s0, sigma_s0, Ac, Bc, Cc, Dc, Ap, Bp, Cp, *flags, zero, zero, zero]).float()
+
+    def coefficient_table(self, begin_index=0):
+        """rows of the schedule from step begin_index on.  A begun schedule starts with an empty history (diffusers: lower_order_nums
+        = 0, last_sample = None), so its first row has no corrector and a first-order predictor; the final-step rule is judged on the
+        full N."""
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() first")
+        N = len(self.timesteps)
+        if not 0 <= begin_index < N:
+            raise ValueError(f"begin_index {begin_index} outside the schedule of {N} steps")
+        rows = []
+        for i in range(begin_index, N):
+            corr = self.row_order(i - 1, begin_index) if self.uses_corrector(i, begin_index) else 0
+            rows.append(self.step_coefficients(i, self.row_order(i, begin_index), corr))
+        return torch.stack(rows)
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, **kw):
+        """x at the next timestep from eps via the device kernel (aldm_unipc_step_fused, eager mode); fp32 tensors of any layout.
+        The last corrected sample and the previous two converted outputs stay on the device, one state tensor per sample shape;
+        the kernel's ring turns on the parity of the counter it is given, which alternates here between two one-word tensors."""
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() first")
+        dev = sample.device
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        i = self._step_index
+        x = sample.detach().float().contiguous().clone()
+        e = model_output.detach().float().contiguous()
+        ops._require_gpu(x)
+        key = (tuple(x.shape), dev)
+        st = self._state.get(key)
+        corr = self._this_order if (i > 0 and (i - 1) not in self.config.disable_corrector and st is not None) else 0
+        cfg, N = self.config, len(self.timesteps)
+        order = min(cfg.solver_order, N - i) if cfg.lower_order_final else cfg.solver_order
+        order = min(order, self._lower_order_nums + 1)
+        if st is None:
+            if order == 2:
+                raise ValueError(f"step(): no previous model output for a sample of shape {tuple(x.shape)}")
+            st = self._state[key] = [torch.zeros((3, *x.shape), dtype=torch.float32, device=dev), 0]
+        if st[1] < max(order - 1, corr):
+            raise ValueError(f"step(): {st[1]} previous model outputs for a sample of shape {tuple(x.shape)}, the step needs more")
+        row = self.step_coefficients(i, order, corr).to(dev)
+        coef = torch.stack([row, row])
+        idx = self._dev.get(("parity", dev))
+        if idx is None:
+            idx = self._dev[("parity", dev)] = [torch.full((1,), v, dtype=torch.int32, device=dev) for v in (0, 1)]
+        ops.unipc_step_fused(e, x, False, 0.0, coef, idx[st[1] & 1], None, st[0])
+        st[1] += 1
+        self._this_order = order
+        if self._lower_order_nums < cfg.solver_order:
             self._lower_order_nums += 1
         self._step_index += 1
         prev = x.to(sample.dtype)

@@ -7,6 +7,7 @@ writes a wav.  LoRA stays un-merged and is applied inside the fused projection G
 Defaults follow the script: r=2, 50 DDIM steps, 10 s, guidance 5.0; alpha defaults to the TRAINED value 2 rather than the
 script's inconsistent 4 (quirk Q3) -- pass --lora-alpha 4 to reproduce the script literally.
 `--scheduler dpmsolver++ --steps 25` swaps in DPMSolverMultistepScheduler (from the checkpoint's scheduler config) instead of DDIM.
+`--scheduler unipc --steps 8` swaps in UniPCMultistepScheduler (predictor-corrector, the sampler for 5-10 steps; `--solver-order` applies).
 `--scheduler euler-a` swaps in EulerAncestralDiscreteScheduler (stochastic: fresh noise in every step, drawn on the device); `--seed` then
 seeds both the initial noise and that in-loop stream.
 `--init-audio in.wav --strength 0.5` starts from a 16 kHz recording (AudioLDMAudioToAudioPipeline: style transfer toward the prompt);
@@ -24,7 +25,7 @@ import torch
 from ..lora import LoraConfig, get_peft_model
 from ..audio2audio import AudioLDMAudioToAudioPipeline, regeneration_mask
 from ..pipeline import AudioLDMPipeline
-from ..scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
+from ..scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, UniPCMultistepScheduler
 from ..unet import UNet2DConditionModel
 
 
@@ -67,10 +68,11 @@ def main(argv=None):
     ap.add_argument("--target-modules", default="to_q,to_v")
     ap.add_argument("--prompt", default="An instrumental hip-hop track in the subgenre of boom bap")
     ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--scheduler", choices=["ddim", "dpmsolver++", "dpmsolver", "euler-a"], default="ddim",
+    ap.add_argument("--scheduler", choices=["ddim", "dpmsolver++", "dpmsolver", "unipc", "euler-a"], default="ddim",
                     help="sampler: the reference's DDIM (default) or diffusers' DPMSolverMultistepScheduler from the same config "
-                         "(dpmsolver uses final_sigmas_type='sigma_min'), or its EulerAncestralDiscreteScheduler (euler-a)")
-    ap.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="DPM-Solver order (ignored with --scheduler ddim / euler-a)")
+                         "(dpmsolver uses final_sigmas_type='sigma_min'), its UniPCMultistepScheduler (unipc: predictor-corrector, for 5-10 "
+                         "steps), or its EulerAncestralDiscreteScheduler (euler-a)")
+    ap.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="DPM-Solver / UniPC order (ignored with --scheduler ddim / euler-a)")
     ap.add_argument("--audio-length", type=float, default=None, help="seconds (default 10, or the --init-audio clip's length)")
     ap.add_argument("--guidance-scale", type=float, default=5.0)
     ap.add_argument("--output", default="./generated_audio_LoRA/ex.wav")
@@ -101,6 +103,8 @@ def main(argv=None):
     pipe = AudioLDMPipeline.from_pretrained(args.model_dir, unet=unet).to(device)
     if args.scheduler == "euler-a":
         pipe.scheduler = EulerAncestralDiscreteScheduler.from_config(pipe.scheduler.config)
+    elif args.scheduler == "unipc":
+        pipe.scheduler = UniPCMultistepScheduler.from_config(pipe.scheduler.config, solver_order=args.solver_order)
     elif args.scheduler != "ddim":
         extra = {"final_sigmas_type": "sigma_min"} if args.scheduler == "dpmsolver" else {}
         pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, algorithm_type=args.scheduler,

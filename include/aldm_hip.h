@@ -467,6 +467,24 @@ int aldm_euler_a_step_fused_masked(const float* eps, float* x, int B, long long 
                                    int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table, long long row_elems,
                                    float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0,
                                    const float* noise, const float* mask, const float* blend, int channels, void* stream);
+/* classifier-free guidance + UniPC multistep predictor-corrector update (orders 1 and 2, bh1 / bh2), the loop body of
+   AudioLDMPipeline.__call__ [REF script/inference/generate_audio.py:47-52] with diffusers' UniPCMultistepScheduler swapped in:
+     e = cfg ? eu + g (et - eu) : eu ;  m_t = convert ? (x - sig_s e) / alpha_s : e
+     xc = corr ? Ac last + Bc m0 + Cc (m1 - m0) + Dc (m_t - m0) : x ;  x' = Ap xc + Bp m_t + Cp (m_t - m0)
+   coef: device fp32 table [n_steps][16] = {alpha_s, sig_s, Ac, Bc, Cc, Dc, Ap, Bp, Cp, convert, corr, corr_reads_m1, pred_reads_m0,
+   0, 0, 0}, the row selected ON DEVICE by step_idx[0].  state fp32 [3][B][n]: plane 0 = last (the corrected sample xc, stored by every
+   step), planes 1 and 2 = the two previous m_t as a ring: step c reads m0 from plane 1 + ((c - 1) & 1) and m1 from plane 1 + (c & 1),
+   then stores m_t over m1 (c = step_idx[0]).  A plane is read only where the row's flags ask for it.  Counter, next time-embedding
+   row and ticket as in aldm_ddim_step_fused; ticket == NULL leaves step_idx alone (eager step: table NULL, timesteps/t_out unused;
+   the caller alternates step_idx[0] between 0 and 1 to turn the ring).  The masked form applies the inpainting blend of
+   aldm_ddim_step_fused_masked to x' only: state receives unblended values. */
+int aldm_unipc_step_fused(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                          int* step_idx, void* x_in_bf16, float* state, const float* table, long long row_elems, float* rowbias,
+                          const float* timesteps, int n_steps, float* t_out, unsigned* ticket, void* stream);
+int aldm_unipc_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                 int* step_idx, void* x_in_bf16, float* state, const float* table, long long row_elems, float* rowbias,
+                                 const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0, const float* noise,
+                                 const float* mask, const float* blend, int channels, void* stream);
 /* measurement aid: keeps `stream` busy for ~us microseconds so that later launches queue up behind it (bench.py) */
 int aldm_sleep_us(int us, void* stream);
 /* device-side loop counter for graph replay: step_idx[0] = (step_idx[0] + 1) mod n_steps ; t_out[0] = timesteps[step_idx[0]] */

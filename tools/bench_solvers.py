@@ -1,6 +1,7 @@
 """Times one real `pipe(...)` call per sampler at config 2 (4 prompts x 10 s, CFG 2.5, rank-4 LoRA, random-init weights), built the
 way bench.py's end-to-end leg builds it: DDIM-200 (the reference app's call), DDIM-25, DPM-Solver++-25 (second order,
-DPMSolverMultistepScheduler.from_config of the DDIM config) and Euler-ancestral-25 (EulerAncestralDiscreteScheduler.from_config; its
+DPMSolverMultistepScheduler.from_config of the DDIM config), UniPC-25 and UniPC-8 (UniPCMultistepScheduler.from_config: the predictor-corrector,
+meant for 5-10 steps) and Euler-ancestral-25 (EulerAncestralDiscreteScheduler.from_config; its
 per-step noise is drawn inside the fused step launch).  One pipeline object; the scheduler is swapped between variants.
 
     python tools/bench_solvers.py [--repeats 3]
@@ -39,7 +40,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     args = ap.parse_args()
     from audioldm_with_lora_amd.pipeline import AudioLDMPipeline
-    from audioldm_with_lora_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
+    from audioldm_with_lora_amd.scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
+                                                    UniPCMultistepScheduler)
     from audioldm_with_lora_amd.vae import AutoencoderKL
     from audioldm_with_lora_amd.vocoder import SpeechT5HifiGan
     batch, seconds, guidance = 4, 10.0, 2.5
@@ -54,6 +56,8 @@ def main():
     variants = [("ddim_200", DDIMScheduler.from_config(ddim_cfg), 200),
                 ("ddim_25", DDIMScheduler.from_config(ddim_cfg), 25),
                 ("dpmsolver++_25", DPMSolverMultistepScheduler.from_config(ddim_cfg), 25),
+                ("unipc_25", UniPCMultistepScheduler.from_config(ddim_cfg), 25),
+                ("unipc_8", UniPCMultistepScheduler.from_config(ddim_cfg), 8),
                 ("euler-a_25", EulerAncestralDiscreteScheduler.from_config(ddim_cfg), 25)]
     res = {}
     for name, sched, n in variants:
