@@ -84,6 +84,15 @@ class PgemmArgs(C.Structure):
     ]
 
 
+class WindowPlanArgs(C.Structure):
+    """Mirror of aldm_window_plan_t (include/aldm_hip.h) -- field order and types must match exactly."""
+    _fields_ = [
+        ("offset", C.c_void_p), ("cover", C.c_void_p), ("weight", C.c_void_p),
+        ("K", C.c_int), ("KC", C.c_int), ("rows", C.c_int), ("hw", C.c_int),
+        ("offset_elems", C.c_longlong), ("cover_elems", C.c_longlong), ("weight_elems", C.c_longlong),
+    ]
+
+
 # name -> (restype, argtypes): every symbol include/aldm_hip.h declares
 PROTOTYPES = {
     "aldm_version": (C.c_char_p, []),
@@ -190,6 +199,8 @@ PROTOTYPES = {
     "aldm_gaussian_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "aldm_train_noise_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aldm_window_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_void_p, C.c_int, C.POINTER(WindowPlanArgs), C.c_void_p]),
+    "aldm_window_blend": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.POINTER(WindowPlanArgs), C.c_void_p]),
     "aldm_sleep_us": (C.c_int, [C.c_int, C.c_void_p]),
     "aldm_gather_row": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "aldm_advance_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -226,6 +237,8 @@ _STEP_INPAINT = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 for _solver, _operand in (("ddim", []), ("dpm", [C.c_void_p]), ("euler_a", [C.c_void_p]), ("unipc", [C.c_void_p])):
     PROTOTYPES[f"aldm_{_solver}_step_fused"] = (C.c_int, _STEP_HEAD + _operand + _STEP_TAIL + [C.c_void_p])
     PROTOTYPES[f"aldm_{_solver}_step_fused_masked"] = (C.c_int, _STEP_HEAD + _operand + _STEP_TAIL + _STEP_INPAINT + [C.c_void_p])
+    # the windowed steps (long-form generation): the unmasked list, then the window plan
+    PROTOTYPES[f"aldm_{_solver}_step_fused_windowed"] = (C.c_int, _STEP_HEAD + _operand + _STEP_TAIL + [C.POINTER(WindowPlanArgs), C.c_void_p])
 
 _lib = None
 

@@ -291,6 +291,71 @@ struct UniPCSolver {
   __device__ __forceinline__ void advance() {}
 };
 
+// Windowed denoising (long-form generation): the latent x [B][rows][wc] (wc = W * C floats per row) is LONG, the
+// UNet ran on K windows of hw rows each as batch rows, and three small read-only tables say how they lie (longform.py WindowPlan):
+//   offset[K]         the long row of window k's row 0; window k's row i is long row (offset[k] + i) mod rows
+//   cover[rows][KC]   the windows over long row r, ascending, -1 behind the last
+//   weight[rows][KC]  their blend weights (positive, sum 1)
+// Window k of clip b is batch row b * K + k: eps [half][b][k][hw][wc] and the next UNet input x_in have that layout.  The tables are
+// plain device memory, never written by a launch that reads them; an entry outside [0, K) or a row outside the window ends the
+// row's list, so no table content can send an access out of bounds.
+constexpr int WIN_MAX_COVER = 4;
+
+struct Windows {
+  const int* offset;
+  const int* cover;
+  const float* weight;
+  int K, KC, rows, hw;
+  long long wc;
+};
+
+// the element offset of long row r (column c of clip b) inside window k's batch row, or -1 where the window does not hold it
+__device__ __forceinline__ long long window_elem(const Windows& w, long long b, int r, long long c, int k) {
+  if (k < 0 || k >= w.K) return -1;
+  int i = r - w.offset[k];
+  if (i < 0) i += w.rows;
+  if (i < 0 || i >= w.hw) return -1;
+  return ((b * w.K + k) * w.hw + i) * w.wc + c;
+}
+
+// One long row's blend of VEC consecutive elements: e = weight[r][0] win_0, then e = fma(weight[r][j], win_j, e) for j = 1 .. in table
+// order -- THE order of the contract (a single window of weight 1.0 returns its element bit for bit; the product is rounded on its
+// own, never contracted into the caller's arithmetic).  `base[j]` receives window j's element offset (-1 from the end of the list on).
+template <int VEC>
+__device__ __forceinline__ void window_blend_row(const Windows& w, const float* __restrict__ src, const float* __restrict__ src2,
+                                                 long long b, int r, long long c, long long (&base)[WIN_MAX_COVER], fvec_t<VEC>& e,
+                                                 fvec_t<VEC>& e2) {
+  typedef fvec_t<VEC> fvec;
+  const int* cv = w.cover + (long long)r * w.KC;
+  const float* wt = w.weight + (long long)r * w.KC;
+  bool live = true;
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) e[k] = 0.f, e2[k] = 0.f;
+#pragma unroll
+  for (int j = 0; j < WIN_MAX_COVER; ++j) {
+    base[j] = -1;
+    if (live && j < w.KC) base[j] = window_elem(w, b, r, c, cv[j]);
+    live = base[j] >= 0;
+    if (live) {
+      const float wj = wt[j];
+      const fvec v = *reinterpret_cast<const fvec*>(src + base[j]);
+      fvec v2 = v;
+      if (src2) v2 = *reinterpret_cast<const fvec*>(src2 + base[j]);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        if (j == 0) {
+#pragma clang fp contract(off)
+          e[k] = wj * v[k];
+          e2[k] = wj * v2[k];
+        } else {
+          e[k] = fmaf(wj, v[k], e[k]);
+          e2[k] = fmaf(wj, v2[k], e2[k]);
+        }
+      }
+    }
+  }
+}
+
 // The whole per-step bookkeeping of the replayed denoise loop as ONE launch behind the UNet: classifier-free guidance + the solver's
 // update (DDIM: as cfg_ddim_step_kernel), the inpainting blend after it (MASKED, see inpaint_blend), the bf16 input of the next UNet
 // call, the NEXT step's row of the precomputed time-embedding table gathered into `rowbias`, and the device-side step counter
@@ -302,12 +367,14 @@ struct UniPCSolver {
 // first dependent load needs; the unmasked ones carry no inpainting operand) and instantiate this frame with their solver.  They form
 // the thread index `tix` themselves: read in here, blockDim.x is not folded to the uniform workgroup size, and every wave starts with
 // one more dependent load.
-template <class Solver, int VEC, bool MASKED>
+// WINDOWED (the four *_windowed kernels further down): eps and x_in are per window, x and the solver's state long (Windows above).
+template <class Solver, int VEC, bool MASKED, bool WINDOWED = false>
 __device__ __forceinline__ void step_fused_body(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg, float g,
                                                 const float* __restrict__ coef, int* __restrict__ step_idx, bf16* __restrict__ x_in,
                                                 Solver s, const float* __restrict__ table, long long row_elems, float* __restrict__ rowbias,
                                                 const float* __restrict__ timesteps, int n_steps, float* __restrict__ t_out,
-                                                unsigned* __restrict__ ticket, long long tix, const Inpaint& ip) {
+                                                unsigned* __restrict__ ticket, long long tix, const Inpaint& ip,
+                                                const Windows& win = Windows{}) {
   typedef fvec_t<VEC> fvec;
   typedef bf16 bvec __attribute__((ext_vector_type(VEC)));
   const int cur = step_idx[0];
@@ -318,8 +385,17 @@ __device__ __forceinline__ void step_fused_body(const float* __restrict__ eps, f
   const long long total = (long long)B * n;
   if (idx < total) {
     // (the operands do not depend on the counter: requested before the coefficient row, which does)
-    fvec eu = *reinterpret_cast<const fvec*>(eps + idx), et = eu;
-    if (cfg) et = *reinterpret_cast<const fvec*>(eps + total + idx);
+    fvec eu, et;
+    long long wbase[WIN_MAX_COVER];
+    if constexpr (WINDOWED) {
+      // x, the solver's state and idx stay in the long layout; eps is per window: both halves blended into the long row first
+      const long long pix = idx / win.wc, b = pix / win.rows;
+      window_blend_row<VEC>(win, eps, cfg ? eps + (long long)B * win.K * win.hw * win.wc : nullptr, b, (int)(pix - b * win.rows),
+                            idx - pix * win.wc, wbase, eu, et);
+    } else {
+      eu = *reinterpret_cast<const fvec*>(eps + idx), et = eu;
+      if (cfg) et = *reinterpret_cast<const fvec*>(eps + total + idx);
+    }
     const fvec xv = *reinterpret_cast<const fvec*>(x + idx);
     fvec kx0, knz;
     if constexpr (MASKED) {
@@ -339,7 +415,17 @@ __device__ __forceinline__ void step_fused_body(const float* __restrict__ eps, f
     }
     *reinterpret_cast<fvec*>(x + idx) = xn;
     s.template store<VEC>(idx);
-    if (x_in) {
+    if constexpr (WINDOWED) {
+      // the next UNet input goes into EVERY window that holds this row, both CFG halves
+      if (x_in) {
+#pragma unroll
+        for (int j = 0; j < WIN_MAX_COVER; ++j)
+          if (wbase[j] >= 0) {
+            *reinterpret_cast<bvec*>(x_in + wbase[j]) = xb;
+            if (cfg) *reinterpret_cast<bvec*>(x_in + (long long)B * win.K * win.hw * win.wc + wbase[j]) = xb;
+          }
+      }
+    } else if (x_in) {
       *reinterpret_cast<bvec*>(x_in + idx) = xb;
       if (cfg) *reinterpret_cast<bvec*>(x_in + total + idx) = xb;
     }
@@ -459,6 +545,108 @@ __global__ __launch_bounds__(256) void unipc_step_fused_masked_kernel(const floa
   step_fused_body<UniPCSolver, VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, UniPCSolver{state, step_idx, (long long)B * n}, table,
                                           row_elems, rowbias, timesteps, n_steps, t_out, ticket,
                                           (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
+}
+
+// The windowed fused steps: the frame above with WINDOWED, the four solvers unchanged.  Their own parameter list -- the plain kernels'
+// (coef and step_idx inside the first 64 bytes), then the plan: offset, cover, weight, K, KC, rows, hw, wc.  n = rows * wc.
+template <int VEC>
+__global__ __launch_bounds__(256) void ddim_step_fused_windowed_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                        int cfg, float g, const float* __restrict__ coef,
+                                                                        int* __restrict__ step_idx, bf16* __restrict__ x_in,
+                                                                        const float* __restrict__ table, long long row_elems,
+                                                                        float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                                        int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket,
+                                                                        const int* offset, const int* cover, const float* weight, int K,
+                                                                        int KC, int rows, int hw, long long wc) {
+  step_fused_body<DdimSolver, VEC, false, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, DdimSolver{}, table, row_elems, rowbias,
+                                              timesteps, n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{},
+                                              Windows{offset, cover, weight, K, KC, rows, hw, wc});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void dpm_step_fused_windowed_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                        int cfg, float g, const float* __restrict__ coef,
+                                                                        int* __restrict__ step_idx, bf16* __restrict__ x_in,
+                                                                        float* __restrict__ hist, const float* __restrict__ table, long long row_elems,
+                                                                        float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                                        int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket,
+                                                                        const int* offset, const int* cover, const float* weight, int K,
+                                                                        int KC, int rows, int hw, long long wc) {
+  step_fused_body<DpmSolver, VEC, false, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, DpmSolver{hist}, table, row_elems, rowbias,
+                                              timesteps, n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{},
+                                              Windows{offset, cover, weight, K, KC, rows, hw, wc});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void euler_a_step_fused_windowed_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                        int cfg, float g, const float* __restrict__ coef,
+                                                                        int* __restrict__ step_idx, bf16* __restrict__ x_in,
+                                                                        uint32_t* __restrict__ rng, const float* __restrict__ table, long long row_elems,
+                                                                        float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                                        int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket,
+                                                                        const int* offset, const int* cover, const float* weight, int K,
+                                                                        int KC, int rows, int hw, long long wc) {
+  step_fused_body<EulerASolver, VEC, false, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, EulerASolver{rng}, table, row_elems, rowbias,
+                                              timesteps, n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{},
+                                              Windows{offset, cover, weight, K, KC, rows, hw, wc});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void unipc_step_fused_windowed_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                        int cfg, float g, const float* __restrict__ coef,
+                                                                        int* __restrict__ step_idx, bf16* __restrict__ x_in,
+                                                                        float* __restrict__ state, const float* __restrict__ table, long long row_elems,
+                                                                        float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                                        int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket,
+                                                                        const int* offset, const int* cover, const float* weight, int K,
+                                                                        int KC, int rows, int hw, long long wc) {
+  step_fused_body<UniPCSolver, VEC, false, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, UniPCSolver{state, step_idx, (long long)B * n}, table, row_elems, rowbias,
+                                              timesteps, n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{},
+                                              Windows{offset, cover, weight, K, KC, rows, hw, wc});
+}
+
+// windows out of the long tensor: out[b * K + k][i][:] = x[b][(offset[k] + i) mod rows][:] * mul, bf16 (the UNet / VAE input: the
+// rounding of f32_to_bf16_kernel) or fp32.  One thread per VEC elements of the output.
+template <int VEC>
+__global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ x, const int* __restrict__ offset, int B, int K,
+                                                            int rows, int hw, long long wc, float mul, void* __restrict__ out, int out_f32) {
+  typedef fvec_t<VEC> fvec;
+  typedef bf16 bvec __attribute__((ext_vector_type(VEC)));
+  const long long idx = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+  if (idx >= (long long)B * K * hw * wc) return;
+  const long long pix = idx / wc, c = idx - pix * wc;
+  const long long bk = pix / hw;
+  const int i = (int)(pix - bk * hw), k = (int)(bk % K);
+  int r = (offset[k] + i) % rows;
+  if (r < 0) r += rows;                                       // (whatever the table holds, the source row is a row of x)
+  fvec v = *reinterpret_cast<const fvec*>(x + ((bk / K) * rows + r) * wc + c);
+  if (out_f32) {
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) v[e] = v[e] * mul;
+    *reinterpret_cast<fvec*>(reinterpret_cast<float*>(out) + idx) = v;
+  } else {
+    bvec o;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) o[e] = (bf16)(v[e] * mul);
+    *reinterpret_cast<bvec*>(reinterpret_cast<bf16*>(out) + idx) = o;
+  }
+}
+
+// windows back into the long tensor: out[b][r][:] = sum_j weight[r][j] win[b * K + cover[r][j]][(r - offset) mod rows][:], in the
+// order of window_blend_row.  One thread per VEC elements of the output.
+template <int VEC>
+__global__ __launch_bounds__(256) void window_blend_kernel(const float* __restrict__ win, int B, long long n, float* __restrict__ out,
+                                                           const int* offset, const int* cover, const float* weight, int K, int KC,
+                                                           int rows, int hw, long long wc) {
+  typedef fvec_t<VEC> fvec;
+  const long long idx = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+  if (idx >= (long long)B * n) return;
+  const Windows w{offset, cover, weight, K, KC, rows, hw, wc};
+  const long long pix = idx / wc, b = pix / rows;
+  long long base[WIN_MAX_COVER];
+  fvec e, unused;
+  window_blend_row<VEC>(w, win, nullptr, b, (int)(pix - b * rows), idx - pix * wc, base, e, unused);
+  *reinterpret_cast<fvec*>(out + idx) = e;
 }
 
 __global__ void advance_step_kernel(int* step_idx, const float* __restrict__ timesteps, int n_steps, float* t_out) {
@@ -887,6 +1075,119 @@ extern "C" int aldm_unipc_step_fused_masked(const float* eps, float* x, int B, l
   return launch_step_fused<UniPCSolver, true>("unipc_step_fused_masked", unipc_step_fused_masked_kernel<4>, unipc_step_fused_masked_kernel<1>,
                                               eps, x, B, n_per_sample, cfg, guidance, coef, step_idx, x_in_bf16, table, row_elems, rowbias,
                                               timesteps, n_steps, t_out, ticket, Inpaint{x0, noise, mask, blend, channels}, stream, state);
+}
+
+// ---- windowed denoising: the plan's checks, the gather / blend launches and the four windowed fused steps ----
+// 0, or the error a plan earns against a long tensor of n_per_sample = rows * wc floats per clip; *wc receives the row width
+static int check_window_plan(const char* name, const aldm_window_plan_t* p, int B, long long n_per_sample, bool tables, long long* wc) {
+  ALDM_CHECK_ARG(p && p->offset && B > 0 && n_per_sample > 0, "%s: bad args", name);
+  ALDM_CHECK_ARG(p->K > 0 && p->rows > 0 && p->hw > 0 && p->hw <= p->rows, "%s: plan needs K > 0 and 0 < hw <= rows (K %d, hw %d, rows %d)",
+                 name, p->K, p->hw, p->rows);
+  ALDM_CHECK_ARG(p->offset_elems == p->K, "%s: offset holds %lld entries, the plan has K = %d windows", name, p->offset_elems, p->K);
+  ALDM_CHECK_ARG(n_per_sample % p->rows == 0, "%s: n_per_sample %lld is no multiple of the plan's %d rows", name, n_per_sample, p->rows);
+  if (tables) {
+    ALDM_CHECK_ARG(p->cover && p->weight && p->KC >= 1, "%s: bad plan tables", name);
+    if (p->KC > WIN_MAX_COVER) {
+      aldm_set_error("%s: a row under %d windows; at most %d are supported", name, p->KC, WIN_MAX_COVER);
+      return ALDM_E_UNSUPPORTED;
+    }
+    const long long want = (long long)p->rows * p->KC;
+    ALDM_CHECK_ARG(p->cover_elems == want && p->weight_elems == want, "%s: cover / weight hold %lld / %lld entries, rows * KC = %lld", name,
+                   p->cover_elems, p->weight_elems, want);
+  }
+  *wc = n_per_sample / p->rows;
+  return ALDM_OK;
+}
+
+extern "C" int aldm_window_gather(const float* x, int B, long long n_per_sample, float mul, void* out, int out_is_f32,
+                                  const aldm_window_plan_t* plan, void* stream) {
+  ALDM_CHECK_ARG(x && out, "window_gather: bad args");
+  long long wc;
+  if (const int rc = check_window_plan("window_gather", plan, B, n_per_sample, false, &wc)) return rc;
+  const long long total = (long long)B * plan->K * plan->hw * wc;
+  if (wc % 4 == 0)
+    hipLaunchKernelGGL(window_gather_kernel<4>, dim3(blocks_for(total / 4, 256)), dim3(256), 0, (hipStream_t)stream, x, plan->offset, B,
+                       plan->K, plan->rows, plan->hw, wc, mul, out, out_is_f32);
+  else
+    hipLaunchKernelGGL(window_gather_kernel<1>, dim3(blocks_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, plan->offset, B, plan->K,
+                       plan->rows, plan->hw, wc, mul, out, out_is_f32);
+  return aldm_launch_status("window_gather");
+}
+
+extern "C" int aldm_window_blend(const float* win, int B, long long n_per_sample, float* out, const aldm_window_plan_t* plan, void* stream) {
+  ALDM_CHECK_ARG(win && out, "window_blend: bad args");
+  long long wc;
+  if (const int rc = check_window_plan("window_blend", plan, B, n_per_sample, true, &wc)) return rc;
+  const long long total = (long long)B * n_per_sample;
+  if (wc % 4 == 0)
+    hipLaunchKernelGGL(window_blend_kernel<4>, dim3(blocks_for(total / 4, 256)), dim3(256), 0, (hipStream_t)stream, win, B, n_per_sample, out,
+                       plan->offset, plan->cover, plan->weight, plan->K, plan->KC, plan->rows, plan->hw, wc);
+  else
+    hipLaunchKernelGGL(window_blend_kernel<1>, dim3(blocks_for(total, 256)), dim3(256), 0, (hipStream_t)stream, win, B, n_per_sample, out,
+                       plan->offset, plan->cover, plan->weight, plan->K, plan->KC, plan->rows, plan->hw, wc);
+  return aldm_launch_status("window_blend");
+}
+
+// launch_step_fused for the windowed kernels: the same checks and grid (one thread per VEC long elements or per four floats of the
+// table row), VEC = 4 only where a vector stays inside a row (wc % 4 == 0), and the plan behind the frame's operands
+template <class Solver, class Kernel, class... Op>
+static int launch_step_fused_windowed(const char* name, Kernel k4, Kernel k1, const float* eps, float* x, int B, long long n_per_sample,
+                                      int cfg, float guidance, const float* coef, int* step_idx, void* x_in_bf16, const float* table,
+                                      long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                      unsigned* ticket, const aldm_window_plan_t* plan, void* stream, Op... op) {
+  ALDM_CHECK_ARG(eps && x && coef && step_idx && (... && op) && B > 0 && n_per_sample > 0 && n_steps > 0, "%s: bad args", name);
+  ALDM_CHECK_ARG(Solver::TICKET_OPTIONAL || ticket, "%s: bad args", name);
+  ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "%s: the counter advance needs timesteps and t_out", name);
+  ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
+                 "%s: table needs ticket, rowbias and row_elems %% 4 == 0", name);
+  long long wc;
+  if (const int rc = check_window_plan(name, plan, B, n_per_sample, true, &wc)) return rc;
+  if (!table) row_elems = 0;
+  const long long total = (long long)B * n_per_sample;
+  const bool v4 = wc % 4 == 0;
+  const long long items = v4 ? total / 4 : total;
+  const long long work = items > row_elems / 4 ? items : row_elems / 4;
+  hipLaunchKernelGGL(v4 ? k4 : k1, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample, cfg, guidance, coef,
+                     step_idx, (bf16*)x_in_bf16, op..., table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan->offset,
+                     plan->cover, plan->weight, plan->K, plan->KC, plan->rows, plan->hw, wc);
+  return aldm_launch_status(name);
+}
+
+extern "C" int aldm_ddim_step_fused_windowed(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                             const float* coef, int* step_idx, void* x_in_bf16, const float* table, long long row_elems,
+                                             float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket,
+                                             const aldm_window_plan_t* plan, void* stream) {
+  return launch_step_fused_windowed<DdimSolver>("ddim_step_fused_windowed", ddim_step_fused_windowed_kernel<4>,
+                                                ddim_step_fused_windowed_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef, step_idx,
+                                                x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan, stream);
+}
+
+extern "C" int aldm_dpm_step_fused_windowed(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                            const float* coef, int* step_idx, void* x_in_bf16, float* hist, const float* table,
+                                            long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                            unsigned* ticket, const aldm_window_plan_t* plan, void* stream) {
+  return launch_step_fused_windowed<DpmSolver>("dpm_step_fused_windowed", dpm_step_fused_windowed_kernel<4>, dpm_step_fused_windowed_kernel<1>,
+                                               eps, x, B, n_per_sample, cfg, guidance, coef, step_idx, x_in_bf16, table, row_elems, rowbias,
+                                               timesteps, n_steps, t_out, ticket, plan, stream, hist);
+}
+
+extern "C" int aldm_euler_a_step_fused_windowed(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                                const float* coef, int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table,
+                                                long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                                unsigned* ticket, const aldm_window_plan_t* plan, void* stream) {
+  return launch_step_fused_windowed<EulerASolver>("euler_a_step_fused_windowed", euler_a_step_fused_windowed_kernel<4>,
+                                                  euler_a_step_fused_windowed_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef,
+                                                  step_idx, x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan,
+                                                  stream, rng_state);
+}
+
+extern "C" int aldm_unipc_step_fused_windowed(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                              const float* coef, int* step_idx, void* x_in_bf16, float* state, const float* table,
+                                              long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                              unsigned* ticket, const aldm_window_plan_t* plan, void* stream) {
+  return launch_step_fused_windowed<UniPCSolver>("unipc_step_fused_windowed", unipc_step_fused_windowed_kernel<4>,
+                                                 unipc_step_fused_windowed_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef, step_idx,
+                                                 x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan, stream, state);
 }
 
 extern "C" int aldm_add_noise(const float* x, const float* noise, const float* coef, int B, long long n_per_sample,

@@ -21,6 +21,9 @@ moves the ordinal with the step counter, so every replay draws fresh noise.  In 
 x / sqrt(sigma^2 + 1).
 Multi-adapter LoRA: a gated engine's UNet launches read a per-sample gate table from one more device buffer
 (set_adapters): another routing, other weights or no adapter at all is a copy into that buffer -- no repack, no re-capture.
+Long-form generation: WindowedDenoiseEngine keeps ONE long latent [B, rows, W, C] and runs the UNet on K
+overlapping windows of the trained length as batch rows; the windowed fused step (ops.*_step_fused_windowed) blends the windows' eps
+into the long latent, updates it and scatters the next UNet input back into every window -- still one launch behind the UNet.
 """
 import torch
 
@@ -299,3 +302,98 @@ class DenoiseEngine:
 
     def latents_nchw(self):
         return ops.nhwc_to_nchw_f32(self.x)
+
+
+class WindowedDenoiseEngine(DenoiseEngine):
+    """The loop on a LONG latent as K overlapping windows (longform.WindowPlan over the time axis): B clips times K windows are the
+    UNet's batch rows, shapes it is tuned for.  x, hist, state and the Philox stream stay in the long layout [B, rows, W, C]; x_in,
+    the class labels, the time-embedding table and the gate table have one row per (clip, window): 2 * B * K under CFG, all in ONE
+    UNet call (no sub-batching: activation memory grows with K).  A plan of one window is DenoiseEngine, bit
+    for bit.  Audio-to-audio on long clips is not built: chains > 1, masked and begin_index > 0 raise."""
+
+    def __init__(self, unet, scheduler, batch, plan, width, num_inference_steps, guidance_scale=2.5, device="cuda", use_graph=True,
+                 chains=None, begin_index=0, masked=False, gated=False):
+        if chains not in (None, 1):
+            raise NotImplementedError("WindowedDenoiseEngine: chains > 1 is not built (the windows already fill the batch)")
+        if masked or begin_index:
+            raise NotImplementedError("WindowedDenoiseEngine: masked / begun (audio-to-audio) runs on a long latent are not built")
+        self.plan, self.K, self.hw = plan, plan.K, plan.window_rows
+        super().__init__(unet, scheduler, batch, plan.rows, width, num_inference_steps, guidance_scale, device=device, use_graph=use_graph,
+                         gated=gated)
+        self.bc = batch * self.K                                  # rows per CFG half of everything the UNet sees
+        self.x_in = [torch.zeros((2 if self.cfg else 1) * self.bc, self.hw, width, self.C, dtype=torch.bfloat16, device=self.dev)]
+        self._win = plan.device(self.dev)                         # offset / cover / weight tables (the plan keeps them alive)
+        self._step = getattr(ops, self._step.__name__ + "_windowed")
+
+    def _per_window(self, entries, what):
+        """one entry per clip, or one per (clip, window) in that order -> one per (clip, window)"""
+        if entries is None:
+            return None
+        entries = list(entries)
+        if len(entries) == self.B * self.K:
+            return entries
+        if len(entries) == self.B:
+            return [e for e in entries for _ in range(self.K)]
+        raise ValueError(f"{what} needs one entry per clip ({self.B}) or per (clip, window) ({self.B * self.K}), got {len(entries)}")
+
+    def _windows_of(self, e):
+        """[B, D] (repeated over the windows) or [B, K, D] (one prompt per window) -> [B * K, D]"""
+        if e is None:
+            return None
+        if e.dim() == 2 and e.shape[0] == self.B:
+            e = e[:, None, :].expand(self.B, self.K, e.shape[-1])
+        if e.dim() != 3 or tuple(e.shape[:2]) != (self.B, self.K):
+            raise ValueError(f"prompt embeddings must be [{self.B}, D] or [{self.B}, {self.K}, D], got {tuple(e.shape)}")
+        return e.reshape(self.B * self.K, e.shape[-1])
+
+    def set_condition(self, prompt_embeds, negative_prompt_embeds=None):
+        """[B, D] L2-normalised prompt embeddings, the same for every window of a clip, or [B, K, D]: one prompt per window (a prompt
+        schedule along the track).  The negative embeddings likewise."""
+        super().set_condition(self._windows_of(prompt_embeds), self._windows_of(negative_prompt_embeds))
+
+    def _fill_gate(self, adapter_names, adapter_weights):
+        names, weights = self._per_window(adapter_names, "adapter_names"), self._per_window(adapter_weights, "adapter_weights")
+        g = self.unet.device_gate(names, self.B * self.K, weights)
+        if g is None:
+            g = self.unet.gate_table(names, self.B * self.K).to(self.dev)
+        new = [(torch.cat([g, g]) if self.cfg else g).contiguous()]
+        if self.gate is None:
+            self.gate = new
+        else:
+            self.gate[0].copy_(new[0])
+
+    def set_adapters(self, adapter_names=None, adapter_weights=None):
+        """DenoiseEngine.set_adapters with one entry per clip, or one per (clip, window)."""
+        names = self._per_window(adapter_names, "adapter_names")
+        plain = adapter_weights is None and self.unet.routing_is_plain(names)
+        if self.gate is None:
+            if plain:
+                return
+            if self.graph is not None:
+                raise ops._lib.AldmError("WindowedDenoiseEngine: this graph was captured without a gate table (plain single-adapter "
+                                         "model); build a new engine to route adapters per clip")
+        self._fill_gate(adapter_names, adapter_weights)
+
+    def set_latents(self, latents_nchw):
+        """latents [B, C, rows, W] fp32 of the LONG clip, already multiplied by init_noise_sigma; the windows of the first UNet input
+        are gathered out of it (Euler-ancestral: with row 0's input scale)."""
+        self.x.copy_(ops.nchw_to_nhwc(latents_nchw.to(self.dev, torch.float32).contiguous(), out_f32=True))
+        xb = ops.window_gather(self.x, self._win, self.in_scale0)
+        self.x_in[0][: self.bc].copy_(xb)
+        if self.cfg:
+            self.x_in[0][self.bc:].copy_(xb)
+        self.step_idx.zero_()
+        self.t_buf.copy_(self.timesteps_f32[:1])
+        if self.hist is not None:
+            self.hist.zero_()
+        if self.state is not None:
+            self.state.zero_()
+        if self.rng is not None:
+            self.rng[2:].zero_()
+        self._prime()
+
+    def _one_step(self):
+        # one UNet call on all windows, then the windowed fused step: blend, update, scatter, next row, counter -- one launch
+        eps = self.unet.forward_nhwc(self.x_in[0], self.t_buf, self.cls[0], rowbias=self.rowbias[0], gate=self._gate(0))
+        self._step(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], *self._solver_args, self.temb[0], self.rowbias[0],
+                   self.timesteps_f32, self.t_buf, self.ticket, self._win)

@@ -1410,6 +1410,102 @@ def euler_a_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, rng_s
                 (x0, noise, mask, blend))
 
 
+# ---- windowed denoising: long-form and loopable generation (csrc/elementwise.hip, longform.py) ------------
+def _window_plan(plan):
+    """aldm_window_plan_t of a plan's device tables (longform.WindowPlan.device(): offset int32 [K], cover int32 [rows, KC], weight
+    fp32 [rows, KC] and K, KC, rows, hw).  What the tables hold goes along as counted here, so the launcher itself rejects tables
+    that do not fit the plan."""
+    for t, dt in ((plan.offset, torch.int32), (plan.cover, torch.int32), (plan.weight, torch.float32)):
+        _require_gpu(t)
+        assert t.dtype == dt and t.is_contiguous(), "window plan tables: contiguous int32 offset / cover and fp32 weight on the device"
+    return _lib.WindowPlanArgs(plan.offset.data_ptr(), plan.cover.data_ptr(), plan.weight.data_ptr(), int(plan.K), int(plan.KC),
+                               int(plan.rows), int(plan.hw), plan.offset.numel(), plan.cover.numel(), plan.weight.numel())
+
+
+def window_gather(x, plan, mul=1.0, out_f32=False, out=None):
+    """Windows out of a long tensor (aldm_window_gather): x fp32 [B, rows, W, C] -> [B * K, hw, W, C], window k of clip b at batch row
+    b * K + k, rows taken modulo `rows`.  bf16(x * mul) -- the rounding of f32_to_bf16 -- or fp32 (out_f32)."""
+    _require_gpu(x)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() >= 2
+    B = x.shape[0]
+    shape = (B * int(plan.K), int(plan.hw)) + tuple(x.shape[2:])
+    dt = torch.float32 if out_f32 else torch.bfloat16
+    if out is None:
+        out = torch.empty(shape, dtype=dt, device=x.device)
+    assert out.dtype == dt and out.is_contiguous() and tuple(out.shape) == shape
+    args = _window_plan(plan)
+    check(_launch("window_gather", 0.0, (4.0 + (4.0 if out_f32 else 2.0)) * out.numel(),
+                  lambda: _lib.load().aldm_window_gather(_p(x), B, x.numel() // B, float(mul), _p(out), int(out_f32), C.byref(args), _stream())),
+          "aldm_window_gather")
+    return out
+
+
+def window_blend(win, plan, out=None):
+    """Windows back into a long tensor (aldm_window_blend): win fp32 [B * K, hw, W, C] -> [B, rows, W, C], every long row the
+    weighted sum of the windows over it (weight[r][0] * win_0, then fused multiply-adds in table order)."""
+    _require_gpu(win)
+    assert win.dtype == torch.float32 and win.is_contiguous() and win.dim() >= 2 and win.shape[0] % int(plan.K) == 0
+    B = win.shape[0] // int(plan.K)
+    shape = (B, int(plan.rows)) + tuple(win.shape[2:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=win.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape
+    args = _window_plan(plan)
+    check(_launch("window_blend", 2.0 * win.numel(), 4.0 * (win.numel() + out.numel()),
+                  lambda: _lib.load().aldm_window_blend(_p(win), B, out.numel() // B, _p(out), C.byref(args), _stream())),
+          "aldm_window_blend")
+    return out
+
+
+def _step_fused_windowed(solver, eps, x, cfg, guidance, coef, step_idx, x_in, operand, table, rowbias, timesteps_f32, t_out, ticket, plan):
+    """The frame of the four windowed fused steps (launch_step_fused_windowed): _step_fused's checks with eps and x_in per window.
+    x fp32 [B, rows, W, C] long; eps fp32 [halves * B * K, hw, W, C]; x_in bf16 of eps's shape (or None)."""
+    coef_cols, flops, solver_bytes, ticket_optional = _STEP_SOLVERS[solver]
+    _require_gpu(x)
+    B = x.shape[0]
+    n = x.numel() // B
+    halves = 2 if cfg else 1
+    row = table[0].numel() if table is not None else 0
+    assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.shape[1] == coef_cols and step_idx.dtype == torch.int32
+    assert x.dtype == torch.float32 and x.is_contiguous() and eps.dtype == torch.float32 and eps.is_contiguous()
+    win_elems = B * int(plan.K) * int(plan.hw) * (n // max(1, int(plan.rows)))
+    assert eps.numel() == win_elems * halves, "eps: [halves * B * K, hw, W, C]"
+    assert x_in is None or (x_in.dtype == torch.bfloat16 and x_in.is_contiguous() and x_in.numel() == eps.numel()), "x_in: bf16 of eps's shape"
+    assert (ticket_optional and ticket is None) or (ticket.dtype == torch.int32 and timesteps_f32 is not None and t_out is not None)
+    n_steps = timesteps_f32.numel() if timesteps_f32 is not None else coef.shape[0]
+    name = f"{solver}_step_fused_windowed"
+    args = _window_plan(plan)
+    fn = getattr(_lib.load(), "aldm_" + name)
+    # bytes: every window's eps and bf16 input (1 or 2 halves), x read / write and the solver's per long element, the table row
+    check(_launch(name, (flops + 4.0 * halves) * x.numel(), 6.0 * eps.numel() + (8.0 + solver_bytes) * x.numel() + 8.0 * row,
+                  lambda: fn(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in), *map(_p, operand), _p(table), row,
+                             _p(rowbias), _p(timesteps_f32), n_steps, _p(t_out), _p(ticket), C.byref(args), _stream())), "aldm_" + name)
+
+
+def ddim_step_fused_windowed(eps, x, cfg, guidance, coef, step_idx, x_in, table, rowbias, timesteps_f32, t_out, ticket, plan):
+    """ddim_step_fused on a long latent with eps and x_in per window (aldm_ddim_step_fused_windowed): the windows' eps halves are
+    blended into the long row, the update runs on the blend, and the next UNet input is stored into every window over the row."""
+    _step_fused_windowed("ddim", eps, x, cfg, guidance, coef, step_idx, x_in, (), table, rowbias, timesteps_f32, t_out, ticket, plan)
+
+
+def dpm_step_fused_windowed(eps, x, cfg, guidance, coef, step_idx, x_in, hist, table, rowbias, timesteps_f32, t_out, ticket, plan):
+    """dpm_step_fused on a long latent (aldm_dpm_step_fused_windowed); hist fp32 in x's long shape."""
+    assert hist.dtype == torch.float32 and hist.numel() == x.numel()
+    _step_fused_windowed("dpm", eps, x, cfg, guidance, coef, step_idx, x_in, (hist,), table, rowbias, timesteps_f32, t_out, ticket, plan)
+
+
+def unipc_step_fused_windowed(eps, x, cfg, guidance, coef, step_idx, x_in, state, table, rowbias, timesteps_f32, t_out, ticket, plan):
+    """unipc_step_fused on a long latent (aldm_unipc_step_fused_windowed); state fp32 [3, *x.shape], long."""
+    _check_unipc_state(state, x)
+    _step_fused_windowed("unipc", eps, x, cfg, guidance, coef, step_idx, x_in, (state,), table, rowbias, timesteps_f32, t_out, ticket, plan)
+
+
+def euler_a_step_fused_windowed(eps, x, cfg, guidance, coef, step_idx, x_in, rng_state, table, rowbias, timesteps_f32, t_out, ticket, plan):
+    """euler_a_step_fused on a long latent (aldm_euler_a_step_fused_windowed): element i of the LONG latent is element i of the draw."""
+    _check_state(rng_state)
+    _step_fused_windowed("euler_a", eps, x, cfg, guidance, coef, step_idx, x_in, (rng_state,), table, rowbias, timesteps_f32, t_out, ticket, plan)
+
+
 def add_noise(x, noise, coef):
     _require_gpu(x)
     B = x.shape[0]

@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .engine import DenoiseEngine
+from .engine import DenoiseEngine, WindowedDenoiseEngine
+from .longform import plan_for_seconds
 from .scheduler import DDIMScheduler, _fresh_seed
 from .unet import UNet2DConditionModel
 from .vae import AutoencoderKL
@@ -41,6 +42,7 @@ class AudioLDMPipeline:
         self.vae_scale_factor = 2 ** (len(vae.cfg["block_out_channels"]) - 1)
         self.device = torch.device("cpu")
         self._engines = {}
+        self._plans = {}
         self._progress = {}
 
     @classmethod
@@ -117,16 +119,78 @@ class AudioLDMPipeline:
             height = int(np.ceil(height / self.vae_scale_factor)) * self.vae_scale_factor
         return height, n_samples
 
-    def engine(self, batch, h, w, steps, guidance, gated=False):
+    def engine(self, batch, h, w, steps, guidance, gated=False, plan=None):
         # the scheduler is part of the key: a graph captured with one scheduler's update and coefficients must never replay for another
-        # (gated: a graph whose fused-LoRA launches read a per-clip gate table is another graph than the plain single-adapter one)
+        # (gated: a graph whose fused-LoRA launches read a per-clip gate table is another graph than the plain single-adapter one;
+        # plan: a windowed engine's graph holds the plan's tables and window count, so different plans never share one)
         key = (batch, h, w, steps, float(guidance), type(self.scheduler).__name__, _frozen_config(self.scheduler)) + ((True,) if gated else ())
+        if plan is not None:
+            key = key + (("windowed",) + plan.key,)
         eng = self._engines.get(key)
         if eng is not None and (eng.unet is not self._unet or eng.scheduler is not self.scheduler or eng.stale()):
             eng = None                                  # weights / adapter / scheduler changed since the capture: never replay the old graph
+        if eng is None and plan is not None:
+            eng = self._engines[key] = WindowedDenoiseEngine(self._unet, self.scheduler, batch, plan, w, steps, guidance, device=self.device,
+                                                             gated=gated)
         if eng is None:
             eng = self._engines[key] = DenoiseEngine(self._unet, self.scheduler, batch, h, w, steps, guidance, device=self.device, gated=gated)
         return eng
+
+    # ---- long-form and loopable generation ----
+    def window_plan(self, audio_length_in_s, window_length_in_s, window_overlap_in_s=None, loop=False):
+        """(the latent plan, the mel plan) of a windowed call: longform.plan_for_seconds with this pipeline's frame rate and VAE
+        scale, and the same plan at the mel's resolution.  Kept per key, so the device tables a captured graph reads stay alive."""
+        vc = self.vocoder.config
+        if window_overlap_in_s is None:
+            window_overlap_in_s = window_length_in_s / 4.0
+        up = float(np.prod(vc.upsample_rates)) / vc.sampling_rate
+        plan = plan_for_seconds(audio_length_in_s, window_length_in_s, window_overlap_in_s, up, self.vae_scale_factor, loop)
+        if plan.key not in self._plans:
+            self._plans[plan.key] = (plan, plan.scaled(self.vae_scale_factor))
+        return self._plans[plan.key]
+
+    def vocoder_half_field(self):
+        """Mel frames on either side of a frame that can reach its audio: the vocoder's receptive half-field, from its config alone
+        (DESIGN.md section 18 has the derivation).  Walks the stack from the waveform back to the mel, a radius in samples of each
+        stage: conv_post and conv_pre (kernel 7) add 3; a stage's residual blocks run side by side, so the widest counts, each
+        dilation d of kernel k adding (k - 1) / 2 * (d + 1); a transposed conv (kernel k, stride u, padding p) maps a radius R of
+        its output to ceil((R + max(p, k - 1 - p)) / u) of its input."""
+        vc = self.vocoder.config
+        res = max((k - 1) // 2 * (sum(d) + len(d)) for k, d in zip(vc.resblock_kernel_sizes, vc.resblock_dilation_sizes))
+        r = 3
+        for u, k in reversed(list(zip(vc.upsample_rates, vc.upsample_kernel_sizes))):
+            p = (k - u) // 2
+            r = -(-(r + res + max(p, k - 1 - p)) // u)
+        return r + 3
+
+    def _window_prompt_embeds(self, window_prompts, window_prompt_embeds, n_prompts, K, num_waveforms_per_prompt):
+        """[B, K, D] L2-normalised embeddings, one per (clip, window): from K strings per prompt, or as given"""
+        if window_prompt_embeds is None:
+            wp = [list(window_prompts)] if isinstance(window_prompts[0], str) else [list(p) for p in window_prompts]
+            if len(wp) != n_prompts or any(len(p) != K for p in wp):
+                raise ValueError(f"window_prompts needs {K} strings (one per window) for each of the {n_prompts} prompts")
+            window_prompt_embeds = self._encode_prompt([t for p in wp for t in p], n_prompts * K).view(n_prompts, K, -1)
+        if window_prompt_embeds.dim() != 3 or tuple(window_prompt_embeds.shape[:2]) != (n_prompts, K):
+            raise ValueError(f"window_prompt_embeds must be [{n_prompts}, {K}, D], got {tuple(window_prompt_embeds.shape)}")
+        return window_prompt_embeds.repeat_interleave(num_waveforms_per_prompt, dim=0) if num_waveforms_per_prompt > 1 else window_prompt_embeds
+
+    def decode_windows_nhwc(self, x_long, plan, mel_plan, loop=False):
+        """steps 6-7 of a long latent [B, rows, w, 8] fp32: the VAE decodes the plan's windows as batch rows (shapes it is tuned and
+        tested for), the windows' mels are blended into one long mel by the plan at the mel's resolution, and the vocoder runs on the
+        whole mel -> (waveform [B, 160 * 4 rows (+ 32 when not looped)], mel [B, 4 rows, 64, 1] fp32).  loop: the mel is padded
+        circularly by the vocoder's receptive half-field on both sides and the waveform trimmed back, so that sample 0 continues
+        from the last sample."""
+        z = ops.window_gather(x_long, plan.device(self.device), 1.0 / self.vae.config.scaling_factor)
+        mel = ops.window_blend(self.vae.decode_nhwc(z).contiguous(), mel_plan.device(self.device))       # [B, T, 64, 1] fp32
+        B, T, F, _ = mel.shape
+        if not loop:
+            return self.vocoder.forward_nhwc(ops.f32_to_bf16(mel).view(B, 1, T, F)), mel
+        P = self.vocoder_half_field()
+        idx = torch.arange(-P, T + P, device=mel.device) % T
+        padded = mel.index_select(1, idx).contiguous()
+        wav = self.vocoder.forward_nhwc(ops.f32_to_bf16(padded).view(B, 1, T + 2 * P, F))
+        hop = int(np.prod(self.vocoder.config.upsample_rates))
+        return wav[:, P * hop:(P + T) * hop], mel
 
     # ---- LoRA adapters (diffusers' surface; DESIGN.md section 13) ----
     def _peft(self):
@@ -216,7 +280,12 @@ class AudioLDMPipeline:
     def __call__(self, prompt=None, audio_length_in_s=None, num_inference_steps=10, guidance_scale=2.5,
                  negative_prompt=None, num_waveforms_per_prompt=1, eta=0.0, generator=None, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, return_dict=True, output_type="np", adapter_names=None,
-                 adapter_weights=None, **kw):
+                 adapter_weights=None, window_length_in_s=None, window_overlap_in_s=None, loop=False, window_prompts=None,
+                 window_prompt_embeds=None, **kw):
+        """window_length_in_s (default None: one clip of audio_length_in_s, as ever) turns on windowed denoising for clips longer
+        than the UNet was trained on: overlapping windows of that length (window_overlap_in_s, default a quarter of it) along one
+        long latent, blended at every step; loop=True makes the clip close on itself (its length is rounded UP to a whole number of
+        window strides).  window_prompts: K strings per prompt, or window_prompt_embeds [B, K, D] -- one prompt per window."""
         if self.device.type != "cuda":
             raise ops._lib.AldmError("AudioLDMPipeline runs on the MI355X only: call .to('cuda') (no CPU fallback)")
         if eta != 0.0:
@@ -227,9 +296,25 @@ class AudioLDMPipeline:
             inner = getattr(getattr(self.unet, "base_model", None), "model", self.unet)          # a PeftModel wraps the UNet
             audio_length_in_s = inner.config.sample_size * self.vae_scale_factor * float(np.prod(vc.upsample_rates)) / vc.sampling_rate
         height, n_samples = self.geometry(audio_length_in_s)
+        plan = mel_plan = None
+        if window_length_in_s is None:
+            if loop or window_prompts is not None or window_prompt_embeds is not None or window_overlap_in_s is not None:
+                raise ValueError("loop / window_prompts / window_overlap_in_s need window_length_in_s")
+        else:
+            plan, mel_plan = self.window_plan(audio_length_in_s, window_length_in_s, window_overlap_in_s, loop)
+            height = plan.rows * self.vae_scale_factor
+            if loop:                                    # the whole rounded-up loop: trimming it would open the seam
+                n_samples = height * int(np.prod(vc.upsample_rates))
+            if prompt is None and prompt_embeds is None and window_prompt_embeds is not None:
+                prompt_embeds = window_prompt_embeds[:, 0]          # (batch size and the negative half come from the per-clip path)
+            elif prompt is None and prompt_embeds is None and window_prompts is not None:
+                prompt = [window_prompts[0]] if isinstance(window_prompts[0], str) else [p[0] for p in window_prompts]
         prompt_embeds, negative_prompt_embeds = self._prompt_embeds(prompt, prompt_embeds, negative_prompt, negative_prompt_embeds,
                                                                     guidance_scale, num_waveforms_per_prompt)
         batch = prompt_embeds.shape[0]
+        if plan is not None and (window_prompts is not None or window_prompt_embeds is not None):
+            prompt_embeds = self._window_prompt_embeds(window_prompts, window_prompt_embeds, batch // num_waveforms_per_prompt, plan.K,
+                                                       num_waveforms_per_prompt)
         h, w = height // self.vae_scale_factor, vc.model_in_dim // self.vae_scale_factor
         shape = (batch, self._unet.cfg["in_channels"], h, w)
         if latents is None:
@@ -241,7 +326,7 @@ class AudioLDMPipeline:
         latents = latents.to(self.device, torch.float32) * self.scheduler.init_noise_sigma
 
         gated, adapter_names, adapter_weights = self._route(adapter_names, adapter_weights, batch // num_waveforms_per_prompt, num_waveforms_per_prompt)
-        eng = self.engine(batch, h, w, num_inference_steps, guidance_scale, gated=gated)
+        eng = self.engine(batch, h, w, num_inference_steps, guidance_scale, gated=gated, plan=plan)
         eng.set_adapters(adapter_names, adapter_weights)
         eng.set_condition(prompt_embeds, negative_prompt_embeds)
         self._seed_engine(eng, generator)
@@ -249,10 +334,12 @@ class AudioLDMPipeline:
         if eng.graph is None and eng.use_graph:
             eng.capture()
         eng.run()
-        wav, mel = self.decode_latents_nhwc(eng.x)
+        wav, mel = self.decode_latents_nhwc(eng.x) if plan is None else self.decode_windows_nhwc(eng.x, plan, mel_plan, loop)
         audio = wav[:, :n_samples]
         if output_type == "np":
             audio = audio.float().cpu().numpy()
         if not return_dict:
             return (audio,)
+        if plan is not None:                            # a windowed call also hands back its plan and the blended mel [B, T, 64] (device)
+            return AudioPipelineOutput(audios=audio, plan=plan, mel=mel[..., 0])
         return AudioPipelineOutput(audios=audio)

@@ -15,6 +15,9 @@ seeds both the initial noise and that in-loop stream.
 `--lora NAME=PATH` (repeatable) loads named adapters side by side; `--adapters SPEC` routes them per prompt -- a comma list with one item
 per prompt (`--prompt` then takes prompts separated by `|`): `NAME`, `NAME:0.7`, `base`, or a blend `A:0.5+B:0.5`.  One call, one
 captured graph: the adapted and the original model of the reference's log_validation side by side.
+`--audio-length 60 --window-seconds 10.24 --window-overlap-seconds 2.56` generates a clip longer than the model was trained on by
+windowed denoising (overlapping windows of the trained length along one long latent, blended at every step); `--loop` makes it close
+on itself (the length is rounded up to a whole number of window strides); `--window-prompts "a|b|c"` gives every window its own prompt.
 """
 import argparse
 import os
@@ -74,6 +77,11 @@ def main(argv=None):
                          "steps), or its EulerAncestralDiscreteScheduler (euler-a)")
     ap.add_argument("--solver-order", type=int, choices=[1, 2], default=2, help="DPM-Solver / UniPC order (ignored with --scheduler ddim / euler-a)")
     ap.add_argument("--audio-length", type=float, default=None, help="seconds (default 10, or the --init-audio clip's length)")
+    ap.add_argument("--window-seconds", type=float, default=None,
+                    help="long-form generation: denoise --audio-length as overlapping windows of this length (10.24 = the trained length)")
+    ap.add_argument("--window-overlap-seconds", type=float, default=None, help="overlap of neighbouring windows (default: a quarter of --window-seconds)")
+    ap.add_argument("--loop", action="store_true", help="with --window-seconds: a clip that closes on itself (length rounded up to whole window strides)")
+    ap.add_argument("--window-prompts", default=None, metavar="A|B|C", help="with --window-seconds: one prompt per window, separated by '|'")
     ap.add_argument("--guidance-scale", type=float, default=5.0)
     ap.add_argument("--output", default="./generated_audio_LoRA/ex.wav")
     ap.add_argument("--seed", type=int, default=None, help="seed of the initial-noise generator and, with --scheduler euler-a, of the in-loop noise stream (the reference seeds "
@@ -91,6 +99,10 @@ def main(argv=None):
         ap.error("--adapters needs --lora NAME=PATH")
     if args.init_audio is None and (args.regenerate_seconds or args.regenerate_bands):
         ap.error("--regenerate-seconds / --regenerate-bands need --init-audio")
+    if args.window_seconds is None and (args.loop or args.window_prompts or args.window_overlap_seconds is not None):
+        ap.error("--loop / --window-prompts / --window-overlap-seconds need --window-seconds")
+    if args.window_seconds is not None and (args.init_audio is not None or args.adapters is not None):
+        ap.error("--window-seconds runs text-to-audio only (no --init-audio, no --adapters)")
 
     device = "cuda"
     unet = UNet2DConditionModel.from_pretrained(args.model_dir, subfolder="unet")
@@ -131,9 +143,14 @@ def main(argv=None):
         print(f"Generated {len(audios)} clips saved to: {stem}_*{ext or '.wav'}")
         return
     if args.init_audio is None:
+        windowed = {}
+        if args.window_seconds is not None:
+            windowed = dict(window_length_in_s=args.window_seconds, window_overlap_in_s=args.window_overlap_seconds, loop=args.loop)
+            if args.window_prompts:
+                windowed["window_prompts"] = [p.strip() for p in args.window_prompts.split("|")]
         audio = pipe(prompt=args.prompt, num_inference_steps=args.steps,
                      audio_length_in_s=10.0 if args.audio_length is None else args.audio_length,
-                     guidance_scale=args.guidance_scale, generator=generator).audios[0]
+                     guidance_scale=args.guidance_scale, generator=generator, **windowed).audios[0]
     else:
         audio = _audio_to_audio(pipe, args, generator)
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)

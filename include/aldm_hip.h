@@ -485,6 +485,52 @@ int aldm_unipc_step_fused_masked(const float* eps, float* x, int B, long long n_
                                  int* step_idx, void* x_in_bf16, float* state, const float* table, long long row_elems, float* rowbias,
                                  const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0, const float* noise,
                                  const float* mask, const float* blend, int channels, void* stream);
+/* ---- windowed denoising (long-form and loopable generation) ----
+   One long tensor [B][rows][wc] (wc = W * C contiguous floats per time row) and K windows of hw rows each as batch rows
+   [B * K][hw][wc]: window k of clip b is batch row b * K + k, and its row i is long row (offset[k] + i) mod rows.  The plan is three
+   small device tables, read-only to every launch that takes them:
+     offset int32 [K] ;  cover int32 [rows][KC]: the windows over long row r, ascending, -1 behind the last ;
+     weight fp32 [rows][KC]: their blend weights (positive, sum 1 per row).
+   *_elems say what the caller allocated for each table and are checked against K and rows * KC (ALDM_E_ARG); 1 <= KC <= 4, more is
+   ALDM_E_UNSUPPORTED; hw <= rows.  Nothing is launched on an error.  A cover entry outside [0, K), or one whose window does not hold
+   the row, ends that row's list: no table content sends an access out of bounds. */
+typedef struct {
+  const int* offset;
+  const int* cover;
+  const float* weight;
+  int K, KC, rows, hw;
+  long long offset_elems, cover_elems, weight_elems;
+} aldm_window_plan_t;
+/* out[b * K + k][i][:] = x[b][(offset[k] + i) mod rows][:] * mul: bf16 (the rounding of aldm_f32_to_bf16: the first UNet input, the
+   VAE input) or fp32 (out_is_f32).  x fp32 [B][rows][wc]; n_per_sample = rows * wc.  Only plan->offset / K / rows / hw are used. */
+int aldm_window_gather(const float* x, int B, long long n_per_sample, float mul, void* out, int out_is_f32,
+                       const aldm_window_plan_t* plan, void* stream);
+/* out[b][r][:] = w_0 win_0 + w_1 win_1 + ... over the windows of cover[r], as e = w_0 win_0 ; e = fma(w_j, win_j, e) in table order
+   (one window of weight 1.0 is copied bit for bit).  win fp32 [B * K][hw][wc], out fp32 [B][rows][wc]; n_per_sample = rows * wc. */
+int aldm_window_blend(const float* win, int B, long long n_per_sample, float* out, const aldm_window_plan_t* plan, void* stream);
+/* The four fused scheduler steps on a long latent: aldm_{ddim,dpm,euler_a,unipc}_step_fused with eps and x_in PER WINDOW.
+   x, hist / state and the Philox stream's element index stay in the long layout [B][rows][wc] (n_per_sample = rows * wc); eps is fp32
+   [half][B * K][hw][wc] and each half is first blended into the long row as in aldm_window_blend; the solver's update then runs
+   unchanged on the blended (eps_u, eps_t) and x; the bf16 input of the next UNet call is stored into EVERY window that holds the row,
+   in both halves: x_in bf16 [half][B * K][hw][wc].  One thread owns 4 consecutive long elements when wc % 4 == 0 (a vector never
+   straddles a row), else 1.  Counter, next time-embedding row, ticket, t_out and the wrap to row 0 exactly as in the plain launches; a
+   plan of ONE window of weight 1.0 with rows == hw reproduces them bit for bit.  No masked form. */
+int aldm_ddim_step_fused_windowed(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                  int* step_idx, void* x_in_bf16, const float* table, long long row_elems, float* rowbias,
+                                  const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const aldm_window_plan_t* plan,
+                                  void* stream);
+int aldm_dpm_step_fused_windowed(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                 int* step_idx, void* x_in_bf16, float* hist, const float* table, long long row_elems, float* rowbias,
+                                 const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const aldm_window_plan_t* plan,
+                                 void* stream);
+int aldm_euler_a_step_fused_windowed(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                     int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table, long long row_elems,
+                                     float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket,
+                                     const aldm_window_plan_t* plan, void* stream);
+int aldm_unipc_step_fused_windowed(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                   int* step_idx, void* x_in_bf16, float* state, const float* table, long long row_elems, float* rowbias,
+                                   const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const aldm_window_plan_t* plan,
+                                   void* stream);
 /* measurement aid: keeps `stream` busy for ~us microseconds so that later launches queue up behind it (bench.py) */
 int aldm_sleep_us(int us, void* stream);
 /* device-side loop counter for graph replay: step_idx[0] = (step_idx[0] + 1) mod n_steps ; t_out[0] = timesteps[step_idx[0]] */
