@@ -239,6 +239,9 @@ for _solver, _operand in (("ddim", []), ("dpm", [C.c_void_p]), ("euler_a", [C.c_
     PROTOTYPES[f"aldm_{_solver}_step_fused_masked"] = (C.c_int, _STEP_HEAD + _operand + _STEP_TAIL + _STEP_INPAINT + [C.c_void_p])
     # the windowed steps (long-form generation): the unmasked list, then the window plan
     PROTOTYPES[f"aldm_{_solver}_step_fused_windowed"] = (C.c_int, _STEP_HEAD + _operand + _STEP_TAIL + [C.POINTER(WindowPlanArgs), C.c_void_p])
+    # the masked windowed steps (audio-to-audio on a long latent): the windowed list, then the inpainting operands behind the plan
+    PROTOTYPES[f"aldm_{_solver}_step_fused_windowed_masked"] = (C.c_int, _STEP_HEAD + _operand + _STEP_TAIL + [C.POINTER(WindowPlanArgs)]
+                                                                + _STEP_INPAINT + [C.c_void_p])
 
 _lib = None
 

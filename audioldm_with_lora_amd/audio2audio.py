@@ -11,12 +11,17 @@ rows are then in sigma space, (a, s) = (1, sigma).
     x0 = scaling_factor * vae.encode(log_mel(audio)).latent_dist.sample()
     x  = a_begin x0 + s_begin eps                         (x = eps exactly at strength 1)
     for k, t in enumerate(timesteps[begin:]):  x = step(unet(x, t), t, x);  x = (1 - m) (a_k x0 + s_k eps) + m x
+
+Long recordings: `window_length_in_s=` runs all of the above on ONE long latent as overlapping windows of the
+trained length -- the recording is encoded window by window and the moments blended into the long layout, the loop is the windowed
+fused step with the blend inside it (aldm_*_step_fused_windowed[_masked]), and the decode is the windowed one.  A mask that keeps
+the recording and regenerates what lies behind it continues a clip to any length.
 """
 import numpy as np
 import torch
 
 from . import ops
-from .engine import DenoiseEngine
+from .engine import DenoiseEngine, WindowedAudioToAudioEngine
 from .mel import LogMelFrontEnd
 from .pipeline import AudioLDMPipeline, AudioPipelineOutput, _frozen_config
 
@@ -46,6 +51,16 @@ def regeneration_mask(height, n_mel, seconds=None, bands=None):
     return m
 
 
+def continuation_mask(height, n_mel, recording_seconds):
+    """The mask that CONTINUES a recording: keep its frames, regenerate every frame from its end to the end of a clip of `height` mel
+    frames (regeneration_mask over [recording_seconds, the clip's end)).  With strength 1.0 and windows this extends a clip to any
+    length: the kept rows are put back after every step and returned as the recording's own encoding."""
+    t0 = float(recording_seconds)
+    if not (t0 > 0.0 and int(np.floor(t0 / HOP_SECONDS + 1e-6)) < height):
+        raise ValueError(f"a recording of {recording_seconds} s leaves nothing to generate in a clip of {height * HOP_SECONDS:g} s")
+    return regeneration_mask(height, n_mel, seconds=(t0, (height + 1) * HOP_SECONDS))
+
+
 def reduce_mask(mask, factor):
     """[B, H, W] mel-resolution mask -> [B, H / factor, W / factor] latent-resolution mask: the max over each factor x factor cell, so
     every latent pixel that touches a regenerated mel cell is regenerated.  Host-side (a few kB, once per call)."""
@@ -65,12 +80,17 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
         new.device = pipe.device
         return new
 
-    def engine(self, batch, h, w, steps, guidance, begin_index=0, masked=False, gated=False):
+    def engine(self, batch, h, w, steps, guidance, begin_index=0, masked=False, gated=False, plan=None):
         key = (batch, h, w, steps, float(guidance), type(self.scheduler).__name__, _frozen_config(self.scheduler), int(begin_index),
                bool(masked)) + ((True,) if gated else ())
+        if plan is not None:                            # (a windowed graph holds the plan's tables: plans never share one)
+            key = key + (("windowed",) + plan.key,)
         eng = self._engines.get(key)
         if eng is not None and (eng.unet is not self._unet or eng.scheduler is not self.scheduler or eng.stale()):
             eng = None
+        if eng is None and plan is not None:
+            eng = self._engines[key] = WindowedAudioToAudioEngine(self._unet, self.scheduler, batch, plan, w, steps, guidance,
+                                                                  device=self.device, begin_index=begin_index, masked=masked, gated=gated)
         if eng is None:
             eng = self._engines[key] = DenoiseEngine(self._unet, self.scheduler, batch, h, w, steps, guidance, device=self.device,
                                                      begin_index=begin_index, masked=masked, gated=gated)
@@ -105,11 +125,26 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
             raise ValueError(f"mask batch {m.shape[0]} does not match {batch // per_prompt} prompt(s)")
         return reduce_mask(m.contiguous(), self.vae_scale_factor)
 
+    def encode_windows(self, mel, plan, mel_plan):
+        """The VAE moments of a long mel [B, 1, T, n_mel] fp32 as NCHW [B, 2C, rows, w] fp32: the mel plan's windows are gathered
+        (bf16, the rounding of the plain path's input cast), encoded as batch rows -- shapes the VAE is tuned and tested for -- and
+        the windows' MOMENTS (mean | logvar) blended linearly into the long layout by the latent plan's weights.  The posterior is
+        sampled once, on the long moments: blending samples instead would average independent draws and shrink the variance in the
+        overlaps.  A plan of one window is vae.encode(mel).latent_dist.parameters, bit for bit."""
+        B, _, T, n_mel = mel.shape
+        win = ops.window_gather(mel.contiguous().view(B, T, n_mel, 1), mel_plan.device(self.device))      # one channel: NCHW is NHWC
+        mom = ops.window_blend(self.vae.encode_nhwc(win).contiguous(), plan.device(self.device))          # [B, rows, w, 2C] fp32
+        return ops.nhwc_to_nchw_f32(mom)
+
     @torch.no_grad()
     def __call__(self, prompt=None, audio=None, sampling_rate=16000, strength=0.5, mask=None, audio_length_in_s=None,
                  num_inference_steps=50, guidance_scale=2.5, negative_prompt=None, num_waveforms_per_prompt=1, generator=None,
                  latents=None, prompt_embeds=None, negative_prompt_embeds=None, return_dict=True, output_type="np", adapter_names=None,
-                 adapter_weights=None):
+                 adapter_weights=None, window_length_in_s=None, window_overlap_in_s=None, loop=False, window_prompts=None,
+                 window_prompt_embeds=None):
+        """window_length_in_s / window_overlap_in_s / loop / window_prompts / window_prompt_embeds: as in AudioLDMPipeline.__call__
+        (None: one clip at the recording's own length, as ever).  With windows, `mask` and `latents` are those of the LONG clip, whose
+        length is audio_length_in_s or the recording's (a looped plan rounds it UP and the longer clip is returned)."""
         if self.device.type != "cuda":
             raise ops._lib.AldmError("AudioLDMAudioToAudioPipeline runs on the MI355X only: call .to('cuda') (no CPU fallback)")
         if audio is None:
@@ -120,6 +155,13 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
         if int(sampling_rate) != int(vc.sampling_rate):
             raise ValueError(f"audio at {sampling_rate} Hz: the vocoder runs at {vc.sampling_rate} Hz and there is no resampler here")
         _, begin = self.scheduler.get_timesteps(num_inference_steps, strength)    # raises on a strength that leaves no step
+        if window_length_in_s is None:
+            if loop or window_prompts is not None or window_prompt_embeds is not None or window_overlap_in_s is not None:
+                raise ValueError("loop / window_prompts / window_overlap_in_s need window_length_in_s")
+        elif prompt is None and prompt_embeds is None and window_prompt_embeds is not None:
+            prompt_embeds = window_prompt_embeds[:, 0]              # (batch size and the negative half come from the per-clip path)
+        elif prompt is None and prompt_embeds is None and window_prompts is not None:
+            prompt = [window_prompts[0]] if isinstance(window_prompts[0], str) else [p[0] for p in window_prompts]
         prompt_embeds, negative_prompt_embeds = self._prompt_embeds(prompt, prompt_embeds, negative_prompt, negative_prompt_embeds,
                                                                     guidance_scale, num_waveforms_per_prompt)
         batch = prompt_embeds.shape[0]
@@ -127,6 +169,15 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
         if audio_length_in_s is None:
             audio_length_in_s = wav.shape[-1] / float(vc.sampling_rate)
         height, n_samples = self.geometry(audio_length_in_s)
+        plan = mel_plan = None
+        if window_length_in_s is not None:
+            plan, mel_plan = self.window_plan(audio_length_in_s, window_length_in_s, window_overlap_in_s, loop)
+            height = plan.rows * self.vae_scale_factor
+            if loop:                                    # the whole rounded-up loop: trimming it would open the seam
+                n_samples = height * int(np.prod(vc.upsample_rates))
+            if window_prompts is not None or window_prompt_embeds is not None:
+                prompt_embeds = self._window_prompt_embeds(window_prompts, window_prompt_embeds, batch // num_waveforms_per_prompt, plan.K,
+                                                           num_waveforms_per_prompt)
         n_mel = vc.model_in_dim
         h, w = height // self.vae_scale_factor, n_mel // self.vae_scale_factor
         shape = (batch, self._unet.cfg["in_channels"], h, w)
@@ -136,16 +187,19 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
 
         # encode: log-mel front end (pads / crops to `height` frames) -> VAE moments -> posterior sample
         mel = LogMelFrontEnd(device=self.device, target_length=height, n_mel=n_mel)(wav.to(self.device))
-        dist = self.vae.encode(mel).latent_dist
-        if tuple(dist.mean.shape) != shape:
-            raise ValueError(f"the VAE encodes to {tuple(dist.mean.shape)}, the UNet expects {shape}")
+        if plan is None:
+            params = self.vae.encode(mel).latent_dist.parameters
+        else:
+            params = self.encode_windows(mel, plan, mel_plan)
+        if tuple(params.shape) != (shape[0], 2 * shape[1]) + shape[2:]:
+            raise ValueError(f"the VAE encodes to {tuple(params.chunk(2, dim=1)[0].shape)}, the UNet expects {shape}")
         # random draws, in this order, on the generator's device: the posterior noise, then eps (unless latents= gives it)
         gdev = generator.device if generator is not None else torch.device("cpu")
         post = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32)
         if latents is None:
             latents = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32)
         eps = latents.to(self.device, torch.float32).contiguous()
-        x0 = ops.gaussian_sample(dist.parameters.float(), post.to(self.device)) * self.vae.config.scaling_factor
+        x0 = ops.gaussian_sample(params.float(), post.to(self.device)) * self.vae.config.scaling_factor
         if float(strength) == 1.0:
             x = eps                                                   # diffusers' is_strength_max: pure noise, not a * x0 + s * eps
             if self.scheduler.init_noise_sigma != 1.0:                # (sigma-space schedulers start at init_noise_sigma * noise)
@@ -156,7 +210,11 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
             x = ops.add_noise(x0, eps, coef)
 
         gated, adapter_names, adapter_weights = self._route(adapter_names, adapter_weights, batch // num_waveforms_per_prompt, num_waveforms_per_prompt)
-        eng = self.engine(batch, h, w, num_inference_steps, guidance_scale, begin_index=begin, masked=m_lat is not None, gated=gated)
+        if plan is None:
+            eng = self.engine(batch, h, w, num_inference_steps, guidance_scale, begin_index=begin, masked=m_lat is not None, gated=gated)
+        else:
+            eng = self.engine(batch, h, w, num_inference_steps, guidance_scale, begin_index=begin, masked=m_lat is not None, gated=gated,
+                              plan=plan)
         eng.set_adapters(adapter_names, adapter_weights)
         eng.set_condition(prompt_embeds, negative_prompt_embeds)
         self._seed_engine(eng, generator)
@@ -166,13 +224,16 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
         if eng.graph is None and eng.use_graph:
             eng.capture()
         eng.run()
+        mel_out = None
         if output_type == "latent":
             out = eng.latents_nchw()
         else:
-            wav_out, _ = self.decode_latents_nhwc(eng.x)
+            wav_out, mel_out = self.decode_latents_nhwc(eng.x) if plan is None else self.decode_windows_nhwc(eng.x, plan, mel_plan, loop)
             out = wav_out[:, :n_samples]
             if output_type == "np":
                 out = out.float().cpu().numpy()
         if not return_dict:
             return (out,)
+        if plan is not None:                            # a windowed call also hands back its plan and the blended mel [B, T, 64] (device)
+            return AudioPipelineOutput(audios=out, plan=plan, mel=None if mel_out is None else mel_out[..., 0])
         return AudioPipelineOutput(audios=out)

@@ -367,7 +367,8 @@ __device__ __forceinline__ void window_blend_row(const Windows& w, const float* 
 // first dependent load needs; the unmasked ones carry no inpainting operand) and instantiate this frame with their solver.  They form
 // the thread index `tix` themselves: read in here, blockDim.x is not folded to the uniform workgroup size, and every wave starts with
 // one more dependent load.
-// WINDOWED (the four *_windowed kernels further down): eps and x_in are per window, x and the solver's state long (Windows above).
+// WINDOWED (the *_windowed[_masked] kernels further down): eps and x_in are per window, x and the solver's state long (Windows above);
+// with MASKED also x0, noise and the mask, and the scatter takes the blended value.
 template <class Solver, int VEC, bool MASKED, bool WINDOWED = false>
 __device__ __forceinline__ void step_fused_body(const float* __restrict__ eps, float* __restrict__ x, int B, long long n, int cfg, float g,
                                                 const float* __restrict__ coef, int* __restrict__ step_idx, bf16* __restrict__ x_in,
@@ -603,6 +604,66 @@ __global__ __launch_bounds__(256) void unipc_step_fused_windowed_kernel(const fl
   step_fused_body<UniPCSolver, VEC, false, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, UniPCSolver{state, step_idx, (long long)B * n}, table, row_elems, rowbias,
                                               timesteps, n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{},
                                               Windows{offset, cover, weight, K, KC, rows, hw, wc});
+}
+
+// The windowed MASKED fused steps (audio-to-audio on a long latent): the frame with MASKED and WINDOWED both.
+// x0, noise and the mask are LONG like x ([B][rows][W][C] and [B][rows][W]); the blend runs on the long value after the solver's update
+// and before the scatter, so every covering window receives the blended value.  Their own parameter list -- the windowed kernels',
+// then the inpainting operands behind the plan.
+template <int VEC>
+__global__ __launch_bounds__(256) void ddim_step_fused_windowed_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                              int cfg, float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                                              bf16* __restrict__ x_in, const float* __restrict__ table,
+                                                                              long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                                              int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket,
+                                                                              const int* offset, const int* cover, const float* weight, int K, int KC, int rows,
+                                                                              int hw, long long wc, const float* __restrict__ x0, const float* __restrict__ noise,
+                                                                              const float* __restrict__ mask, const float* __restrict__ blend, int C) {
+  step_fused_body<DdimSolver, VEC, true, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, DdimSolver{}, table, row_elems, rowbias, timesteps,
+      n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C},
+      Windows{offset, cover, weight, K, KC, rows, hw, wc});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void dpm_step_fused_windowed_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                             int cfg, float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                                             bf16* __restrict__ x_in, float* __restrict__ hist, const float* __restrict__ table,
+                                                                             long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                                             int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket,
+                                                                             const int* offset, const int* cover, const float* weight, int K, int KC, int rows,
+                                                                             int hw, long long wc, const float* __restrict__ x0, const float* __restrict__ noise,
+                                                                             const float* __restrict__ mask, const float* __restrict__ blend, int C) {
+  step_fused_body<DpmSolver, VEC, true, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, DpmSolver{hist}, table, row_elems, rowbias, timesteps,
+      n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C},
+      Windows{offset, cover, weight, K, KC, rows, hw, wc});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void euler_a_step_fused_windowed_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                                 int cfg, float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                                                 bf16* __restrict__ x_in, uint32_t* __restrict__ rng, const float* __restrict__ table,
+                                                                                 long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                                                 int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket,
+                                                                                 const int* offset, const int* cover, const float* weight, int K, int KC, int rows,
+                                                                                 int hw, long long wc, const float* __restrict__ x0, const float* __restrict__ noise,
+                                                                                 const float* __restrict__ mask, const float* __restrict__ blend, int C) {
+  step_fused_body<EulerASolver, VEC, true, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, EulerASolver{rng}, table, row_elems, rowbias, timesteps,
+      n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C},
+      Windows{offset, cover, weight, K, KC, rows, hw, wc});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void unipc_step_fused_windowed_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                               int cfg, float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                                               bf16* __restrict__ x_in, float* __restrict__ state, const float* __restrict__ table,
+                                                                               long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                                               int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket,
+                                                                               const int* offset, const int* cover, const float* weight, int K, int KC, int rows,
+                                                                               int hw, long long wc, const float* __restrict__ x0, const float* __restrict__ noise,
+                                                                               const float* __restrict__ mask, const float* __restrict__ blend, int C) {
+  step_fused_body<UniPCSolver, VEC, true, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, UniPCSolver{state, step_idx, (long long)B * n}, table, row_elems, rowbias, timesteps,
+      n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C},
+      Windows{offset, cover, weight, K, KC, rows, hw, wc});
 }
 
 // windows out of the long tensor: out[b * K + k][i][:] = x[b][(offset[k] + i) mod rows][:] * mul, bf16 (the UNet / VAE input: the
@@ -1188,6 +1249,77 @@ extern "C" int aldm_unipc_step_fused_windowed(const float* eps, float* x, int B,
   return launch_step_fused_windowed<UniPCSolver>("unipc_step_fused_windowed", unipc_step_fused_windowed_kernel<4>,
                                                  unipc_step_fused_windowed_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef, step_idx,
                                                  x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan, stream, state);
+}
+
+// launch_step_fused_windowed for the masked windowed kernels: its checks joined with launch_step_fused<.., true>'s (the inpainting
+// operands, n % C == 0, the 32-bit mask index), and the inpainting operands behind the plan.  A rejected call launches nothing.
+template <class Solver, class Kernel, class... Op>
+static int launch_step_fused_windowed_masked(const char* name, Kernel k4, Kernel k1, const float* eps, float* x, int B, long long n_per_sample,
+                                             int cfg, float guidance, const float* coef, int* step_idx, void* x_in_bf16, const float* table,
+                                             long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                             unsigned* ticket, const aldm_window_plan_t* plan, const Inpaint& ip, void* stream, Op... op) {
+  ALDM_CHECK_ARG(eps && x && coef && step_idx && (... && op) && B > 0 && n_per_sample > 0 && n_steps > 0, "%s: bad args", name);
+  ALDM_CHECK_ARG(Solver::TICKET_OPTIONAL || ticket, "%s: bad args", name);
+  ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "%s: the counter advance needs timesteps and t_out", name);
+  ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
+                 "%s: table needs ticket, rowbias and row_elems %% 4 == 0", name);
+  ALDM_CHECK_ARG(ip.x0 && ip.noise && ip.mask && ip.blend && ip.C > 0 && n_per_sample % ip.C == 0 && (long long)B * n_per_sample < (1ll << 31),
+                 "%s: bad inpainting args", name);
+  long long wc;
+  if (const int rc = check_window_plan(name, plan, B, n_per_sample, true, &wc)) return rc;
+  if (!table) row_elems = 0;
+  const long long total = (long long)B * n_per_sample;
+  const bool v4 = wc % 4 == 0;
+  const long long items = v4 ? total / 4 : total;
+  const long long work = items > row_elems / 4 ? items : row_elems / 4;
+  hipLaunchKernelGGL(v4 ? k4 : k1, dim3(blocks_for(work, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, B, n_per_sample, cfg, guidance, coef,
+                     step_idx, (bf16*)x_in_bf16, op..., table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan->offset,
+                     plan->cover, plan->weight, plan->K, plan->KC, plan->rows, plan->hw, wc, ip.x0, ip.noise, ip.mask, ip.blend, ip.C);
+  return aldm_launch_status(name);
+}
+
+extern "C" int aldm_ddim_step_fused_windowed_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                                    const float* coef, int* step_idx, void* x_in_bf16, const float* table,
+                                                    long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                                    unsigned* ticket, const aldm_window_plan_t* plan, const float* x0, const float* noise,
+                                                    const float* mask, const float* blend, int channels, void* stream) {
+  return launch_step_fused_windowed_masked<DdimSolver>("ddim_step_fused_windowed_masked", ddim_step_fused_windowed_masked_kernel<4>,
+                                                ddim_step_fused_windowed_masked_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef,
+                                                step_idx, x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan,
+                                                Inpaint{x0, noise, mask, blend, channels}, stream);
+}
+
+extern "C" int aldm_dpm_step_fused_windowed_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                                   const float* coef, int* step_idx, void* x_in_bf16, float* hist, const float* table,
+                                                   long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                                   unsigned* ticket, const aldm_window_plan_t* plan, const float* x0, const float* noise,
+                                                   const float* mask, const float* blend, int channels, void* stream) {
+  return launch_step_fused_windowed_masked<DpmSolver>("dpm_step_fused_windowed_masked", dpm_step_fused_windowed_masked_kernel<4>,
+                                                dpm_step_fused_windowed_masked_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef,
+                                                step_idx, x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan,
+                                                Inpaint{x0, noise, mask, blend, channels}, stream, hist);
+}
+
+extern "C" int aldm_euler_a_step_fused_windowed_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                                       const float* coef, int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table,
+                                                       long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                                       unsigned* ticket, const aldm_window_plan_t* plan, const float* x0, const float* noise,
+                                                       const float* mask, const float* blend, int channels, void* stream) {
+  return launch_step_fused_windowed_masked<EulerASolver>("euler_a_step_fused_windowed_masked", euler_a_step_fused_windowed_masked_kernel<4>,
+                                                euler_a_step_fused_windowed_masked_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef,
+                                                step_idx, x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan,
+                                                Inpaint{x0, noise, mask, blend, channels}, stream, rng_state);
+}
+
+extern "C" int aldm_unipc_step_fused_windowed_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                                     const float* coef, int* step_idx, void* x_in_bf16, float* state, const float* table,
+                                                     long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                                     unsigned* ticket, const aldm_window_plan_t* plan, const float* x0, const float* noise,
+                                                     const float* mask, const float* blend, int channels, void* stream) {
+  return launch_step_fused_windowed_masked<UniPCSolver>("unipc_step_fused_windowed_masked", unipc_step_fused_windowed_masked_kernel<4>,
+                                                unipc_step_fused_windowed_masked_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef,
+                                                step_idx, x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan,
+                                                Inpaint{x0, noise, mask, blend, channels}, stream, state);
 }
 
 extern "C" int aldm_add_noise(const float* x, const float* noise, const float* coef, int B, long long n_per_sample,

@@ -24,6 +24,8 @@ Multi-adapter LoRA: a gated engine's UNet launches read a
 Long-form generation: WindowedDenoiseEngine keeps ONE long latent [B, rows, W, C] and runs the UNet on K
 overlapping windows of the trained length as batch rows; the windowed fused step (ops.*_step_fused_windowed) blends the windows' eps
 into the long latent, updates it and scatters the next UNet input back into every window -- still one launch behind the UNet.
+Long-form audio-to-audio: WindowedAudioToAudioEngine is that engine on a suffix of the schedule, with the
+inpainting blend on the long latent inside the same launch (ops.*_step_fused_windowed_masked).
 """
 import torch
 
@@ -309,21 +311,25 @@ class WindowedDenoiseEngine(DenoiseEngine):
     UNet's batch rows, shapes it is tuned for.  x, hist, state and the Philox stream stay in the long layout [B, rows, W, C]; x_in,
     the class labels, the time-embedding table and the gate table have one row per (clip, window): 2 * B * K under CFG, all in ONE
     UNet call (no sub-batching: activation memory grows with K).  A plan of one window is DenoiseEngine, bit
-    for bit.  Audio-to-audio on long clips is not built: chains > 1, masked and begin_index > 0 raise."""
+    for bit.  This class starts from noise: chains > 1, masked and begin_index > 0 raise (WindowedAudioToAudioEngine below takes the
+    last two)."""
+    _AUDIO_TO_AUDIO = False
 
     def __init__(self, unet, scheduler, batch, plan, width, num_inference_steps, guidance_scale=2.5, device="cuda", use_graph=True,
                  chains=None, begin_index=0, masked=False, gated=False):
         if chains not in (None, 1):
-            raise NotImplementedError("WindowedDenoiseEngine: chains > 1 is not built (the windows already fill the batch)")
-        if masked or begin_index:
-            raise NotImplementedError("WindowedDenoiseEngine: masked / begun (audio-to-audio) runs on a long latent are not built")
+            raise NotImplementedError(f"{type(self).__name__}: chains > 1 is not built (the windows already fill the batch)")
+        if (masked or begin_index) and not self._AUDIO_TO_AUDIO:
+            raise NotImplementedError("WindowedDenoiseEngine: masked / begun (audio-to-audio) runs on a long latent take a "
+                                      "WindowedAudioToAudioEngine")
         self.plan, self.K, self.hw = plan, plan.K, plan.window_rows
         super().__init__(unet, scheduler, batch, plan.rows, width, num_inference_steps, guidance_scale, device=device, use_graph=use_graph,
-                         gated=gated)
+                         begin_index=begin_index, masked=masked, gated=gated)
         self.bc = batch * self.K                                  # rows per CFG half of everything the UNet sees
         self.x_in = [torch.zeros((2 if self.cfg else 1) * self.bc, self.hw, width, self.C, dtype=torch.bfloat16, device=self.dev)]
         self._win = plan.device(self.dev)                         # offset / cover / weight tables (the plan keeps them alive)
-        self._step = getattr(ops, self._step.__name__ + "_windowed")
+        solver = "euler_a" if self.euler else "dpm" if self.dpm else "unipc" if self.unipc else "ddim"
+        self._step = getattr(ops, solver + "_step_fused_windowed" + ("_masked" if self.masked else ""))
 
     def _per_window(self, entries, what):
         """one entry per clip, or one per (clip, window) in that order -> one per (clip, window)"""
@@ -396,4 +402,21 @@ class WindowedDenoiseEngine(DenoiseEngine):
         # one UNet call on all windows, then the windowed fused step: blend, update, scatter, next row, counter -- one launch
         eps = self.unet.forward_nhwc(self.x_in[0], self.t_buf, self.cls[0], rowbias=self.rowbias[0], gate=self._gate(0))
         self._step(eps, self.x, self.cfg, self.g, self.coef, self.step_idx, self.x_in[0], *self._solver_args, self.temb[0], self.rowbias[0],
-                   self.timesteps_f32, self.t_buf, self.ticket, self._win)
+                   self.timesteps_f32, self.t_buf, self.ticket, self._win, *self._inpaint_args)
+
+
+class WindowedAudioToAudioEngine(WindowedDenoiseEngine):
+    """WindowedDenoiseEngine that starts from a recording: `begin_index` runs the suffix timesteps[begin:] --
+    its coefficient table, timesteps and Euler-ancestral's first input scale exactly as DenoiseEngine derives them -- and `masked`
+    swaps in ops.*_step_fused_windowed_masked, whose x0, noise and mask [B, rows, W] are LONG like x (set_inpaint takes the long
+    tensors).  A step stays one UNet call on all windows plus one launch, the loop one captured graph; a plan of one window is
+    DenoiseEngine(begin_index, masked), bit for bit.  chains > 1 stays refused."""
+    _AUDIO_TO_AUDIO = True
+
+    def set_inpaint(self, x0_nchw_long, noise_nchw_long, mask_long):
+        """x0 and noise [B, C, rows, W] fp32 and mask [B, rows, W] of the LONG clip (DenoiseEngine.set_inpaint otherwise)."""
+        want = (self.B, self.C, self.H, self.W)
+        for name, t in (("x0", x0_nchw_long), ("noise", noise_nchw_long)):
+            if tuple(t.shape) != want:
+                raise ValueError(f"{name} shape {tuple(t.shape)}, expected the long clip's {want}")
+        super().set_inpaint(x0_nchw_long, noise_nchw_long, mask_long)

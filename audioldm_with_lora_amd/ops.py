@@ -1457,9 +1457,11 @@ def window_blend(win, plan, out=None):
     return out
 
 
-def _step_fused_windowed(solver, eps, x, cfg, guidance, coef, step_idx, x_in, operand, table, rowbias, timesteps_f32, t_out, ticket, plan):
+def _step_fused_windowed(solver, eps, x, cfg, guidance, coef, step_idx, x_in, operand, table, rowbias, timesteps_f32, t_out, ticket, plan,
+                         inpaint=None):
     """The frame of the four windowed fused steps (launch_step_fused_windowed): _step_fused's checks with eps and x_in per window.
-    x fp32 [B, rows, W, C] long; eps fp32 [halves * B * K, hw, W, C]; x_in bf16 of eps's shape (or None)."""
+    x fp32 [B, rows, W, C] long; eps fp32 [halves * B * K, hw, W, C]; x_in bf16 of eps's shape (or None).  inpaint: None or the LONG
+    (x0, noise, mask, blend) of aldm_<solver>_step_fused_windowed_masked."""
     coef_cols, flops, solver_bytes, ticket_optional = _STEP_SOLVERS[solver]
     _require_gpu(x)
     B = x.shape[0]
@@ -1475,11 +1477,20 @@ def _step_fused_windowed(solver, eps, x, cfg, guidance, coef, step_idx, x_in, op
     n_steps = timesteps_f32.numel() if timesteps_f32 is not None else coef.shape[0]
     name = f"{solver}_step_fused_windowed"
     args = _window_plan(plan)
+    flops = flops + 4.0 * halves
+    long_bytes = 8.0 + solver_bytes
+    tail = ()
+    if inpaint is not None:
+        assert x.dim() >= 2, "x: channels-last [B, rows, W, C]"
+        ch = _inpaint_args(x, *inpaint, n_steps)
+        name, flops = name + "_masked", flops + 4.0
+        long_bytes = long_bytes + 8.0 + 4.0 / ch             # the three extra long reads: x0 and noise (4 B each), the mask (4 B per pixel)
+        tail = (*map(_p, inpaint), ch)
     fn = getattr(_lib.load(), "aldm_" + name)
     # bytes: every window's eps and bf16 input (1 or 2 halves), x read / write and the solver's per long element, the table row
-    check(_launch(name, (flops + 4.0 * halves) * x.numel(), 6.0 * eps.numel() + (8.0 + solver_bytes) * x.numel() + 8.0 * row,
+    check(_launch(name, flops * x.numel(), 6.0 * eps.numel() + long_bytes * x.numel() + 8.0 * row,
                   lambda: fn(_p(eps), _p(x), B, n, int(cfg), guidance, _p(coef), _p(step_idx), _p(x_in), *map(_p, operand), _p(table), row,
-                             _p(rowbias), _p(timesteps_f32), n_steps, _p(t_out), _p(ticket), C.byref(args), _stream())), "aldm_" + name)
+                             _p(rowbias), _p(timesteps_f32), n_steps, _p(t_out), _p(ticket), C.byref(args), *tail, _stream())), "aldm_" + name)
 
 
 def ddim_step_fused_windowed(eps, x, cfg, guidance, coef, step_idx, x_in, table, rowbias, timesteps_f32, t_out, ticket, plan):
@@ -1504,6 +1515,39 @@ def euler_a_step_fused_windowed(eps, x, cfg, guidance, coef, step_idx, x_in, rng
     """euler_a_step_fused on a long latent (aldm_euler_a_step_fused_windowed): element i of the LONG latent is element i of the draw."""
     _check_state(rng_state)
     _step_fused_windowed("euler_a", eps, x, cfg, guidance, coef, step_idx, x_in, (rng_state,), table, rowbias, timesteps_f32, t_out, ticket, plan)
+
+
+def ddim_step_fused_windowed_masked(eps, x, cfg, guidance, coef, step_idx, x_in, table, rowbias, timesteps_f32, t_out, ticket, plan, x0, noise,
+                                    mask, blend):
+    """ddim_step_fused_windowed followed by the inpainting blend on the long latent, before the scatter
+    (aldm_ddim_step_fused_windowed_masked).  x0, noise fp32 [B, rows, W, C] and mask fp32 [B, rows, W] are long like x; blend fp32
+    [n_steps, 2].  Every covering window receives the bf16 of the BLENDED value."""
+    _step_fused_windowed("ddim", eps, x, cfg, guidance, coef, step_idx, x_in, (), table, rowbias, timesteps_f32, t_out, ticket, plan,
+                         (x0, noise, mask, blend))
+
+
+def dpm_step_fused_windowed_masked(eps, x, cfg, guidance, coef, step_idx, x_in, hist, table, rowbias, timesteps_f32, t_out, ticket, plan, x0,
+                                   noise, mask, blend):
+    """dpm_step_fused_windowed with the inpainting blend (aldm_dpm_step_fused_windowed_masked); hist long, receives unblended values."""
+    assert hist.dtype == torch.float32 and hist.numel() == x.numel()
+    _step_fused_windowed("dpm", eps, x, cfg, guidance, coef, step_idx, x_in, (hist,), table, rowbias, timesteps_f32, t_out, ticket, plan,
+                         (x0, noise, mask, blend))
+
+
+def unipc_step_fused_windowed_masked(eps, x, cfg, guidance, coef, step_idx, x_in, state, table, rowbias, timesteps_f32, t_out, ticket, plan, x0,
+                                     noise, mask, blend):
+    """unipc_step_fused_windowed with the inpainting blend (aldm_unipc_step_fused_windowed_masked); state long, receives unblended values."""
+    _check_unipc_state(state, x)
+    _step_fused_windowed("unipc", eps, x, cfg, guidance, coef, step_idx, x_in, (state,), table, rowbias, timesteps_f32, t_out, ticket, plan,
+                         (x0, noise, mask, blend))
+
+
+def euler_a_step_fused_windowed_masked(eps, x, cfg, guidance, coef, step_idx, x_in, rng_state, table, rowbias, timesteps_f32, t_out, ticket, plan,
+                                       x0, noise, mask, blend):
+    """euler_a_step_fused_windowed with the inpainting blend (aldm_euler_a_step_fused_windowed_masked); blend rows (1, sigma_next)."""
+    _check_state(rng_state)
+    _step_fused_windowed("euler_a", eps, x, cfg, guidance, coef, step_idx, x_in, (rng_state,), table, rowbias, timesteps_f32, t_out, ticket, plan,
+                         (x0, noise, mask, blend))
 
 
 def add_noise(x, noise, coef):

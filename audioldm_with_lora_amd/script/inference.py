@@ -18,6 +18,9 @@ captured graph: the adapted and the original model of the reference's log_valida
 `--audio-length 60 --window-seconds 10.24 --window-overlap-seconds 2.56` generates a clip longer than the model was trained on by
 windowed denoising (overlapping windows of the trained length along one long latent, blended at every step); `--loop` makes it close
 on itself (the length is rounded up to a whole number of window strides); `--window-prompts "a|b|c"` gives every window its own prompt.
+`--init-audio in.wav --window-seconds 10.24` restyles or inpaints a recording of any length the same way (`--strength`,
+`--regenerate-seconds`, `--regenerate-bands`, `--loop` and `--window-prompts` apply); `--extend-to-seconds T` keeps the recording and
+generates what follows it up to T seconds.
 """
 import argparse
 import os
@@ -26,7 +29,7 @@ import numpy as np
 import torch
 
 from ..lora import LoraConfig, get_peft_model
-from ..audio2audio import AudioLDMAudioToAudioPipeline, regeneration_mask
+from ..audio2audio import AudioLDMAudioToAudioPipeline, continuation_mask, regeneration_mask
 from ..pipeline import AudioLDMPipeline
 from ..scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, UniPCMultistepScheduler
 from ..unet import UNet2DConditionModel
@@ -61,7 +64,8 @@ def parse_adapters(spec):
     return out
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """the command line, checked: what needs another flag exits here (SystemExit), before any model is loaded"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--model-dir", required=True, help="local diffusers-format directory of cvssp/audioldm-s-full-v2")
     ap.add_argument("--lora-weights", default=None, help="checkpoint-*/model.safetensors written by the trainer")
@@ -90,6 +94,8 @@ def main(argv=None):
     ap.add_argument("--strength", type=float, default=0.5, help="with --init-audio: how much of the schedule to run (1 = from noise)")
     ap.add_argument("--regenerate-seconds", default=None, help="with --init-audio: T0,T1 -- regenerate only this time span")
     ap.add_argument("--regenerate-bands", default=None, help="with --init-audio: F0,F1 -- regenerate only this fraction of the mel bins")
+    ap.add_argument("--extend-to-seconds", type=float, default=None, metavar="T",
+                    help="with --init-audio and --window-seconds: keep the recording and generate up to T seconds after it")
     ap.add_argument("--lora", action="append", default=[], metavar="NAME=PATH",
                     help="load a named adapter (.safetensors / .bin file or directory; repeatable).  Rank and targets come from the tensors")
     ap.add_argument("--adapters", default=None, metavar="SPEC",
@@ -101,9 +107,22 @@ def main(argv=None):
         ap.error("--regenerate-seconds / --regenerate-bands need --init-audio")
     if args.window_seconds is None and (args.loop or args.window_prompts or args.window_overlap_seconds is not None):
         ap.error("--loop / --window-prompts / --window-overlap-seconds need --window-seconds")
-    if args.window_seconds is not None and (args.init_audio is not None or args.adapters is not None):
-        ap.error("--window-seconds runs text-to-audio only (no --init-audio, no --adapters)")
+    if args.extend_to_seconds is not None:
+        if args.init_audio is None or args.window_seconds is None:
+            ap.error("--extend-to-seconds needs --init-audio and --window-seconds")
+        if args.regenerate_seconds or args.regenerate_bands:
+            ap.error("--extend-to-seconds builds its own mask (no --regenerate-seconds / --regenerate-bands)")
+        if args.extend_to_seconds <= 0:
+            ap.error("--extend-to-seconds expects a positive number of seconds")
+    for item in args.lora:
+        name, sep, path = item.partition("=")
+        if not sep or not name or not path:
+            ap.error(f"--lora expects NAME=PATH, got {item!r}")
+    return args
 
+
+def main(argv=None):
+    args = parse_args(argv)
     device = "cuda"
     unet = UNet2DConditionModel.from_pretrained(args.model_dir, subfolder="unet")
     if not args.no_lora and not args.lora:
@@ -122,19 +141,27 @@ def main(argv=None):
         pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, algorithm_type=args.scheduler,
                                                                  solver_order=args.solver_order, **extra)
     for item in args.lora:
-        name, sep, path = item.partition("=")
-        if not sep or not name or not path:
-            ap.error(f"--lora expects NAME=PATH, got {item!r}")
+        name, _, path = item.partition("=")
         pipe.load_lora_weights(path, adapter_name=name)
     generator = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
+    windowed = {}
+    if args.window_seconds is not None:
+        windowed = dict(window_length_in_s=args.window_seconds, window_overlap_in_s=args.window_overlap_seconds, loop=args.loop)
+        if args.window_prompts:
+            windowed["window_prompts"] = [p.strip() for p in args.window_prompts.split("|")]
     if args.adapters is not None:
         routing = parse_adapters(args.adapters)
         prompts = [p.strip() for p in args.prompt.split("|")]
         if len(prompts) == 1:
             prompts = prompts * len(routing)
-        audios = pipe(prompt=prompts, num_inference_steps=args.steps, adapter_names=routing,
-                      audio_length_in_s=10.0 if args.audio_length is None else args.audio_length,
-                      guidance_scale=args.guidance_scale, generator=generator).audios
+        if "window_prompts" in windowed:                # the same prompt schedule for every routed clip
+            windowed["window_prompts"] = [windowed["window_prompts"]] * len(prompts)
+        if args.init_audio is not None and windowed:
+            audios = _audio_to_audio(pipe, args, generator, windowed, prompt=prompts, adapter_names=routing)
+        else:
+            audios = pipe(prompt=prompts, num_inference_steps=args.steps, adapter_names=routing,
+                          audio_length_in_s=10.0 if args.audio_length is None else args.audio_length,
+                          guidance_scale=args.guidance_scale, generator=generator, **windowed).audios
         from scipy.io import wavfile
         stem, ext = os.path.splitext(os.path.abspath(args.output))
         os.makedirs(os.path.dirname(stem), exist_ok=True)
@@ -143,16 +170,11 @@ def main(argv=None):
         print(f"Generated {len(audios)} clips saved to: {stem}_*{ext or '.wav'}")
         return
     if args.init_audio is None:
-        windowed = {}
-        if args.window_seconds is not None:
-            windowed = dict(window_length_in_s=args.window_seconds, window_overlap_in_s=args.window_overlap_seconds, loop=args.loop)
-            if args.window_prompts:
-                windowed["window_prompts"] = [p.strip() for p in args.window_prompts.split("|")]
         audio = pipe(prompt=args.prompt, num_inference_steps=args.steps,
                      audio_length_in_s=10.0 if args.audio_length is None else args.audio_length,
                      guidance_scale=args.guidance_scale, generator=generator, **windowed).audios[0]
     else:
-        audio = _audio_to_audio(pipe, args, generator)
+        audio = _audio_to_audio(pipe, args, generator, windowed)[0]
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     from scipy.io import wavfile
     wavfile.write(args.output, 16000, np.asarray(audio, dtype=np.float32))
@@ -185,18 +207,32 @@ def read_wav(path):
     return sr, wav
 
 
-def _audio_to_audio(pipe, args, generator):
+def _audio_to_audio(pipe, args, generator, windowed=None, **routed):
+    """the clips of an --init-audio call; windowed: the window keywords of a --window-seconds call; routed: prompt= / adapter_names= of
+    an --adapters call (one clip per routing entry, all from the same recording)"""
     sr, wav = read_wav(args.init_audio)
     a2a = AudioLDMAudioToAudioPipeline.from_pipe(pipe)
-    seconds = wav.shape[0] / float(sr) if args.audio_length is None else args.audio_length
-    mask = None
-    if args.regenerate_seconds or args.regenerate_bands:
+    windowed = dict(windowed or {})
+    recording = wav.shape[0] / float(sr)
+    seconds = recording if args.audio_length is None else args.audio_length
+    strength = args.strength
+    if args.extend_to_seconds is not None:
+        seconds, strength = args.extend_to_seconds, 1.0
+    n_mel = a2a.vocoder.config.model_in_dim
+    if windowed:                                        # the mask is the LONG clip's (a looped plan rounds its length up)
+        height = a2a.window_plan(seconds, windowed["window_length_in_s"], windowed["window_overlap_in_s"], windowed["loop"])[0].rows * a2a.vae_scale_factor
+    else:
         height, _ = a2a.geometry(seconds)
-        mask = regeneration_mask(height, a2a.vocoder.config.model_in_dim,
+    mask = None
+    if args.extend_to_seconds is not None:
+        mask = continuation_mask(height, n_mel, recording)
+    elif args.regenerate_seconds or args.regenerate_bands:
+        mask = regeneration_mask(height, n_mel,
                                  seconds=_pair(args.regenerate_seconds, "--regenerate-seconds") if args.regenerate_seconds else None,
                                  bands=_pair(args.regenerate_bands, "--regenerate-bands") if args.regenerate_bands else None)
-    return a2a(prompt=args.prompt, audio=wav, sampling_rate=sr, strength=args.strength, mask=mask, audio_length_in_s=seconds,
-               num_inference_steps=args.steps, guidance_scale=args.guidance_scale, generator=generator).audios[0]
+    routed.setdefault("prompt", args.prompt)
+    return a2a(audio=wav, sampling_rate=sr, strength=strength, mask=mask, audio_length_in_s=seconds, num_inference_steps=args.steps,
+               guidance_scale=args.guidance_scale, generator=generator, **windowed, **routed).audios
 
 
 if __name__ == "__main__":

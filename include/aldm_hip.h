@@ -531,6 +531,33 @@ int aldm_unipc_step_fused_windowed(const float* eps, float* x, int B, long long 
                                    int* step_idx, void* x_in_bf16, float* state, const float* table, long long row_elems, float* rowbias,
                                    const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const aldm_window_plan_t* plan,
                                    void* stream);
+/* The windowed fused steps with the inpainting blend (audio-to-audio on a long latent): aldm_*_step_fused_windowed followed by the blend
+   of aldm_*_step_fused_masked on the LONG value, before the scatter.  x0, noise fp32 [B][rows][wc] and mask fp32 [B][rows][wc / channels]
+   are long like x; blend fp32 [n_steps][2].  In a thread: the windows' eps halves are blended, the solver updates, the inpainting blend
+   is applied, and the bf16 of the blended value goes into every covering window, both CFG halves.  hist / state receive unblended
+   values.  The checks of both parents hold (n_per_sample % channels == 0, B * n_per_sample < 2^31, the plan against its tables,
+   KC <= 4); a rejected call launches nothing.  An all-ones mask is the unmasked windowed launch and a plan of one window is the
+   plain masked launch, both bit for bit. */
+int aldm_ddim_step_fused_windowed_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                         const float* coef, int* step_idx, void* x_in_bf16, const float* table, long long row_elems,
+                                         float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket,
+                                         const aldm_window_plan_t* plan, const float* x0, const float* noise, const float* mask,
+                                         const float* blend, int channels, void* stream);
+int aldm_dpm_step_fused_windowed_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                        const float* coef, int* step_idx, void* x_in_bf16, float* hist, const float* table, long long row_elems,
+                                        float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket,
+                                        const aldm_window_plan_t* plan, const float* x0, const float* noise, const float* mask,
+                                        const float* blend, int channels, void* stream);
+int aldm_euler_a_step_fused_windowed_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                            const float* coef, int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table, long long row_elems,
+                                            float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket,
+                                            const aldm_window_plan_t* plan, const float* x0, const float* noise, const float* mask,
+                                            const float* blend, int channels, void* stream);
+int aldm_unipc_step_fused_windowed_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                          const float* coef, int* step_idx, void* x_in_bf16, float* state, const float* table, long long row_elems,
+                                          float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket,
+                                          const aldm_window_plan_t* plan, const float* x0, const float* noise, const float* mask,
+                                          const float* blend, int channels, void* stream);
 /* measurement aid: keeps `stream` busy for ~us microseconds so that later launches queue up behind it (bench.py) */
 int aldm_sleep_us(int us, void* stream);
 /* device-side loop counter for graph replay: step_idx[0] = (step_idx[0] + 1) mod n_steps ; t_out[0] = timesteps[step_idx[0]] */

@@ -12,6 +12,18 @@ Prints one JSON line:
   pipe_ms                            one whole pipe(...) call, windowed (second call: engine built, graph captured)
   unwindowed                         whether pipe(audio_length_in_s=seconds) WITHOUT windows runs at all on this tree -- the UNet's
                                      self-attention over all 1500 x 16 tokens, the VAE's wide head -- and its time if it does
+
+    python tools/bench_longform.py --audio-to-audio [--seconds 60] [--steps 20] [--reps 20]
+
+The audio-to-audio leg instead: a synthetic recording of `seconds`, strength 0.5 (the second half of `steps`),
+the middle third regenerated.  One JSON line:
+  first_a2a_ms_incl_capture, a2a_ms  the first call of a2a(...) (engine built, graph captured) and a later one
+  encode_ms                          the one-off windowed encode: log-mel, gather, VAE encoder on the windows, moment blend, sample
+  launches_per_step, ms_per_step     one masked windowed denoise step, as above
+  masked_windowed_step_us / windowed_step_us / plain_masked_step_us
+                                     the masked windowed launch, the unmasked windowed launch and the plain masked launch at the same
+                                     number of eps bytes, each inside one replayed graph, in this one run
+  extra_long_bytes                   what the masked windowed launch reads on top of the unmasked one: x0, noise and the mask
 """
 import argparse
 import json
@@ -50,6 +62,79 @@ def in_graph_us(fn, reps):
     return best
 
 
+def audio_to_audio_leg(args, pipe, plan, pe, ne, guidance):
+    """the measurements of the --audio-to-audio leg (module docstring) as a dict"""
+    import numpy as np
+    from audioldm_with_lora_amd import ops
+    from audioldm_with_lora_amd.audio2audio import AudioLDMAudioToAudioPipeline, regeneration_mask
+    from audioldm_with_lora_amd.mel import LogMelFrontEnd
+    a2a = AudioLDMAudioToAudioPipeline.from_pipe(pipe)
+    n = int(args.seconds * 16000)
+    t = torch.arange(n) / 16000.0
+    wav = 0.3 * torch.sin(2 * np.pi * 220.0 * t) + 0.05 * torch.randn(n, generator=torch.Generator().manual_seed(3))
+    frames = plan.rows * a2a.vae_scale_factor
+    mask = regeneration_mask(frames, 64, seconds=(args.seconds / 3, 2 * args.seconds / 3))
+    call = dict(prompt_embeds=pe, negative_prompt_embeds=ne, audio=wav, strength=0.5, mask=mask, num_inference_steps=args.steps,
+                guidance_scale=guidance, window_length_in_s=args.window_seconds, window_overlap_in_s=args.overlap_seconds)
+    res = {"what": "long-form audio-to-audio, full-width UNet + rank-4 LoRA, random-init weights, B = 1, CFG 2.5, DDIM, strength 0.5, masked",
+           "seconds": args.seconds, "rows": plan.rows, "windows": plan.K, "steps": args.steps}
+    t0 = time.perf_counter()
+    audio = a2a(generator=torch.Generator().manual_seed(1), **call).audios
+    torch.cuda.synchronize()
+    res["first_a2a_ms_incl_capture"] = round((time.perf_counter() - t0) * 1e3, 1)
+    assert audio.shape == (1, n) and bool((audio == audio).all())
+    t0 = time.perf_counter()
+    a2a(generator=torch.Generator().manual_seed(1), **call)
+    torch.cuda.synchronize()
+    res["a2a_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+
+    # the one-off windowed encode
+    _, mel_plan = a2a.window_plan(args.seconds, args.window_seconds, args.overlap_seconds)
+    front = LogMelFrontEnd(device="cuda", target_length=frames, n_mel=64)
+    post = torch.randn(1, 8, plan.rows, 16, device="cuda")
+    wav_dev = wav[None].cuda()
+    encode = lambda: ops.gaussian_sample(a2a.encode_windows(front(wav_dev), plan, mel_plan), post)
+    encode()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(); encode(); e1.record(); torch.cuda.synchronize()
+    res["encode_ms"] = round(e0.elapsed_time(e1), 3)
+
+    # the step: launches counted on one eager step, replays timed
+    _, begin = a2a.scheduler.get_timesteps(args.steps, 0.5)
+    eng = a2a.engine(1, plan.rows, 16, args.steps, guidance, begin_index=begin, masked=True, plan=plan)
+    x = torch.randn(1, 8, plan.rows, 16)
+    eng.set_latents(x)
+    ops.PROFILE = []
+    eng._one_step()
+    torch.cuda.synchronize()
+    res["launches_per_step"], ops.PROFILE = len(ops.PROFILE), None
+    eng.set_latents(x)
+    torch.cuda.synchronize()
+    e0.record(); eng.run(); e1.record(); torch.cuda.synchronize()
+    res["suffix_steps"], res["ms_per_step"] = eng.n_steps, round(e0.elapsed_time(e1) / eng.n_steps, 3)
+
+    # the three launches at the same number of eps bytes, in this one run
+    K, hw = plan.K, plan.window_rows
+    eps = torch.randn(2 * K, hw, 16, 8, device="cuda")
+    win = plan.device("cuda")
+    x_long, x_plain = torch.randn(1, plan.rows, 16, 8, device="cuda"), torch.randn(K, hw, 16, 8, device="cuda")
+    long_in = (torch.randn_like(x_long), torch.randn_like(x_long), torch.rand(1, plan.rows, 16, device="cuda"), eng.blend)
+    plain_in = (torch.randn_like(x_plain), torch.randn_like(x_plain), torch.rand(K, hw, 16, device="cuda"), eng.blend)
+    xin = torch.zeros(2 * K, hw, 16, 8, dtype=torch.bfloat16, device="cuda")
+    idx, tb, ticket = torch.zeros(1, dtype=torch.int32, device="cuda"), torch.zeros(1, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+    frame = (eng.temb[0], eng.rowbias[0], eng.timesteps_f32, tb, ticket)
+    res["masked_windowed_step_us"] = round(in_graph_us(lambda: ops.ddim_step_fused_windowed_masked(
+        eps, x_long, True, guidance, eng.coef, idx, xin, *frame, win, *long_in), args.reps), 2)
+    res["windowed_step_us"] = round(in_graph_us(lambda: ops.ddim_step_fused_windowed(
+        eps, x_long, True, guidance, eng.coef, idx, xin, *frame, win), args.reps), 2)
+    res["plain_masked_step_us"] = round(in_graph_us(lambda: ops.ddim_step_fused_masked(
+        eps, x_plain, True, guidance, eng.coef, idx, xin, *frame, *plain_in), args.reps), 2)
+    res["eps_bytes"] = eps.numel() * 4
+    res["extra_long_bytes"] = 2 * x_long.numel() * 4 + long_in[2].numel() * 4
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=60.0)
@@ -58,6 +143,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--skip-unwindowed", action="store_true")
+    ap.add_argument("--audio-to-audio", action="store_true", help="measure the long-form audio-to-audio call instead (DESIGN.md section 19)")
     args = ap.parse_args()
     from audioldm_with_lora_amd import ops
     from audioldm_with_lora_amd.pipeline import AudioLDMPipeline
@@ -72,6 +158,9 @@ def main():
     pipe.vae.cuda(); pipe.vocoder.cuda()
     plan, _ = pipe.window_plan(args.seconds, args.window_seconds, args.overlap_seconds)
     lat, pe, ne = synth_inputs(1, plan.rows, 16)
+    if args.audio_to_audio:
+        print(json.dumps(audio_to_audio_leg(args, pipe, plan, pe, ne, guidance)))
+        return
     call = dict(prompt_embeds=pe, negative_prompt_embeds=ne, audio_length_in_s=args.seconds, num_inference_steps=args.steps,
                 guidance_scale=guidance)
     windowed = dict(call, window_length_in_s=args.window_seconds, window_overlap_in_s=args.overlap_seconds)
