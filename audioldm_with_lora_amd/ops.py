@@ -609,7 +609,8 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
             and splits in (None, 1) and gn is None and (not vt_dual or vt is not None)
             and not (qstats and OH * OW >= QSTATS_MIN_HW)
             and (not pw.Rp or getattr(pw, "ranks_used", 99) <= 32)
-            and (pw.ln_s is None or (ln_parts is not None and ln_parts.shape[1] <= 16))
+            and (pw.ln_s is None or (ln_parts is not None and ln_parts.shape[1] <= 16 and (vt is not None or pw.geglu)))   # (aldm_pgemm folds a
+            #                     LayerNorm in its V^T and GEGLU forms only: a plain LayerNorm-folded linear stays on aldm_igemm)
             and not (pw.geglu and (res is not None or vt is not None or pw.Rp or rowstats))
             and not (vt is not None and (res is not None or rowstats or vt_col0 % 32 or (vt_col0 <= 0 and not vt_dual) or vt_col0 < 0))
             and (res is None or (res.is_contiguous() and res.numel() == B * OH * OW * out_ld))

@@ -16,6 +16,8 @@ There is no torch autograd here.  A small launch tape records, per forward op, t
 All LoRA parameters live in one flat fp32 buffer (the nn.Parameters are views into it); one `aldm_lora_pack`
 launch per step refreshes every packed bf16 operand.
 """
+import contextlib
+import gc
 import math
 import os
 import struct
@@ -30,6 +32,23 @@ from .lora import LoraLinear
 from .unet import UNet2DConditionModel, transformer_gn
 
 BK = 64
+
+
+@contextlib.contextmanager
+def capture(graph):
+    """torch.cuda.graph with Python's cyclic collector held off.  torch no longer collects garbage before a capture, so a collector pass
+    that falls INSIDE the ~1000 Python-launched kernels of a step could finalise a dead cycle left by earlier work that owns GPU objects
+    (another captured graph, its memory pool) -- releasing those in the middle of a capture aborts the process.  Collect first, then
+    capture with the collector off."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):   # RCCL's watchdog thread must not void the capture
+            yield
+    finally:
+        if was:
+            gc.enable()
 
 
 # ----------------------------------------------------------------------------------------------
@@ -800,7 +819,7 @@ class LoraTrainer:
         self._static = tuple(a.clone() for a in args)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):   # RCCL's watchdog thread must not void the capture
+        with capture(self.graph):
             run(*self._static)
         self._graph_tab = self.tnb.snapshot()                    # job table of the captured addresses (H2D copies cannot be captured)
         self.tnb.restore(self._graph_tab)
@@ -875,7 +894,7 @@ class LoraTrainer:
                     static = tuple(a.clone() for a in args)
                     torch.cuda.synchronize()
                     g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    with capture(g):
                         body(*static)
                     # every graph's aldm_tn_batched launch reads the trainer's ONE device job table: each graph keeps the table of ITS
                     # captured addresses and puts it back before a replay whenever another graph, a capture or an eager step overwrote it
