@@ -3,7 +3,9 @@
 // score tile is converted in registers and re-used directly as the B operand of O^T += V^T P^T (no LDS round
 // trip for P; the key order inside each 16-wide K-step is the accumulator's row permutation, which the
 // V^T fragment reads reproduce with two 8-byte LDS reads).  K / V^T tiles of 64 keys are shared by the
-// workgroup's waves through padded (bank-conflict-free) LDS images, register-prefetched one tile ahead.
+// workgroup's waves through padded (bank-conflict-free) LDS images, register-prefetched one tile ahead -- at N >= 192 by four LOADER
+// WAVES that do nothing else (template parameter NL, see attention_kernel; ALDM_ATTN_LOADERS=0 keeps the form in which every wave stages
+// its share of the tile between its own MFMAs): 20.4 -> 18.6 us at B 8, N 1000, 7.2 -> 6.8 at N 252, same bits.
 //
 // What bounds the loop (round 4; the round-3 note here -- "a SIMD does not run plain VALU work under its own MFMAs" -- was wrong:
 // tools/micro/mfma_valu_gap.hip, instruction stream pinned by inline asm, hides five v_fma_f32 or three v_exp_f32 under every
@@ -91,8 +93,17 @@ struct AttnCfg {
 // log-sum-exp the backward recomputes P from (p = exp2(s c - lse) then carries a per-row factor of up to 0.25 %).  The LSE form of
 // those head dims therefore ALSO adds the fp32 probabilities up on the VALU (as VL does) and takes the stored lse from that sum;
 // O is normalised exactly as before.  Without LSE nothing changes.
-template <int DP, int NW, int SP, bool PRESCALED, bool FP8 = false, bool LSE = false>
-__global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restrict__ q, int ldq,
+// NL > 0 (loader waves): the workgroup has NL more waves that do nothing but the K / V^T staging -- prefetch_* / stage_* below, with the
+// chunk ownership recomputed for 64 * NL threads, the V^T pad / ones rows and the kv_len tail clearing included -- while the NW compute
+// waves keep the Q fragments, scores() and softmax_pv() and lose the staging: their arithmetic is the NL = 0 kernel's instruction for
+// instruction, so the results are bit-identical.  The hand-over is the per-tile workgroup barrier that was there already and nothing else
+// (no flags, no polling, no atomics): a loader writes tile it + 1 into the LDS buffer the compute waves left at the previous barrier
+// while they work on tile it, and both roles meet at the barrier that ends iteration it.  BARRIER COUNT, every wave of both roles, on
+// every path: 1 (tile 0 staged) + niter (a key group that sits an iteration out -- mine() -- still arrives) + 1 if SP > 1 (the merge);
+// the all-padding workgroup of a kv_len launch leaves before the first of them, all roles together.  Two LDS buffers and two register
+// sets as before, so the loaders run at most one tile ahead in LDS and two in registers.  DESIGN 5.9.
+template <int DP, int NW, int SP, bool PRESCALED, bool FP8 = false, bool LSE = false, int NL = 0>
+__global__ __launch_bounds__(64 * (NW + NL)) void attention_kernel(const bf16* __restrict__ q, int ldq,
                                                             const bf16* __restrict__ k, int ldk,
                                                             const bf16* __restrict__ vt, int vt_ld, long long vt_bs,
                                                             int N, int D, float c /* scale*log2(e) */,
@@ -103,7 +114,8 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
   aldm_prefetch_next_kernargs<96>(threadIdx.x);
 #endif
   using Cfg = AttnCfg<DP, FP8>;
-  constexpr int T = 64 * NW;
+  constexpr int T = NL ? 64 * NL : 64 * NW;   // threads that share the staging of a tile: the loader waves, or (NL = 0) everybody
+  constexpr int TALL = 64 * (NW + NL);
   constexpr int DK = Cfg::DK, DT = Cfg::DT, KS = Cfg::KS, VS = Cfg::VSB;   // (VS shadows the bf16 stride: every use below is per-format)
 #ifndef ATTN_FP8_PBIAS
 #define ATTN_FP8_PBIAS 8.f
@@ -120,7 +132,11 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
   char* Ks = smem;                              // [2][SP][KV][KS]
   char* Vs = smem + 2 * SP * Cfg::KBYTES;       // [2][SP][DT*32][VS]
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  int wave = tid >> 6;
+  if constexpr (NL > 0) wave = __builtin_amdgcn_readfirstlane(wave);   // the role split below is a scalar branch
+  const bool loader = NL > 0 && wave >= NW;
+  const int stid = NL ? tid - 64 * NW : tid;    // index among the staging threads (loader waves only when NL > 0)
   const int r = lane & 31, hh = lane >> 5;
   // XCD-aware order: the dispatcher deals workgroups round-robin over the 8 XCDs, so with the natural order every XCD's L2
   // pulls every (batch, head)'s K / V^T (PMC: 70 MB fetched per launch for 16 MB of operands at N = 1000).  Give each XCD
@@ -149,7 +165,7 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
   const int Nk = kv_len ? max(1, min(kv_len[b], N)) : N;
   if (kv_len && qblk * QW * 32 >= Nk) {
     // every query of this workgroup is padding: its rows are never read as keys, so write zeros and leave
-    for (int i = tid; i < QW * 32 * (D / 4); i += T) {
+    for (int i = tid; i < QW * 32 * (D / 4); i += TALL) {
       const int row = qblk * QW * 32 + i / (D / 4), c4 = i % (D / 4);
       if (row < N) *reinterpret_cast<uint2*>(out + ((long long)b * N + row) * out_ld + head * D + c4 * 4) = make_uint2(0u, 0u);
     }
@@ -158,9 +174,9 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
 
   // rows D .. DT*32-1 of both V^T buffers are written once and stay for the whole kernel: zero (head-dim padding), except
   // row DP = ones (bf16 1.0 pairs): the P V MFMAs then also accumulate l = sum_k p in O^T row DP
-  {
+  if (NL == 0 || loader) {
     const int npad = DT * 32 - D;
-    for (int i = tid; i < 2 * SP * npad * (VS / 8); i += T) {
+    for (int i = stid; i < 2 * SP * npad * (VS / 8); i += T) {
       const int buf = i / (npad * (VS / 8)), rem = i - buf * npad * (VS / 8);
       const unsigned fill = (!Cfg::VL && D + rem / (VS / 8) == DP) ? (FP8 ? 0x38383838u : 0x3F803F80u) : 0u;   // 1.0 as bf16 / e4m3 pairs
       reinterpret_cast<uint2*>(Vs + buf * Cfg::VBYTES + D * VS)[rem] = make_uint2(fill, fill);
@@ -172,7 +188,7 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
 #pragma unroll
   for (int ks = 0; ks < DK; ++ks) {
     const int col = 16 * ks + 8 * hh;
-    const bf16x8 qv = (q0 + r < N && col < D) ? *reinterpret_cast<const bf16x8*>(qb + (long long)(q0 + r) * ldq + col) : zero8;
+    const bf16x8 qv = (!loader && q0 + r < N && col < D) ? *reinterpret_cast<const bf16x8*>(qb + (long long)(q0 + r) * ldq + col) : zero8;
     if constexpr (FP8) { const uint2 f = bf16x8_to_fp8(qv); qf[ks] = pack2(f.x, f.y); }
     else qf[ks] = qv;
   }
@@ -190,13 +206,13 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
   unsigned k_off[KPT], v_off[VPT];
 #pragma unroll
   for (int i = 0; i < KPT; ++i) {
-    const int cidx = tid + i * T;
+    const int cidx = stid + i * T;
     const int row = cidx / (DP / 8), ch = cidx - row * (DP / 8);
     k_off[i] = (cidx < KCH && ch * 8 < D) ? (unsigned)row * (unsigned)(ldk * 2) + ch * 16 : OOB;
   }
 #pragma unroll
   for (int i = 0; i < VPT; ++i) {
-    const int cidx = tid + i * T;
+    const int cidx = stid + i * T;
     const int row = cidx >> 3, ch = cidx & 7;
     v_off[i] = (cidx < VCH && row < D) ? (unsigned)row * (unsigned)(vt_ld * 2) + ch * 16 : OOB;
   }
@@ -232,7 +248,7 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
    for (int j = 0; j < SP; ++j) {
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
-      const int cidx = tid + i * T;
+      const int cidx = stid + i * T;
       const int row = cidx / (DP / 8), ch = cidx - row * (DP / 8);
       if (cidx < KCH) {
         if constexpr (FP8) *reinterpret_cast<uint2*>(Ks + (buf * SP + j) * Cfg::KBYTES + row * KS + ch * 8) = bf16x8_to_fp8(kreg[SET][j][i]);
@@ -248,7 +264,7 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
     const int kv0 = kvbase + j * KV;
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
-      const int cidx = tid + i * T;
+      const int cidx = stid + i * T;
       const int row = cidx >> 3, ch = cidx & 7;
       if (cidx < VCH) {
         bf16x8 v = vreg[SET][j][i];
@@ -452,50 +468,89 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
   // (wave-uniform) a key group past the last tile of an odd count sits that iteration out
   auto mine = [&](int it) { return SP == 1 || (it * SP + grp) * KV < Nk; };
 
-  prefetch(0, Set0{});
-  prefetch(SP * KV, Set1{});
-  stage(0, Set0{}, 0);
-  // Drain every global load issued so far (Q fragments, both prefetch sets) HERE, with the builtin the compiler's wait-count pass
-  // models: otherwise the first use of the Q fragments inside the loop gets an `s_waitcnt vmcnt(0)` that, from the second
-  // iteration on, waits for the K / V^T prefetch issued a few instructions earlier -- a full L2 round trip exposed per tile, in
-  // every wave at once (the ISA showed exactly that).  vmcnt = 0, expcnt / lgkmcnt untouched.
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __syncthreads();
-  // two register sets: the loads of tile-group it+2 are issued at the top of iteration it and written to LDS at the bottom of
-  // iteration it+1 -- two iterations of flight time (one iteration, ~0.5 us, does not cover an L2 miss)
-  auto iteration = [&](int it, auto curc) {     // curc: the register set that is free (its tile-group was staged last iteration)
-    constexpr int CUR = decltype(curc)::value;
-    // Order inside a tile: the S^T MFMAs first, then -- in their shadow, nothing depends on them yet -- the next tile's staging
-    // (registers -> LDS; its buffer was last read before the barrier that ended the previous iteration) and the prefetch of the tile
-    // after it (scalar descriptor arithmetic + buffer loads), then the softmax and the P V MFMAs.  Fenced, because left alone the
-    // scheduler put the staging behind the last P V MFMA, where nothing runs beside it.
-    f32x16 s[2];
-    const bool me = mine(it);
+  if constexpr (NL > 0) {
+    if (loader) {
+      // ================================ loader waves: the K / V^T stream and nothing else ================================
+      prefetch(0, Set0{});
+      prefetch(SP * KV, Set1{});
+      stage(0, Set0{}, 0);                        // (the compiler's own counted wait: set 0 has landed, set 1 stays in flight)
+      __syncthreads();                            // barrier 0: tile-group 0 is in LDS buffer 0
+      // iteration it: request tile-group it + 2 into the register set that was staged last iteration, then write tile-group it + 1
+      // (requested an iteration ago) into the buffer the compute waves left at the previous barrier, and meet them at this one
+      auto feed = [&](int it, auto curc) __attribute__((always_inline)) {
+        constexpr int CUR = decltype(curc)::value;
+        prefetch((it + 2) * SP * KV, curc);       // (unconditional, as in the NL = 0 form: past the last tile the bound is 0 -> zeros, no traffic)
+        if (it + 1 < niter) stage((it & 1) ^ 1, std::integral_constant<int, CUR ^ 1>{}, (it + 1) * SP * KV);
+        __syncthreads();
+      };
+      for (int it = 0; it < niter; it += 2) {
+        feed(it, Set0{});
+        if (it + 1 < niter) feed(it + 1, Set1{});
+      }
+      if constexpr (SP > 1) __syncthreads();      // the key groups' merge barrier: every wave of the workgroup arrives
+      return;
+    }
+    // ================================ compute waves ================================
+    __builtin_amdgcn_s_waitcnt(0x0F70);           // the Q fragments (see the NL = 0 form below)
+    __syncthreads();
+    auto tile = [&](int it) __attribute__((always_inline)) {   // (left to the inliner, the larger head dims kept this a call: O^T in scratch)
+      f32x16 s[2];
+      if (mine(it)) {
+        scores(it, s);
+        softmax_pv(it, s);
+      }
+      __syncthreads();
+    };
+    for (int it = 0; it < niter; it += 2) {       // (two tiles per trip like the NL = 0 loop: the buffer parity is a constant in each)
+      tile(it);
+      if (it + 1 < niter) tile(it + 1);
+    }
+  } else {
+    prefetch(0, Set0{});
+    prefetch(SP * KV, Set1{});
+    stage(0, Set0{}, 0);
+    // Drain every global load issued so far (Q fragments, both prefetch sets) HERE, with the builtin the compiler's wait-count pass
+    // models: otherwise the first use of the Q fragments inside the loop gets an `s_waitcnt vmcnt(0)` that, from the second
+    // iteration on, waits for the K / V^T prefetch issued a few instructions earlier -- a full L2 round trip exposed per tile, in
+    // every wave at once (the ISA showed exactly that).  vmcnt = 0, expcnt / lgkmcnt untouched.
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __syncthreads();
+    // two register sets: the loads of tile-group it+2 are issued at the top of iteration it and written to LDS at the bottom of
+    // iteration it+1 -- two iterations of flight time (one iteration, ~0.5 us, does not cover an L2 miss)
+    auto iteration = [&](int it, auto curc) {     // curc: the register set that is free (its tile-group was staged last iteration)
+      constexpr int CUR = decltype(curc)::value;
+      // Order inside a tile: the S^T MFMAs first, then -- in their shadow, nothing depends on them yet -- the next tile's staging
+      // (registers -> LDS; its buffer was last read before the barrier that ended the previous iteration) and the prefetch of the tile
+      // after it (scalar descriptor arithmetic + buffer loads), then the softmax and the P V MFMAs.  Fenced, because left alone the
+      // scheduler put the staging behind the last P V MFMA, where nothing runs beside it.
+      f32x16 s[2];
+      const bool me = mine(it);
 #if ATTN_FENCE
-    if (me) scores(it, s);
-    __builtin_amdgcn_sched_barrier(0);
-    if (it + 1 < niter) stage((it & 1) ^ 1, std::integral_constant<int, CUR ^ 1>{}, (it + 1) * SP * KV);
-    prefetch((it + 2) * SP * KV, curc);         // (unconditional: past the last tile the descriptor's bound is 0 -> zeros, no traffic;
-                                                //  a fixed number of loads per iteration lets the compiler count them in s_waitcnt)
-    __builtin_amdgcn_sched_barrier(0);
-    if (me) softmax_pv(it, s);
+      if (me) scores(it, s);
+      __builtin_amdgcn_sched_barrier(0);
+      if (it + 1 < niter) stage((it & 1) ^ 1, std::integral_constant<int, CUR ^ 1>{}, (it + 1) * SP * KV);
+      prefetch((it + 2) * SP * KV, curc);         // (unconditional: past the last tile the descriptor's bound is 0 -> zeros, no traffic;
+                                                  //  a fixed number of loads per iteration lets the compiler count them in s_waitcnt)
+      __builtin_amdgcn_sched_barrier(0);
+      if (me) softmax_pv(it, s);
 #else
 #ifndef ATTN_DIAG_NOLOAD
-    prefetch((it + 2) * SP * KV, curc);
+      prefetch((it + 2) * SP * KV, curc);
 #endif
-    if (me) {
-      scores(it, s);
-      softmax_pv(it, s);
-    }
+      if (me) {
+        scores(it, s);
+        softmax_pv(it, s);
+      }
 #ifndef ATTN_DIAG_NOLOAD
-    if (it + 1 < niter) stage((it & 1) ^ 1, std::integral_constant<int, CUR ^ 1>{}, (it + 1) * SP * KV);
+      if (it + 1 < niter) stage((it & 1) ^ 1, std::integral_constant<int, CUR ^ 1>{}, (it + 1) * SP * KV);
 #endif
 #endif
-    __syncthreads();
-  };
-  for (int it = 0; it < niter; it += 2) {
-    iteration(it, Set0{});
-    if (it + 1 < niter) iteration(it + 1, Set1{});
+      __syncthreads();
+    };
+    for (int it = 0; it < niter; it += 2) {
+      iteration(it, Set0{});
+      if (it + 1 < niter) iteration(it + 1, Set1{});
+    }
   }
   if constexpr ((Cfg::VL && !ML) || LSUM) l_run = l_pk[0] + l_pk[1];
 
@@ -556,20 +611,35 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const bf16* __restri
   }
 }
 
-template <int DP, int NW, int SP, bool PS, bool FP8 = false, bool LSE = false>
+template <int DP, int NW, int SP, bool PS, bool FP8 = false, bool LSE = false, int NL = 0>
 int launch_attn(const void* q, int ldq, const void* k, int ldk, const void* vt, int vt_ld, long long vt_bs, int B, int N,
                 int H, int D, float scale, void* out, int out_ld, float* lse, const int* kv_len, hipStream_t st) {
   using Cfg = AttnCfg<DP, FP8>;
-  auto kern = attention_kernel<DP, NW, SP, PS, FP8, LSE>;
+  auto kern = attention_kernel<DP, NW, SP, PS, FP8, LSE, NL>;
   constexpr int MERGE = SP == 1 ? 0 : (SP - 1) * (NW / SP) * (Cfg::DT * 16 + 2) * 256;   // the key groups' (m, O^T, l) exchange re-uses the staging area
   constexpr int LDS = 2 * SP * Cfg::TILE > MERGE ? 2 * SP * Cfg::TILE : MERGE;             // (one-byte images can be smaller than it)
   static unsigned long long attr_done = 0;   // per-device bit mask (aldm_set_max_lds)
   if (LDS > 48 * 1024)
     if (int rc = aldm_set_max_lds(reinterpret_cast<const void*>(kern), LDS, &attr_done, "attention")) return rc;
   dim3 grid(cdiv(N, 32 * (NW / SP)), H, B);
-  hipLaunchKernelGGL(kern, grid, dim3(64 * NW), LDS, st, (const bf16*)q, ldq, (const bf16*)k, ldk, (const bf16*)vt,
+  hipLaunchKernelGGL(kern, grid, dim3(64 * (NW + NL)), LDS, st, (const bf16*)q, ldq, (const bf16*)k, ldk, (const bf16*)vt,
                      vt_ld, vt_bs, N, D, scale * 1.44269504088896340736f, (bf16*)out, out_ld, lse, kv_len);
   return aldm_launch_status("attention");
+}
+
+// Loader waves per workgroup (attention_kernel, NL) for a launch of N keys: the ONE place that picks the form.  ALDM_ATTN_LOADERS=0
+// (read at every launch, so that one process can run both forms) keeps the NL = 0 kernel everywhere; 4 puts the loaders on every
+// multi-wave form (N >= 64; a tuning aid, tools/bench_attn.py, and how the tests reach the 4-wave one-group form); anything else is the
+// product rule: four loaders on the N >= 192 forms (the UNet's N = 1000 / 252 and the trainer's 1024 / 256 sites), none below.
+// Measured at B 8 x 8 heads, replayed graph: N 1000 d 32 20.40 -> 18.62 us with four loaders (19.37 with two), N 252 d 48
+// 7.24 -> 6.75 (7.45 with two: 3 chunks a thread, 136 VGPRs), N 64 d 80 5.20 -> 5.23 -- hence four, and nothing below 192.
+constexpr int ATTN_NL = 4;
+inline int attn_loaders(int N) {
+  const char* e = getenv("ALDM_ATTN_LOADERS");
+  const int v = e ? atoi(e) : -1;
+  if (v == 0) return 0;
+  if (v == ATTN_NL) return N >= 64 ? ATTN_NL : 0;
+  return N >= 192 ? ATTN_NL : 0;
 }
 
 template <int DP, bool PS, bool FP8 = false>
@@ -582,13 +652,20 @@ int launch_attn_d(const void* q, int ldq, const void* k, int ldk, const void* vt
   // N = 1000 with 4 heads 16.6 -> 14.6 us; at N = 1000 x 64 (batch, head) pairs the kernel is VALU-throughput-bound (softmax)
   // and the split only adds the merge: 22.9 -> 23.4 us, so the full-size case keeps one wave per query block
 #define ALDM_ATTN_ARGS q, ldq, k, ldk, vt, vt_ld, vt_bs, B, N, H, D, scale, out, out_ld, lse, kv_len, st
+  const int nl = attn_loaders(N);
+  // (NWV, SPV) with the loader count picked above; LSEV: the lse form (never fp8, never prescaled)
+#define ALDM_ATTN_NL(NWV, SPV, F8V, LSEV)                                                   \
+  do {                                                                                      \
+    if (nl) return launch_attn<DP, NWV, SPV, PS, F8V, LSEV, ATTN_NL>(ALDM_ATTN_ARGS);       \
+    return launch_attn<DP, NWV, SPV, PS, F8V, LSEV>(ALDM_ATTN_ARGS);                        \
+  } while (0)
   if constexpr (FP8) {                        // (the tuning overrides below are not instantiated for the fp8 form)
     if (N >= 768) {
-      if ((long long)cdiv(N, 256) * H * B >= 256) return launch_attn<DP, 8, 1, PS, true>(ALDM_ATTN_ARGS);
-      return launch_attn<DP, 8, 2, PS, true>(ALDM_ATTN_ARGS);
+      if ((long long)cdiv(N, 256) * H * B >= 256) ALDM_ATTN_NL(8, 1, true, false);
+      ALDM_ATTN_NL(8, 2, true, false);
     }
-    if (N >= 192) return launch_attn<DP, 4, 2, PS, true>(ALDM_ATTN_ARGS);
-    if (N >= 64) return launch_attn<DP, 4, 1, PS, true>(ALDM_ATTN_ARGS);
+    if (N >= 192) ALDM_ATTN_NL(4, 2, true, false);
+    if (N >= 64) ALDM_ATTN_NL(4, 1, true, false);
     return launch_attn<DP, 1, 1, PS, true>(ALDM_ATTN_ARGS);
   }
   // the lse form of the head dims whose l is the row of ones sums the fp32 probabilities for the stored lse (attention_kernel, LSE)
@@ -598,6 +675,13 @@ int launch_attn_d(const void* q, int ldq, const void* k, int ldk, const void* vt
       if (lse) return launch_attn<DP, NWV, SPV, PS, false, true>(ALDM_ATTN_ARGS);           \
     }                                                                                       \
     return launch_attn<DP, NWV, SPV, PS>(ALDM_ATTN_ARGS);                                   \
+  } while (0)
+#define ALDM_ATTN_GOL(NWV, SPV)   /* the same with loader waves where attn_loaders() asks for them */ \
+  do {                                                                                      \
+    if constexpr (!PS && DP % 32 != 0) {                                                    \
+      if (lse) ALDM_ATTN_NL(NWV, SPV, false, true);                                         \
+    }                                                                                       \
+    ALDM_ATTN_NL(NWV, SPV, false, false);                                                   \
   } while (0)
   static const int force = getenv("ALDM_ATTN_CFG") ? atoi(getenv("ALDM_ATTN_CFG")) : 0;   // tuning aid: 10 * waves + key split
   if (force == 81) ALDM_ATTN_GO(8, 1);
@@ -609,13 +693,15 @@ int launch_attn_d(const void* q, int ldq, const void* k, int ldk, const void* vt
     if (force == 162) return launch_attn<DP, 16, 2, PS>(ALDM_ATTN_ARGS);   // 16 waves = 4 per SIMD, keys split over two wave groups
   }
   if (N >= 768) {
-    if ((long long)cdiv(N, 256) * H * B >= 256) ALDM_ATTN_GO(8, 1);
-    ALDM_ATTN_GO(8, 2);
+    if ((long long)cdiv(N, 256) * H * B >= 256) ALDM_ATTN_GOL(8, 1);
+    ALDM_ATTN_GOL(8, 2);
   }
-  if (N >= 192) ALDM_ATTN_GO(4, 2);
-  if (N >= 64) ALDM_ATTN_GO(4, 1);   // N = 64 x 64 (batch, head) pairs: 4 waves 5.2 us vs 2 waves 5.7 us
+  if (N >= 192) ALDM_ATTN_GOL(4, 2);
+  if (N >= 64) ALDM_ATTN_GOL(4, 1);   // N = 64 x 64 (batch, head) pairs: 4 waves 5.2 us vs 2 waves 5.7 us
   ALDM_ATTN_GO(1, 1);
 #undef ALDM_ATTN_GO
+#undef ALDM_ATTN_GOL
+#undef ALDM_ATTN_NL
 #undef ALDM_ATTN_ARGS
 }
 

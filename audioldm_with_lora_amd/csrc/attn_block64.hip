@@ -7,7 +7,9 @@
 // two-stage LDS-DMA ring, keep Q / K / V^T of the head in LDS (37 KB) and run the 64 x 64 attention on them -- Q | K | V never
 // touch HBM and two launches (19 us) become one.  SURVEY.md 2.3 K1 ("fused QKV-GEMM + LoRA epilogue -> flash-style attention").
 //
-//   * 4 wave64; wave w owns tokens 16 w .. 16 w + 15 through both phases.  v_mfma_f32_16x16x32_bf16, issued "swapped" (weight rows
+//   * 4 compute wave64 (+ 4 loader waves that own the weight stream below, template parameter LW; ALDM_B64_LOADERS=0 keeps the
+//     256-thread form in which the multiplying waves also stage the weights: 15.1 -> 12.9 us per launch at B 8, same bits);
+//     wave w owns tokens 16 w .. 16 w + 15 through both phases.  v_mfma_f32_16x16x32_bf16, issued "swapped" (weight rows
 //     = A operand) so a lane owns ONE token column: LayerNorm mean / rstd and the softmax state are lane-local.
 //   * the weight stream goes HBM/L2 -> registers -> LDS: plain 16-byte loads, six tiles (20 KB + the tile's 1 KB of LoRA-B rows)
 //     in flight per workgroup, ds_write_b128 into a double-buffered swizzled image.  (With one workgroup per CU the LDS-DMA path
@@ -22,6 +24,7 @@
 //     B operand once K is read with the matching k-slot order; softmax over the 64 keys in registers (Q is pre-scaled by
 //     d^-0.5 log2 e at pack time), O^T = V^T P^T with the S^T accumulators re-used as the B operand.
 #include "igemm_core.h"   // make_rsrc / lds_ptr_t / wait_vmcnt
+#include <cstdlib>
 
 namespace {
 
@@ -52,14 +55,21 @@ struct Blk64Args {
 #endif
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+constexpr bool B64_LOADERS_DEFAULT = true;
 
 // F8 (BASELINE config 5): Q / K / V / P enter the two attention products as OCP e4m3 (v_mfma_f32_16x16x32_fp8_fp8, fp32 accumulation); the
 // fragments are converted where they are used, from the same bf16-rounded values the two-launch fp8 path quantises, P carries 2^8 into
 // its conversion (e4m3 tops out at 448) and the normaliser sums the converted values, so the factor cancels exactly.
 // GATED (multi-adapter routing): T'' of sample b is multiplied, in fp32 and before its rounding to bf16, by row b of the gate table --
 // column j of T belongs to one adapter, so the row selects / weights / blends the adapters of this sample.
-template <int C, int D, int RT /* LoRA rank tiles of 16: 0, 1 or 2 */, bool F8 = false, bool GATED = false>
-__global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
+// LW (loader waves): 512 threads -- waves 0 .. 3 are the compute waves above minus gload / lstore (X fragments, lread, the MFMAs, the
+// per-tile epilogue and the whole attention phase, unchanged in order and arithmetic: bit-identical results), waves 4 .. 7 own the weight
+// stream (gload / lstore: weight tiles, LoRA-A tiles, LoRA-B rows; the same chunk ownership, swizzle, P-deep flight and NS stages, with
+// loader l in the place of wave l) and nothing else.  One raw s_barrier per tile executed by all eight waves is the whole hand-over:
+// every wave, either role, runs 1 + NTILES of them on its only path; the loaders leave after the last tile (the attention phase has no
+// workgroup barrier).  Register-staged like the LW = 0 form.  DESIGN 5.9.
+template <int C, int D, int RT /* LoRA rank tiles of 16: 0, 1 or 2 */, bool F8 = false, bool GATED = false, bool LW = false>
+__global__ __launch_bounds__(LW ? 512 : 256) void attn_block64_kernel(const Blk64Args p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   aldm_touch_kernargs<sizeof(Blk64Args)>();
 #ifndef ALDM_NO_KA_PREFETCH
@@ -89,8 +99,10 @@ __global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
   const int head = blockIdx.x, b = blockIdx.y;
   const int N = p.N;
   const long long row0 = (long long)b * N;
+  const bool loader = LW && wave >= 4;
+  const int lw = LW ? wave - 4 : wave;                       // this wave's share of a tile's chunks (loader waves only when LW)
   const int tok = 16 * wave + n;
-  const bool live = tok < N;
+  const bool live = !loader && tok < N;
   B64_STAMP(0)
 
   const __amdgpu_buffer_rsrc_t rs_x = aldm_igemm_detail::make_rsrc(p.x + row0 * C, (unsigned)(N * C * 2));
@@ -116,21 +128,21 @@ __global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
   }
   f32x4 sa[RT ? RT : 1], ca[RT ? RT : 1];
 #pragma unroll
-  for (int t = 0; t < RT; ++t) {
+  for (int t = 0; t < RT && !loader; ++t) {
     sa[t] = *reinterpret_cast<const f32x4*>(p.ln_sa + 16 * t + 4 * g);
     ca[t] = *reinterpret_cast<const f32x4*>(p.ln_ca + 16 * t + 4 * g);
   }
   f32x4 gt[(GATED && RT) ? RT : 1];
   if constexpr (GATED) {
 #pragma unroll
-    for (int t = 0; t < RT; ++t) gt[t] = *reinterpret_cast<const f32x4*>(p.gate + (long long)b * p.Rp + 16 * t + 4 * g);
+    for (int t = 0; t < RT && !loader; ++t) gt[t] = *reinterpret_cast<const f32x4*>(p.gate + (long long)b * p.Rp + 16 * t + 4 * g);
   }
   __builtin_amdgcn_sched_barrier(0);
   // ---- X fragments of this wave's 16 tokens straight into registers (B operand): lane (n, g) holds X[16 w + n][32 ks + 8 g .. + 7].
   //      They stay there across all weight tiles, so X never needs LDS; rows >= N read as zeros through the descriptor. ----
   bf16x8 xf[KSTEPS];
 #pragma unroll
-  for (int ks = 0; ks < KSTEPS; ++ks)
+  for (int ks = 0; ks < KSTEPS && !loader; ++ks)
     xf[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_x, tok * (C * 2) + (32 * ks + 8 * g) * 2, 0, 0));
   __builtin_amdgcn_sched_barrier(0);
 
@@ -145,7 +157,7 @@ __global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
   int w_src[5], w_dst[5];                                      // per-lane chunk of a tile: source byte offset (row-relative), swizzled LDS offset
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
-    const int c = (wave + 4 * i) * 64 + lane, row = c / CPR, ph = c - row * CPR;
+    const int c = (lw + 4 * i) * 64 + lane, row = c / CPR, ph = c - row * CPR;
     w_src[i] = row * (p.Kpad * 2) + ph * 16;
     w_dst[i] = row * (C * 2) + ((ph ^ (row & 15)) * 16);
   }
@@ -158,22 +170,46 @@ __global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
     const int base = r0 * (p.Kpad * 2);
 #pragma unroll
     for (int i = 0; i < 5; ++i) wreg[slot][i] = __builtin_amdgcn_raw_buffer_load_b128(la ? rs_a : rs_w, base + w_src[i], 0, 0);
-    if (RT > 0 && !la && wave == (t & 3)) breg[slot] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, r0 * (p.Rp * 2) + b_src, 0, 0);
+    if (RT > 0 && !la && lw == (t & 3)) breg[slot] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, r0 * (p.Rp * 2) + b_src, 0, 0);
   };
   auto lstore = [&](int t) {
     const int slot = t % P;
     char* const dst = Wr + (t % NS) * WSTAGE;
 #pragma unroll
     for (int i = 0; i < 5; ++i) *reinterpret_cast<u32x4*>(dst + w_dst[i]) = wreg[slot][i];
-    if (RT > 0 && t >= RT && wave == (t & 3)) *reinterpret_cast<u32x4*>(dst + WTILE + lane * 16) = breg[slot];
+    if (RT > 0 && t >= RT && lw == (t & 3)) *reinterpret_cast<u32x4*>(dst + WTILE + lane * 16) = breg[slot];
   };
   const int w_rd = n * (C * 2);                               // this lane's row of a tile image; chunk (4 ks + g) ^ n
   bf16x8 wf[2][KSTEPS];
   auto lread = [&](int t, int ks) {
     wf[t & 1][ks] = *reinterpret_cast<const bf16x8*>(Wr + (t % NS) * WSTAGE + w_rd + (((4 * ks + g) ^ n) * 16));
   };
+  if constexpr (LW) {
+    if (loader) {
+      // ================================ loader waves: the weight stream and nothing else ================================
 #pragma unroll
-  for (int t = 0; t < P; ++t) gload(t);
+      for (int t = 0; t < P; ++t) gload(t);
+      lstore(0);
+      if (P < NTILES) gload(P);
+      lstore(1);
+      if (P + 1 < NTILES) gload(P + 1);
+      __builtin_amdgcn_s_waitcnt(0xC07F);                     // barrier 0: tiles 0 and 1 are in LDS (lgkmcnt(0); the loads stay in flight)
+      __builtin_amdgcn_s_barrier();
+#pragma unroll
+      for (int t = 0; t < NTILES; ++t) {                     // barrier 1 + t ends tile t: stage (t + 2) % NS was last read in iteration t - 1
+        if (t + 2 < NTILES) {
+          lstore(t + 2);
+          if (t + 2 + P < NTILES) gload(t + 2 + P);
+        }
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_s_barrier();
+      }
+      return;
+    }
+  } else {
+#pragma unroll
+    for (int t = 0; t < P; ++t) gload(t);
+  }
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- LayerNorm statistics of this lane's token (16 w + n) from the producer's partials; s_n | c_n of the head's columns ----
@@ -184,10 +220,12 @@ __global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
   }
   if (tid < 3 * D) { sn_l[tid] = sn_v; cn_l[tid] = cn_v; }
   B64_STAMP(1)
-  lstore(0);
-  if (P < NTILES) gload(P);
-  lstore(1);
-  if (P + 1 < NTILES) gload(P + 1);
+  if constexpr (!LW) {
+    lstore(0);
+    if (P < NTILES) gload(P);
+    lstore(1);
+    if (P + 1 < NTILES) gload(P + 1);
+  }
   // raw barriers throughout: __syncthreads()' fence would drain the weight loads in flight (vmcnt(0)); the LDS writes are covered
   // by the explicit lgkmcnt(0)
   __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -207,9 +245,11 @@ __global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
   for (int t = 0; t < NTILES; ++t) {
     // stage t % NS holds tile t and its fragments are in wf[t & 1] (read during iteration t - 1); stage (t + 1) % NS holds tile t + 1
     // (all waves' parts, barrier passed); stage (t + 2) % NS was last read in iteration t - 2
-    if (t + 2 < NTILES) {
-      lstore(t + 2);
-      if (t + 2 + P < NTILES) gload(t + 2 + P);
+    if constexpr (!LW) {
+      if (t + 2 < NTILES) {
+        lstore(t + 2);
+        if (t + 2 + P < NTILES) gload(t + 2 + P);
+      }
     }
     // with one wave per SIMD only this wave's own instruction stream can fill the 12 idle issue cycles behind each MFMA: the
     // fragment reads of tile t + 1 are interleaved with the MFMAs of tile t
@@ -340,15 +380,24 @@ __global__ __launch_bounds__(256) void attn_block64_kernel(const Blk64Args p) {
 #endif
 }
 
-template <int C, int D, int RT, bool F8 = false, bool GATED = false>
-int launch_blk64(const Blk64Args& a, int B, hipStream_t st) {
+template <int C, int D, int RT, bool F8, bool GATED, bool LW>
+int launch_blk64_form(const Blk64Args& a, int B, hipStream_t st) {
   constexpr int LDS = 3 * (16 * C * 2 + 1024) + 64 * (D * 2 + 16) + D * (64 * 2 + 8) + 2 * 3 * D * 4;
   static_assert(LDS <= 160 * 1024, "LDS budget");
-  auto kern = attn_block64_kernel<C, D, RT, F8, GATED>;
+  auto kern = attn_block64_kernel<C, D, RT, F8, GATED, LW>;
   static unsigned long long attr_done = 0;
   if (int rc = aldm_set_max_lds(reinterpret_cast<const void*>(kern), LDS, &attr_done, "attn_block64")) return rc;
-  hipLaunchKernelGGL(kern, dim3(a.H, B), dim3(256), LDS, st, a);
+  hipLaunchKernelGGL(kern, dim3(a.H, B), dim3(LW ? 512 : 256), LDS, st, a);
   return aldm_launch_status("attn_block64");
+}
+
+// The ONE place that picks the form: four loader waves beside the four compute waves unless ALDM_B64_LOADERS=0 (read at every launch;
+// an A/B switch), which keeps the 256-thread kernel whose multiplying waves also stage the weights.
+template <int C, int D, int RT, bool F8 = false, bool GATED = false>
+int launch_blk64(const Blk64Args& a, int B, hipStream_t st) {
+  const char* e = getenv("ALDM_B64_LOADERS");
+  if (e && atoi(e) == 0) return launch_blk64_form<C, D, RT, F8, GATED, false>(a, B, st);
+  return launch_blk64_form<C, D, RT, F8, GATED, B64_LOADERS_DEFAULT>(a, B, st);
 }
 
 unsigned long long* g_b64_diag = nullptr;
