@@ -72,21 +72,35 @@ def pack_conv_transpose1d(w, b, stride, padding):
     return SimpleNamespace(phases=phases, stride=stride, padding=padding, k=k, ntap=ntap)
 
 
-def run_conv_transpose1d(P, x, out_len, post_act=ACT_NONE, post_slope=0.0, out2=False):
-    """x [B, 1, T, Cin] -> y [B, 1, out_len, Cout] (+ optional leaky-relu'd copy)."""
-    B, _, T, _ = x.shape
-    co = P.phases[0].N
-    y = torch.empty(B, 1, out_len, co, dtype=torch.bfloat16, device=x.device)
-    y2 = torch.empty_like(y) if out2 else None
-    u, p = P.stride, P.padding
-    for phi, pw in enumerate(P.phases):
-        # outputs t = u*q + phi - p, q >= q0 ; input index = q - i
+def transpose_phase_plan(k, u, p, out_len):
+    """The phase launches of ConvTranspose1d(k, stride u, padding p) over out_len outputs: [(phi, q0, t0, nq), ...].
+    Phase phi writes the outputs t = u q + phi - p for q = q0 .. q0 + nq - 1, the first at t0; output q reads input q - i at the
+    phase's tap i.  A phase with no output in [0, out_len) is left out.  Which taps a phase has (j = phi + u i < k) is
+    pack_conv_transpose1d's business: the plan itself does not depend on k, which only names the layer."""
+    plan = []
+    for phi in range(u):
         q0 = max(0, -((phi - p) // u))           # smallest q with t >= 0  (ceil((p - phi)/u))
         t0 = u * q0 + phi - p
         if t0 >= out_len:
             continue
         nq = (out_len - 1 - t0) // u + 1
-        ops.conv(x, pw, pad=(0, -q0), dil=(1, -1), out_hw=(1, nq), out=y, out_ld=co, out_batch_stride=out_len * co,
+        plan.append((phi, q0, t0, nq))
+    return plan
+
+
+def run_conv_transpose1d(P, x, out_len, post_act=ACT_NONE, post_slope=0.0, out2=False, out=None, out2_buf=None):
+    """x [B, 1, T, Cin] -> y [B, 1, out_len, Cout] (+ optional leaky-relu'd copy).  out / out2_buf: caller-supplied buffers of that
+    shape (bf16, contiguous) to write into instead of fresh ones."""
+    B, _, T, _ = x.shape
+    co = P.phases[0].N
+    y = torch.empty(B, 1, out_len, co, dtype=torch.bfloat16, device=x.device) if out is None else out
+    y2 = (torch.empty_like(y) if out2_buf is None else out2_buf) if out2 else None
+    for t in (y, y2):
+        assert t is None or (t.shape == (B, 1, out_len, co) and t.dtype == torch.bfloat16 and t.is_contiguous() and t.device == x.device)
+    u = P.stride
+    for phi, q0, t0, nq in transpose_phase_plan(P.k, u, P.padding, out_len):
+        # outputs t = u*q + phi - p, q >= q0 ; input index = q - i
+        ops.conv(x, P.phases[phi], pad=(0, -q0), dil=(1, -1), out_hw=(1, nq), out=y, out_ld=co, out_batch_stride=out_len * co,
                  out_pix_stride=u, out_pix_offset=t0, post_act=post_act, post_slope=post_slope, out2=y2)
     return (y, y2) if out2 else y
 
@@ -149,8 +163,9 @@ class SpeechT5HifiGan(nn.Module):
         self._plan = P
         return P
 
-    def forward_nhwc(self, mel):
-        """mel [B, 1, T, 64] channels-last bf16 -> waveform [B, 160 T + 32] fp32."""
+    def forward_nhwc(self, mel, taps=None):
+        """mel [B, 1, T, 64] channels-last bf16 -> waveform [B, 160 T + 32] fp32.  taps: a list that receives, per stage, (stage, h, a):
+        the up-sampler's output and the post-MRF activation that feeds the next stage (the tensors themselves)."""
         cfg, P = self.config, self.plan()
         slope = cfg.leaky_relu_slope
         if cfg.normalize_before:
@@ -181,6 +196,8 @@ class SpeechT5HifiGan(nn.Module):
                             acc = ops.hifigan_respair(r, c1, c2, d, slope, alpha=1.0 / nk, res2=acc,
                                                       post_act=(ACT_LRELU if fin else ACT_NONE), post_slope=(0.01 if last else slope))
                 a = acc
+                if taps is not None:
+                    taps.append((i, h, a))
                 continue
             h, ha = run_conv_transpose1d(up, a, T, post_act=ACT_LRELU, post_slope=slope, out2=True)
             acc = None
@@ -202,6 +219,8 @@ class SpeechT5HifiGan(nn.Module):
                         acc = ops.conv(t, c2, pad=(0, (rb.k - 1) // 2), res=r, alpha=1.0 / nk, res2=acc,
                                        post_act=(ACT_LRELU if fin else ACT_NONE), post_slope=(0.01 if last else slope))
             a = acc
+            if taps is not None:
+                taps.append((i, h, a))
         if a.shape[3] % 8 == 0 and a.shape[3] <= 128 and P.post.KW % 2 == 1 and P.post.KW <= 15:
             return ops.conv1d_to1(a, P.post, act=ACT_TANH)       # one output channel: an HBM-bound stencil, not a GEMM with 1 live column
         w = ops.conv(a, P.post, pad=(0, (P.post.KW - 1) // 2), out_act=ACT_TANH, out_f32=True)

@@ -67,12 +67,15 @@ def accepts(got, exact, rounded):
     return e_l2 <= L2_MARGIN * f_l2 and e_max <= MAX_MARGIN * f_max
 
 
-def check(got, exact, rounded, what):
-    import conftest
+def check(got, exact, rounded, what, record=None):
+    """record(value, what): where the two measured ratios go (default: conftest.record, one line each in the test log)."""
+    if record is None:
+        import conftest
+        record = conftest.record
     assert bool(torch.isfinite(got.detach().to("cpu").to(F64)).all()), f"{what}: non-finite values"
     e_l2, f_l2, e_max, f_max = floor_ratios(got, exact, rounded)
-    conftest.record(_ratio(e_l2, f_l2), what + " l2/floor")
-    conftest.record(_ratio(e_max, f_max), what + " max/floor")
+    record(_ratio(e_l2, f_l2), what + " l2/floor")
+    record(_ratio(e_max, f_max), what + " max/floor")
     assert e_l2 <= L2_MARGIN * f_l2, f"{what}: rel L2 {e_l2:.4g} > {L2_MARGIN} x floor {f_l2:.4g}"
     assert e_max <= MAX_MARGIN * f_max, f"{what}: max err {e_max:.4g} > {MAX_MARGIN} x floor {f_max:.4g}"
 

@@ -143,32 +143,34 @@ def test_packing_layouts():
 
 
 def test_vocoder_transposed_conv_phase_decomposition_matches_torch():
-    """Host-side phase math (which taps / which output rows) checked with plain torch on the CPU."""
+    """Host-side phase math (which taps / which output rows) checked with plain torch on the CPU: the plan is the product's own
+    (vocoder.transpose_phase_plan, what run_conv_transpose1d launches), the taps of a phase are pack_conv_transpose1d's."""
     from audioldm_with_lora_amd import vocoder as V
     g = torch.Generator().manual_seed(0)
-    for (k, u) in ((16, 5), (16, 4), (8, 2), (4, 2)):
-        p = (k - u) // 2
-        w = torch.randn(8, 8, k, generator=g)
-        x = torch.randn(1, 8, 9, generator=g)
-        want = torch.nn.functional.conv_transpose1d(x, w, None, stride=u, padding=p)
-        out_len = want.shape[2]
-        got = torch.zeros_like(want)
-        ntap = (k + u - 1) // u
-        for phi in range(u):
-            q0 = max(0, -((phi - p) // u))
-            t0 = u * q0 + phi - p
-            if t0 >= out_len:
-                continue
-            nq = (out_len - 1 - t0) // u + 1
-            for qi in range(nq):
-                q = qi + q0
-                acc = torch.zeros(8)
-                for i, j in enumerate(range(phi, k, u)):
-                    s = q - i
-                    if 0 <= s < x.shape[2]:
-                        acc += w[:, :, j].t() @ x[0, :, s]
-                got[0, :, t0 + u * qi] = acc
-        torch.testing.assert_close(got, want, rtol=1e-4, atol=1e-4)
+    # (16, 5, 5) and (7, 3, 2): k % u != 0 (phases with fewer taps); (3, 4, 0): phase 3 has no tap at all and, at T = 1, no output
+    for (k, u, p) in ((16, 5, 5), (16, 4, 6), (8, 2, 3), (4, 2, 1), (7, 3, 2), (3, 4, 0)):
+        for T in (1, 2, 3, 9):
+            w = torch.randn(8, 8, k, generator=g)
+            b = torch.randn(8, generator=g)
+            x = torch.randn(1, 8, T, generator=g)
+            want = torch.nn.functional.conv_transpose1d(x, w, b, stride=u, padding=p)
+            out_len = want.shape[2]
+            got = torch.full_like(want, float("nan"))
+            plan = V.transpose_phase_plan(k, u, p, out_len)
+            assert len(plan) == len({phi for phi, *_ in plan}) <= u
+            if (k, u, p, T) == (3, 4, 0, 1):
+                assert [phi for phi, *_ in plan] == [0, 1, 2]
+            for phi, q0, t0, nq in plan:
+                for qi in range(nq):
+                    q = qi + q0
+                    acc = b.clone()
+                    for i, j in enumerate(range(phi, k, u)):
+                        s = q - i
+                        if 0 <= s < x.shape[2]:
+                            acc += w[:, :, j].t() @ x[0, :, s]
+                    assert torch.isnan(got[0, :, t0 + u * qi]).all()       # every output is written once
+                    got[0, :, t0 + u * qi] = acc
+            torch.testing.assert_close(got, want, rtol=1e-4, atol=1e-4)
 
 
 def test_tuned_table_is_well_formed():
