@@ -3,7 +3,8 @@
 Drop-in surface for the reference's entry points:
 AudioLDMPipeline / UNet2DConditionModel / AutoencoderKL / SpeechT5HifiGan / DDIMScheduler / DPMSolverMultistepScheduler /
 UniPCMultistepScheduler / EulerAncestralDiscreteScheduler (all four in scheduler.py; the last two exported here on first use as well) and the peft-shaped LoraConfig / get_peft_model helpers; AudioLDMAudioToAudioPipeline (audio2audio.py,
-exported here on first use) starts from a recording.  No CPU fallback: ops raise if libaldm_hip.so is missing.
+exported here on first use) starts from a recording; Resampler / resample (resample.py, likewise) bring audio of any rate to another
+on the device.  No CPU fallback: ops raise if libaldm_hip.so is missing.
 """
 __version__ = "0.1.0"
 
@@ -18,4 +19,10 @@ def __getattr__(name):
     if name == "EulerAncestralDiscreteScheduler":
         from .scheduler import EulerAncestralDiscreteScheduler
         return EulerAncestralDiscreteScheduler
+    if name == "Resampler":
+        from .resample import Resampler
+        return Resampler
+    if name == "resample":                              # the function; resample.py makes its module callable as it (and keeps the name)
+        import importlib
+        return importlib.import_module(".resample", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -24,6 +24,8 @@ from . import ops
 from .engine import DenoiseEngine, WindowedAudioToAudioEngine
 from .mel import LogMelFrontEnd
 from .pipeline import AudioLDMPipeline, AudioPipelineOutput, _frozen_config
+from .resample import Resampler, ratio
+from .resample import resample as resample_audio
 
 HOP_SECONDS = 0.01        # one mel frame per 160 samples at 16 kHz
 
@@ -141,8 +143,11 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
                  num_inference_steps=50, guidance_scale=2.5, negative_prompt=None, num_waveforms_per_prompt=1, generator=None,
                  latents=None, prompt_embeds=None, negative_prompt_embeds=None, return_dict=True, output_type="np", adapter_names=None,
                  adapter_weights=None, window_length_in_s=None, window_overlap_in_s=None, loop=False, window_prompts=None,
-                 window_prompt_embeds=None):
-        """window_length_in_s / window_overlap_in_s / loop / window_prompts / window_prompt_embeds: as in AudioLDMPipeline.__call__
+                 window_prompt_embeds=None, resample=False, output_sampling_rate=None):
+        """resample=True: a recording at another rate than the vocoder's 16 kHz is resampled on the device first (resample.py), on the
+        plain and the windowed path alike, and everything downstream sees the 16 kHz clip; without it such a rate raises.
+        output_sampling_rate: as in AudioLDMPipeline.__call__ (not with output_type="latent").
+        window_length_in_s / window_overlap_in_s / loop / window_prompts / window_prompt_embeds: as in AudioLDMPipeline.__call__
         (None: one clip at the recording's own length, as ever).  With windows, `mask` and `latents` are those of the LONG clip, whose
         length is audio_length_in_s or the recording's (a looped plan rounds it UP and the longer clip is returned)."""
         if self.device.type != "cuda":
@@ -153,7 +158,14 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
             raise ValueError(f"output_type must be 'np', 'pt' or 'latent', got {output_type!r}")
         vc = self.vocoder.config
         if int(sampling_rate) != int(vc.sampling_rate):
-            raise ValueError(f"audio at {sampling_rate} Hz: the vocoder runs at {vc.sampling_rate} Hz and there is no resampler here")
+            if not resample:
+                raise ValueError(f"audio at {sampling_rate} Hz: the vocoder runs at {vc.sampling_rate} Hz; pass resample=True to resample "
+                                 "the recording on the device first")
+            ratio(sampling_rate, vc.sampling_rate)                  # (raises on a rate that cannot be reached, before any work)
+        if output_sampling_rate is not None:
+            if output_type == "latent":
+                raise ValueError("output_sampling_rate applies to a waveform, not to output_type='latent'")
+            ratio(vc.sampling_rate, output_sampling_rate)
         _, begin = self.scheduler.get_timesteps(num_inference_steps, strength)    # raises on a strength that leaves no step
         if window_length_in_s is None:
             if loop or window_prompts is not None or window_prompt_embeds is not None or window_overlap_in_s is not None:
@@ -165,6 +177,9 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
         prompt_embeds, negative_prompt_embeds = self._prompt_embeds(prompt, prompt_embeds, negative_prompt, negative_prompt_embeds,
                                                                     guidance_scale, num_waveforms_per_prompt)
         batch = prompt_embeds.shape[0]
+        if int(sampling_rate) != int(vc.sampling_rate):             # resample=True: the recording becomes its 16 kHz form here
+            a = torch.as_tensor(np.asarray(audio, dtype=np.float32)) if not torch.is_tensor(audio) else audio.detach().float()
+            audio = Resampler(sampling_rate, vc.sampling_rate, self.device)(a.to(self.device))
         wav = self._audio_batch(audio, batch, num_waveforms_per_prompt)
         if audio_length_in_s is None:
             audio_length_in_s = wav.shape[-1] / float(vc.sampling_rate)
@@ -225,15 +240,18 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
             eng.capture()
         eng.run()
         mel_out = None
+        rate = int(vc.sampling_rate)
         if output_type == "latent":
             out = eng.latents_nchw()
         else:
             wav_out, mel_out = self.decode_latents_nhwc(eng.x) if plan is None else self.decode_windows_nhwc(eng.x, plan, mel_plan, loop)
             out = wav_out[:, :n_samples]
+            if output_sampling_rate is not None:
+                out, rate = resample_audio(out, rate, output_sampling_rate), int(output_sampling_rate)
             if output_type == "np":
                 out = out.float().cpu().numpy()
         if not return_dict:
             return (out,)
         if plan is not None:                            # a windowed call also hands back its plan and the blended mel [B, T, 64] (device)
-            return AudioPipelineOutput(audios=out, plan=plan, mel=None if mel_out is None else mel_out[..., 0])
-        return AudioPipelineOutput(audios=out)
+            return AudioPipelineOutput(audios=out, sampling_rate=rate, plan=plan, mel=None if mel_out is None else mel_out[..., 0])
+        return AudioPipelineOutput(audios=out, sampling_rate=rate)

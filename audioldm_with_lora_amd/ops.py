@@ -1582,6 +1582,34 @@ def gaussian_sample(params_nchw, noise):
     return out
 
 
+def resample_poly(x, up, down, lens=None, table=None):
+    """scipy.signal.resample_poly(x, up, down) on the device (aldm_resample_poly; resample.py has the definition): x fp32 [B, T] whose
+    row b holds lens[b] samples (all T when None) -> (y fp32 [B, ceil(T up / down)], out_lens int32 [B] on the host); y is 0 from
+    out_lens[b] = ceil(lens[b] up / down) on.  table: resample.phase_table(up, down) on x's device (looked up when None)."""
+    from . import resample as R
+    up, down = R.check_ratio(up, down)
+    _require_gpu(x)
+    if x.dim() != 2 or x.numel() == 0:
+        raise ValueError(f"resample_poly: x must be a non-empty [B, T], got {tuple(x.shape)}")
+    x = x.to(torch.float32).contiguous()
+    B, T = x.shape
+    lens = torch.full((B,), T, dtype=torch.int32) if lens is None else torch.as_tensor(lens).to("cpu", torch.int32).reshape(-1)
+    if lens.numel() != B or int(lens.min()) < 0 or int(lens.max()) > T:
+        raise ValueError(f"resample_poly: lens must hold {B} lengths in [0, {T}], got {lens.tolist()}")
+    if table is None:
+        table = R.device_table(up, down, x.device)
+    half = 10 * max(up, down)
+    K = -(-(2 * half + 1) // up)
+    if tuple(table.shape) != (up, K) or table.dtype != torch.float32 or table.device != x.device or not table.is_contiguous():
+        raise ValueError(f"resample_poly: table must be contiguous fp32 [{up}, {K}] on {x.device}")
+    T_out = R.output_length(T, up, down)
+    y = torch.empty(B, T_out, dtype=torch.float32, device=x.device)
+    dl = lens.to(x.device)
+    check(_lib.load().aldm_resample_poly(_p(x), _p(dl), B, T, _p(table), up, down, K, half, _p(y), T_out, _stream()),
+          "aldm_resample_poly")
+    return y, ((lens.to(torch.int64) * up + down - 1) // down).to(torch.int32)
+
+
 def train_noise_fused(state, alphas_cumprod, moments=None, latents=None, scaling_factor=1.0, noise_offset=0.0, ticket=None,
                       timesteps_out=None):
     """The training step's batch noising with on-device randomness as one launch (aldm_train_noise_fused; stream contract in

@@ -16,6 +16,7 @@ import torch
 from . import ops
 from .engine import DenoiseEngine, WindowedDenoiseEngine
 from .longform import plan_for_seconds
+from .resample import ratio, resample
 from .scheduler import DDIMScheduler, _fresh_seed
 from .unet import UNet2DConditionModel
 from .vae import AutoencoderKL
@@ -281,8 +282,10 @@ class AudioLDMPipeline:
                  negative_prompt=None, num_waveforms_per_prompt=1, eta=0.0, generator=None, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, return_dict=True, output_type="np", adapter_names=None,
                  adapter_weights=None, window_length_in_s=None, window_overlap_in_s=None, loop=False, window_prompts=None,
-                 window_prompt_embeds=None, **kw):
-        """window_length_in_s (default None: one clip of audio_length_in_s, as ever) turns on windowed denoising for clips longer
+                 window_prompt_embeds=None, output_sampling_rate=None, **kw):
+        """output_sampling_rate (default None: the vocoder's 16 kHz, as ever): the trimmed waveform is resampled to this rate on the
+        device before it leaves for the host (resample.py; ceil(n_samples up / down) samples); the output carries `sampling_rate`.
+        window_length_in_s (default None: one clip of audio_length_in_s, as ever) turns on windowed denoising for clips longer
         than the UNet was trained on: overlapping windows of that length (window_overlap_in_s, default a quarter of it) along one
         long latent, blended at every step; loop=True makes the clip close on itself (its length is rounded UP to a whole number of
         window strides).  window_prompts: K strings per prompt, or window_prompt_embeds [B, K, D] -- one prompt per window."""
@@ -291,6 +294,8 @@ class AudioLDMPipeline:
         if eta != 0.0:
             raise NotImplementedError("the reference path uses eta = 0")
         vc = self.vocoder.config
+        if output_sampling_rate is not None:
+            ratio(vc.sampling_rate, output_sampling_rate)           # (raises on a rate that cannot be reached, before any work)
         if audio_length_in_s is None:
             # diffusers: unet.config.sample_size * vae_scale_factor * prod(upsample_rates) / sampling_rate
             inner = getattr(getattr(self.unet, "base_model", None), "model", self.unet)          # a PeftModel wraps the UNet
@@ -336,10 +341,13 @@ class AudioLDMPipeline:
         eng.run()
         wav, mel = self.decode_latents_nhwc(eng.x) if plan is None else self.decode_windows_nhwc(eng.x, plan, mel_plan, loop)
         audio = wav[:, :n_samples]
+        rate = int(vc.sampling_rate)
+        if output_sampling_rate is not None:
+            audio, rate = resample(audio, rate, output_sampling_rate), int(output_sampling_rate)
         if output_type == "np":
             audio = audio.float().cpu().numpy()
         if not return_dict:
             return (audio,)
         if plan is not None:                            # a windowed call also hands back its plan and the blended mel [B, T, 64] (device)
-            return AudioPipelineOutput(audios=audio, plan=plan, mel=mel[..., 0])
-        return AudioPipelineOutput(audios=audio)
+            return AudioPipelineOutput(audios=audio, sampling_rate=rate, plan=plan, mel=mel[..., 0])
+        return AudioPipelineOutput(audios=audio, sampling_rate=rate)

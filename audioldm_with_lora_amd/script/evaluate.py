@@ -2,7 +2,8 @@
 script/inference/inference.py sets out to do (the shipped file does not parse).
 
 Reads every *.wav of --gen-dir / --ref-dir with scipy.io.wavfile (the 16 kHz float32 files script/inference.py writes;
-int PCM is scaled to [-1, 1], stereo is mono-mixed), embeds them with the CLAP model of --clap-dir on the HIP kernels, and
+int PCM is scaled to [-1, 1], stereo is mono-mixed; a file at another rate is brought to 16 kHz on the device, resample.py --
+what the reference's librosa.load(sr=16000) does, with this library's filter), embeds them with the CLAP model of --clap-dir on the HIP kernels, and
 prints one JSON line: the CLAP score of every generated file against --prompt, their mean, and KAD in the inference.py
 variant (bandwidth 1, no scale).  Clips must be at most 10 s long.
 
@@ -16,22 +17,30 @@ import os
 import numpy as np
 
 
-def load_wav_16k(path):
+def load_wav(path):
+    """(rate, mono fp32 samples) of a wav file"""
     from scipy.io import wavfile
     sr, x = wavfile.read(path)
-    if sr != 16000:
-        raise ValueError(f"{path}: {sr} Hz (16 kHz files expected)")
     if np.issubdtype(x.dtype, np.integer):
         x = x.astype(np.float32) / float(np.iinfo(x.dtype).max + 1)
     x = np.asarray(x, dtype=np.float32)
-    return x.mean(axis=1) if x.ndim == 2 else x
+    return int(sr), (x.mean(axis=1) if x.ndim == 2 else x)
+
+
+def to_16k(rate, x, device="cuda"):
+    """a clip at 16 kHz: itself (the host array, untouched), or resampled on the device (a GPU tensor)"""
+    if rate == 16000:
+        return x
+    import torch
+    from ..resample import resample
+    return resample(torch.from_numpy(np.ascontiguousarray(x)).to(device), rate, 16000)
 
 
 def load_dir(d):
     names = sorted(f for f in os.listdir(d) if f.lower().endswith(".wav"))
     if len(names) < 2:
         raise ValueError(f"{d}: KAD needs at least two .wav files, found {len(names)}")
-    return names, [load_wav_16k(os.path.join(d, n)) for n in names]
+    return names, [to_16k(*load_wav(os.path.join(d, n))) for n in names]
 
 
 def main(argv=None):

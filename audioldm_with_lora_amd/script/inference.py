@@ -10,7 +10,9 @@ script's inconsistent 4 (quirk Q3) -- pass --lora-alpha 4 to reproduce the scrip
 `--scheduler unipc --steps 8` swaps in UniPCMultistepScheduler (predictor-corrector, the sampler for 5-10 steps; `--solver-order` applies).
 `--scheduler euler-a` swaps in EulerAncestralDiscreteScheduler (stochastic: fresh noise in every step, drawn on the device); `--seed` then
 seeds both the initial noise and that in-loop stream.
-`--init-audio in.wav --strength 0.5` starts from a 16 kHz recording (AudioLDMAudioToAudioPipeline: style transfer toward the prompt);
+`--init-audio in.wav --strength 0.5` starts from a recording (AudioLDMAudioToAudioPipeline: style transfer toward the prompt); a file
+that is not at the model's 16 kHz (44.1 / 48 kHz, ...) is resampled on the device first, and `--output-sampling-rate R` writes the
+wav files at R Hz instead of 16 kHz (resample.py: scipy.signal.resample_poly's filter);
 `--regenerate-seconds T0,T1` / `--regenerate-bands F0,F1` regenerate only that time span / fraction of the mel bins and keep the rest.
 `--lora NAME=PATH` (repeatable) loads named adapters side by side; `--adapters SPEC` routes them per prompt -- a comma list with one item
 per prompt (`--prompt` then takes prompts separated by `|`): `NAME`, `NAME:0.7`, `base`, or a blend `A:0.5+B:0.5`.  One call, one
@@ -90,7 +92,8 @@ def parse_args(argv=None):
     ap.add_argument("--output", default="./generated_audio_LoRA/ex.wav")
     ap.add_argument("--seed", type=int, default=None, help="seed of the initial-noise generator and, with --scheduler euler-a, of the in-loop noise stream (the reference seeds "
                          "nothing, quirk Q5)")
-    ap.add_argument("--init-audio", default=None, help="16 kHz wav to start from (audio-to-audio); read with scipy")
+    ap.add_argument("--init-audio", default=None, help="wav to start from (audio-to-audio), any rate: resampled to the model's on the device; read with scipy")
+    ap.add_argument("--output-sampling-rate", type=int, default=None, metavar="R", help="write the wav files at R Hz (default: the model's 16000)")
     ap.add_argument("--strength", type=float, default=0.5, help="with --init-audio: how much of the schedule to run (1 = from noise)")
     ap.add_argument("--regenerate-seconds", default=None, help="with --init-audio: T0,T1 -- regenerate only this time span")
     ap.add_argument("--regenerate-bands", default=None, help="with --init-audio: F0,F1 -- regenerate only this fraction of the mel bins")
@@ -101,6 +104,8 @@ def parse_args(argv=None):
     ap.add_argument("--adapters", default=None, metavar="SPEC",
                     help="per-prompt routing, one item per prompt (prompts separated by '|'): NAME, NAME:0.7, base, A:0.5+B:0.5")
     args = ap.parse_args(argv)
+    if args.output_sampling_rate is not None and args.output_sampling_rate <= 0:
+        ap.error("--output-sampling-rate expects a positive rate in Hz")
     if args.adapters and not args.lora:
         ap.error("--adapters needs --lora NAME=PATH")
     if args.init_audio is None and (args.regenerate_seconds or args.regenerate_bands):
@@ -144,6 +149,8 @@ def main(argv=None):
         name, _, path = item.partition("=")
         pipe.load_lora_weights(path, adapter_name=name)
     generator = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
+    out_rate = int(pipe.vocoder.config.sampling_rate) if args.output_sampling_rate is None else args.output_sampling_rate
+    rated = {} if args.output_sampling_rate is None else {"output_sampling_rate": args.output_sampling_rate}
     windowed = {}
     if args.window_seconds is not None:
         windowed = dict(window_length_in_s=args.window_seconds, window_overlap_in_s=args.window_overlap_seconds, loop=args.loop)
@@ -157,27 +164,27 @@ def main(argv=None):
         if "window_prompts" in windowed:                # the same prompt schedule for every routed clip
             windowed["window_prompts"] = [windowed["window_prompts"]] * len(prompts)
         if args.init_audio is not None and windowed:
-            audios = _audio_to_audio(pipe, args, generator, windowed, prompt=prompts, adapter_names=routing)
+            audios = _audio_to_audio(pipe, args, generator, windowed, prompt=prompts, adapter_names=routing, **rated)
         else:
             audios = pipe(prompt=prompts, num_inference_steps=args.steps, adapter_names=routing,
                           audio_length_in_s=10.0 if args.audio_length is None else args.audio_length,
-                          guidance_scale=args.guidance_scale, generator=generator, **windowed).audios
+                          guidance_scale=args.guidance_scale, generator=generator, **windowed, **rated).audios
         from scipy.io import wavfile
         stem, ext = os.path.splitext(os.path.abspath(args.output))
         os.makedirs(os.path.dirname(stem), exist_ok=True)
         for i, a in enumerate(audios):
-            wavfile.write(f"{stem}_{i}{ext or '.wav'}", 16000, np.asarray(a, dtype=np.float32))
+            wavfile.write(f"{stem}_{i}{ext or '.wav'}", out_rate, np.asarray(a, dtype=np.float32))
         print(f"Generated {len(audios)} clips saved to: {stem}_*{ext or '.wav'}")
         return
     if args.init_audio is None:
         audio = pipe(prompt=args.prompt, num_inference_steps=args.steps,
                      audio_length_in_s=10.0 if args.audio_length is None else args.audio_length,
-                     guidance_scale=args.guidance_scale, generator=generator, **windowed).audios[0]
+                     guidance_scale=args.guidance_scale, generator=generator, **windowed, **rated).audios[0]
     else:
-        audio = _audio_to_audio(pipe, args, generator, windowed)[0]
+        audio = _audio_to_audio(pipe, args, generator, windowed, **rated)[0]
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     from scipy.io import wavfile
-    wavfile.write(args.output, 16000, np.asarray(audio, dtype=np.float32))
+    wavfile.write(args.output, out_rate, np.asarray(audio, dtype=np.float32))
     print(f"Generated audio saved to: {args.output}")
 
 
@@ -209,9 +216,12 @@ def read_wav(path):
 
 def _audio_to_audio(pipe, args, generator, windowed=None, **routed):
     """the clips of an --init-audio call; windowed: the window keywords of a --window-seconds call; routed: prompt= / adapter_names= of
-    an --adapters call (one clip per routing entry, all from the same recording)"""
+    an --adapters call (one clip per routing entry, all from the same recording), and output_sampling_rate="""
     sr, wav = read_wav(args.init_audio)
     a2a = AudioLDMAudioToAudioPipeline.from_pipe(pipe)
+    model_rate = int(a2a.vocoder.config.sampling_rate)
+    if sr != model_rate:
+        print(f"Resampling {args.init_audio}: {sr} Hz -> {model_rate} Hz")
     windowed = dict(windowed or {})
     recording = wav.shape[0] / float(sr)
     seconds = recording if args.audio_length is None else args.audio_length
@@ -231,7 +241,7 @@ def _audio_to_audio(pipe, args, generator, windowed=None, **routed):
                                  seconds=_pair(args.regenerate_seconds, "--regenerate-seconds") if args.regenerate_seconds else None,
                                  bands=_pair(args.regenerate_bands, "--regenerate-bands") if args.regenerate_bands else None)
     routed.setdefault("prompt", args.prompt)
-    return a2a(audio=wav, sampling_rate=sr, strength=strength, mask=mask, audio_length_in_s=seconds, num_inference_steps=args.steps,
+    return a2a(audio=wav, sampling_rate=sr, resample=sr != model_rate, strength=strength, mask=mask, audio_length_in_s=seconds, num_inference_steps=args.steps,
                guidance_scale=args.guidance_scale, generator=generator, **windowed, **routed).audios
 
 

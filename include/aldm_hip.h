@@ -714,6 +714,17 @@ int aldm_patch_merge_gather(const void* x, int B, int H, int W, int C, void* out
 /* mean over the N tokens of x bf16 [B][N][C] -> out_f32 fp32 [B][C] and out_bf16 bf16 [B][C] */
 int aldm_token_mean(const void* x, int B, int N, int C, float* out_f32, void* out_bf16, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Rational polyphase FIR resampler (csrc/resample.hip): scipy.signal.resample_poly(x, up, down) with its default
+ * Kaiser(5.0) filter h (2 half + 1 taps, half = 10 max(up, down)) and zero padding.  table fp32 [up][K],
+ * K = ceil((2 half + 1) / up), table[p][k] = h[p + k up] (zero behind the end of h): resample.phase_table.
+ *   m = n down + half,  y[b][n] = sum_k table[m mod up][k] x[b][m div up - k]      (x[b][j] = 0 outside [0, lens[b]))
+ * for n < ceil(lens[b] up / down), else 0.  x fp32 [B][T_in], y fp32 [B][T_out], T_out = ceil(T_in up / down).
+ * max(up, down) > 2048, a half / K / T_out that does not match, B > 65535: ALDM_E_ARG.
+ * ------------------------------------------------------------------------------------------ */
+int aldm_resample_poly(const float* x, const int* lens, int B, int T_in, const float* table, int up, int down, int K, int half,
+                       float* y, int T_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
