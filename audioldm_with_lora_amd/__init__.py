@@ -2,7 +2,7 @@
 
 Drop-in surface for the reference's entry points:
 AudioLDMPipeline / UNet2DConditionModel / AutoencoderKL / SpeechT5HifiGan / DDIMScheduler / DPMSolverMultistepScheduler /
-UniPCMultistepScheduler / EulerAncestralDiscreteScheduler (all four in scheduler.py; the last two exported here on first use as well) and the peft-shaped LoraConfig / get_peft_model helpers; AudioLDMAudioToAudioPipeline (audio2audio.py,
+UniPCMultistepScheduler / EulerAncestralDiscreteScheduler / RePaintScheduler (all five in scheduler.py; the last three exported here on first use as well) and the peft-shaped LoraConfig / get_peft_model helpers; AudioLDMAudioToAudioPipeline (audio2audio.py,
 exported here on first use) starts from a recording; Resampler / resample (resample.py, likewise) bring audio of any rate to another
 on the device.  No CPU fallback: ops raise if libaldm_hip.so is missing.
 """
@@ -19,6 +19,9 @@ def __getattr__(name):
     if name == "EulerAncestralDiscreteScheduler":
         from .scheduler import EulerAncestralDiscreteScheduler
         return EulerAncestralDiscreteScheduler
+    if name == "RePaintScheduler":
+        from .scheduler import RePaintScheduler
+        return RePaintScheduler
     if name == "Resampler":
         from .resample import Resampler
         return Resampler

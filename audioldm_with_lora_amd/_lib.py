@@ -244,6 +244,9 @@ for _solver, _operand in (("ddim", []), ("dpm", [C.c_void_p]), ("euler_a", [C.c_
     # the masked windowed steps (audio-to-audio on a long latent): the windowed list, then the inpainting operands behind the plan
     PROTOTYPES[f"aldm_{_solver}_step_fused_windowed_masked"] = (C.c_int, _STEP_HEAD + _operand + _STEP_TAIL + [C.POINTER(WindowPlanArgs)]
                                                                 + _STEP_INPAINT + [C.c_void_p])
+# RePaint exists only masked: the Euler-ancestral masked lists (the operand is the Philox state; `noise` may be NULL)
+PROTOTYPES["aldm_repaint_step_fused_masked"] = PROTOTYPES["aldm_euler_a_step_fused_masked"]
+PROTOTYPES["aldm_repaint_step_fused_windowed_masked"] = PROTOTYPES["aldm_euler_a_step_fused_windowed_masked"]
 
 _lib = None
 

@@ -12,6 +12,10 @@ rows are then in sigma space, (a, s) = (1, sigma).
     x  = a_begin x0 + s_begin eps                         (x = eps exactly at strength 1)
     for k, t in enumerate(timesteps[begin:]):  x = step(unet(x, t), t, x);  x = (1 - m) (a_k x0 + s_k eps) + m x
 
+With a RePaintScheduler the masked loop is RePaint's instead of the legacy one: the known latents are noised
+with FRESH noise at every step and the walk jumps back up the schedule so that the regenerated region can come to agree with what
+was pasted in (aldm_repaint_step_fused[_windowed]_masked).  It needs `mask=` and strength 1.0.
+
 Long recordings: `window_length_in_s=` runs all of the above on ONE long latent as overlapping windows of the
 trained length -- the recording is encoded window by window and the moments blended into the long layout, the loop is the windowed
 fused step with the blend inside it (aldm_*_step_fused_windowed[_masked]), and the decode is the windowed one.  A mask that keeps
@@ -26,6 +30,7 @@ from .mel import LogMelFrontEnd
 from .pipeline import AudioLDMPipeline, AudioPipelineOutput, _frozen_config
 from .resample import Resampler, ratio
 from .resample import resample as resample_audio
+from .scheduler import RePaintScheduler
 
 HOP_SECONDS = 0.01        # one mel frame per 160 samples at 16 kHz
 
@@ -154,6 +159,9 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
             raise ops._lib.AldmError("AudioLDMAudioToAudioPipeline runs on the MI355X only: call .to('cuda') (no CPU fallback)")
         if audio is None:
             raise ValueError("pass audio= (the recording to start from)")
+        if isinstance(self.scheduler, RePaintScheduler) and mask is None:
+            raise ValueError("RePaintScheduler needs mask=: RePaint resamples a masked region against the kept one (style transfer "
+                             "without a mask takes another scheduler)")
         if output_type not in ("np", "pt", "latent"):
             raise ValueError(f"output_type must be 'np', 'pt' or 'latent', got {output_type!r}")
         vc = self.vocoder.config

@@ -135,15 +135,19 @@ __device__ __forceinline__ float unipc_predict(float xc, float m0, float mt, flo
   return fmaf(Ap, xc, fmaf(Bp, mt, Cp * (mt - m0)));
 }
 
-// ---- the fused scheduler step: one frame (step_fused_body), four solvers ---------------------------------------------------------
+// ---- the fused scheduler step: one frame (step_fused_body), five solvers ---------------------------------------------------------
 // What the frame asks of a scheduler.  ROW: the floats per row of its coefficient table.  TICKET_OPTIONAL: whether its entry points
-// take ticket == NULL (the eager scheduler.step: the counter is left alone, and table is NULL there too).  Its one extra kernel
+// take ticket == NULL (the eager scheduler.step: the counter is left alone, and table is NULL there too).  DRAWS_BLEND_NOISE: whether
+// the inpainting blend's noise comes from the solver, not from Inpaint::noise (which may then be NULL).  Its one extra kernel
 // operand, if any, as the first member (the kernels build the solver from it, UniPC's also from the counter and the element count that
-// they hold anyway; every other member starts at zero).  And six hooks,
+// they hold anyway; every other member starts at zero).  And eight hooks,
 // which every thread calls in this order:
 //   begin()             before the bounds test: the state that the last workgroup moves, read where the counter is read
 //   load<VEC>(cf, idx)  the coefficient row `cf` and whatever else the update of elements [idx, idx + VEC) reads
+//   blend_noise<VEC>(noise, idx)  (masked only) the noise of the blend for elements [idx, idx + VEC): Inpaint::noise as it lies in
+//                       memory (the identity, requested ahead of load), or, with DRAWS_BLEND_NOISE, what load drew
 //   update<VEC>(k, ..)  element k's new latent, through the solver's one-element function above
+//   after_blend(k, r)   what becomes of the (blended) latent before it is stored: the identity, but for RePaint's jump
 //   unet_input(r)       the value whose bf16 rounding is the next UNet input
 //   store<VEC>(idx)     what is stored beside x
 //   advance()           what the last workgroup stores beside the counter
@@ -153,6 +157,7 @@ using fvec_t = float __attribute__((ext_vector_type(VEC)));
 struct DdimSolver {
   static constexpr int ROW = 4;
   static constexpr bool TICKET_OPTIONAL = false;
+  static constexpr bool DRAWS_BLEND_NOISE = false;
   float sa, sb, sap, sbp;
   __device__ __forceinline__ void begin() {}
   template <int VEC>
@@ -163,6 +168,11 @@ struct DdimSolver {
   __device__ __forceinline__ float update(int, float eu, float et, float xv, int cfg, float g) {
     return ddim_update(eu, et, xv, cfg, g, sa, sb, sap, sbp);
   }
+  template <int VEC>
+  __device__ __forceinline__ fvec_t<VEC> blend_noise(const float* __restrict__ noise, long long idx) const {
+    return *reinterpret_cast<const fvec_t<VEC>*>(noise + idx);
+  }
+  __device__ __forceinline__ float after_blend(int, float r) const { return r; }
   __device__ __forceinline__ float unet_input(float r) const { return r; }
   template <int VEC> __device__ __forceinline__ void store(long long) {}
   __device__ __forceinline__ void advance() {}
@@ -174,6 +184,7 @@ struct DdimSolver {
 struct DpmSolver {
   static constexpr int ROW = 8;
   static constexpr bool TICKET_OPTIONAL = true;
+  static constexpr bool DRAWS_BLEND_NOISE = false;
   float* __restrict__ hist;
   float alpha_s, sig_s, A, Bc, Cc;
   bool convert, second;
@@ -194,6 +205,11 @@ struct DpmSolver {
     m0[k] = dpm_model_output(eu, et, xv, cfg, g, alpha_s, sig_s, convert);
     return dpm_update(m0[k], second ? m1[k] : m0[k], xv, A, Bc, Cc);
   }
+  template <int VEC>
+  __device__ __forceinline__ fvec_t<VEC> blend_noise(const float* __restrict__ noise, long long idx) const {
+    return *reinterpret_cast<const fvec_t<VEC>*>(noise + idx);
+  }
+  __device__ __forceinline__ float after_blend(int, float r) const { return r; }
   __device__ __forceinline__ float unet_input(float r) const { return r; }
   template <int VEC>
   __device__ __forceinline__ void store(long long idx) {
@@ -213,6 +229,7 @@ struct DpmSolver {
 struct EulerASolver {
   static constexpr int ROW = 4;
   static constexpr bool TICKET_OPTIONAL = true;
+  static constexpr bool DRAWS_BLEND_NOISE = false;
   uint32_t* __restrict__ rng;
   PhiloxState rs;
   float dt, sigma_up, in_scale;
@@ -231,9 +248,64 @@ struct EulerASolver {
   __device__ __forceinline__ float update(int k, float eu, float et, float xv, int cfg, float g) {
     return euler_a_update(eu, et, xv, cfg, g, dt, sigma_up, z[k]);
   }
+  template <int VEC>
+  __device__ __forceinline__ fvec_t<VEC> blend_noise(const float* __restrict__ noise, long long idx) const {
+    return *reinterpret_cast<const fvec_t<VEC>*>(noise + idx);
+  }
+  __device__ __forceinline__ float after_blend(int, float r) const { return r; }
   __device__ __forceinline__ float unet_input(float r) const { return r * in_scale; }
   template <int VEC> __device__ __forceinline__ void store(long long) {}
   __device__ __forceinline__ void advance() { philox_store_next(rng, rs); }
+};
+
+// RePaint (Lugmayr et al., CVPR 2022, Algorithm 1) on a coefficient row {sa, sb, sap, sbp, c1, c2, -, -} (scheduler.py
+// RePaintScheduler.coefficient_table): the DDIM update (eta = 0), the inpainting blend with FRESH noise zk for the known part (line 4
+// of the algorithm; the legacy loop reuses the eps it started from), then the closed-form jump back up over the row's J levels,
+//   x' = c1 xb + c2 zj        ((c1, c2) == (1, 0) on rows without a jump: zj is then not generated and x' = xb)
+// Both noises are generated HERE (draw contract: philox.h): zk is element i of draw d, zj element i of draw d + 1, where d is the
+// ordinal the launch finds and i the element's index in the [B][n] latents (the long latents when windowed); the last workgroup
+// leaves the ordinal at d + 2 on every row.  Only masked entry points exist: without a mask there is nothing to resample towards.
+__device__ __forceinline__ float repaint_jump(float xb, float c1, float c2, float zj) { return fmaf(c2, zj, c1 * xb); }
+
+__device__ __forceinline__ f32x4 philox_normal_lanes(const PhiloxState& s, long long idx, int vec) {
+  f32x4 z = philox_normal4(s, (unsigned long long)(idx >> 2));
+  if (vec == 1) {
+    const int lane = (int)(idx & 3);
+    z[0] = lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3];
+  }
+  return z;
+}
+
+struct RepaintSolver {
+  static constexpr int ROW = 8;
+  static constexpr bool TICKET_OPTIONAL = true;
+  static constexpr bool DRAWS_BLEND_NOISE = true;
+  uint32_t* __restrict__ rng;
+  PhiloxState rs;
+  float sa, sb, sap, sbp, c1, c2;
+  f32x4 zk, zj;                                               // lanes [0, VEC): the normals of elements idx + k
+  __device__ __forceinline__ void begin() { rs = philox_load(rng); }
+  template <int VEC>
+  __device__ __forceinline__ void load(const float* __restrict__ cf, long long idx) {
+    sa = cf[0], sb = cf[1], sap = cf[2], sbp = cf[3], c1 = cf[4], c2 = cf[5];
+    zk = philox_normal_lanes(rs, idx, VEC);
+    if (c2 != 0.f) zj = philox_normal_lanes(philox_at(rs, 1), idx, VEC);   // (uniform over the grid)
+  }
+  template <int VEC>
+  __device__ __forceinline__ fvec_t<VEC> blend_noise(const float* __restrict__, long long) const {
+    fvec_t<VEC> v;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) v[k] = zk[k];
+    return v;
+  }
+  template <int VEC>
+  __device__ __forceinline__ float update(int, float eu, float et, float xv, int cfg, float g) {
+    return ddim_update(eu, et, xv, cfg, g, sa, sb, sap, sbp);
+  }
+  __device__ __forceinline__ float after_blend(int k, float r) const { return c2 != 0.f ? repaint_jump(r, c1, c2, zj[k]) : c1 * r; }
+  __device__ __forceinline__ float unet_input(float r) const { return r; }
+  template <int VEC> __device__ __forceinline__ void store(long long) {}
+  __device__ __forceinline__ void advance() { philox_store_ordinal(rng, philox_at(rs, 2)); }
 };
 
 // state [3][B][n] fp32: plane 0 the last corrected sample, planes 1 and 2 the previous two converted model outputs as a RING indexed by
@@ -245,6 +317,7 @@ struct EulerASolver {
 struct UniPCSolver {
   static constexpr int ROW = 16;
   static constexpr bool TICKET_OPTIONAL = true;
+  static constexpr bool DRAWS_BLEND_NOISE = false;
   float* __restrict__ state;
   const int* __restrict__ step_idx;
   long long total;                                            // B * n: the stride between the planes of state
@@ -279,6 +352,11 @@ struct UniPCSolver {
     xc[k] = corr ? unipc_correct(last[k], m0[k], c2 ? m1[k] : m0[k], mt[k], Ac, Bc, Cc, Dc) : xv;
     return unipc_predict(xc[k], p2 ? m0[k] : mt[k], mt[k], Ap, Bp, Cp);
   }
+  template <int VEC>
+  __device__ __forceinline__ fvec_t<VEC> blend_noise(const float* __restrict__ noise, long long idx) const {
+    return *reinterpret_cast<const fvec_t<VEC>*>(noise + idx);
+  }
+  __device__ __forceinline__ float after_blend(int, float r) const { return r; }
   __device__ __forceinline__ float unet_input(float r) const { return r; }
   template <int VEC>
   __device__ __forceinline__ void store(long long idx) {
@@ -401,9 +479,10 @@ __device__ __forceinline__ void step_fused_body(const float* __restrict__ eps, f
     fvec kx0, knz;
     if constexpr (MASKED) {
       kx0 = *reinterpret_cast<const fvec*>(ip.x0 + idx);
-      knz = *reinterpret_cast<const fvec*>(ip.noise + idx);
+      if constexpr (!Solver::DRAWS_BLEND_NOISE) knz = s.template blend_noise<VEC>(ip.noise, idx);
     }
     s.template load<VEC>(coef + Solver::ROW * cur, idx);
+    if constexpr (MASKED && Solver::DRAWS_BLEND_NOISE) knz = s.template blend_noise<VEC>(ip.noise, idx);   // (drawn by load)
     fvec xn;
     bvec xb;
 #pragma unroll
@@ -411,6 +490,7 @@ __device__ __forceinline__ void step_fused_body(const float* __restrict__ eps, f
       float r = s.template update<VEC>(k, eu[k], et[k], xv[k], cfg, g);
       if constexpr (MASKED)
         r = inpaint_blend(r, kx0[k], knz[k], ip.mask[(unsigned)(idx + k) / (unsigned)ip.C], ip.blend[2 * cur], ip.blend[2 * cur + 1]);
+      r = s.after_blend(k, r);
       xn[k] = r;
       xb[k] = (bf16)s.unet_input(r);
     }
@@ -519,6 +599,22 @@ __global__ __launch_bounds__(256) void euler_a_step_fused_masked_kernel(const fl
   step_fused_body<EulerASolver, VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, EulerASolver{rng}, table, row_elems, rowbias,
                                            timesteps, n_steps, t_out, ticket,
                                            (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
+}
+
+// (euler_a_step_fused_masked_kernel's parameter list; `noise` is carried for the shared launcher and never read)
+template <int VEC>
+__global__ __launch_bounds__(256) void repaint_step_fused_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                        int cfg, float g, const float* __restrict__ coef,
+                                                                        int* __restrict__ step_idx, bf16* __restrict__ x_in,
+                                                                        uint32_t* __restrict__ rng, const float* __restrict__ table,
+                                                                        long long row_elems, float* __restrict__ rowbias,
+                                                                        const float* __restrict__ timesteps, int n_steps, float* __restrict__ t_out,
+                                                                        unsigned* __restrict__ ticket, const float* __restrict__ x0,
+                                                                        const float* __restrict__ noise, const float* __restrict__ mask,
+                                                                        const float* __restrict__ blend, int C) {
+  step_fused_body<RepaintSolver, VEC, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, RepaintSolver{rng}, table, row_elems, rowbias,
+                                            timesteps, n_steps, t_out, ticket,
+                                            (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C});
 }
 
 template <int VEC>
@@ -648,6 +744,20 @@ __global__ __launch_bounds__(256) void euler_a_step_fused_windowed_masked_kernel
                                                                                  int hw, long long wc, const float* __restrict__ x0, const float* __restrict__ noise,
                                                                                  const float* __restrict__ mask, const float* __restrict__ blend, int C) {
   step_fused_body<EulerASolver, VEC, true, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, EulerASolver{rng}, table, row_elems, rowbias, timesteps,
+      n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C},
+      Windows{offset, cover, weight, K, KC, rows, hw, wc});
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void repaint_step_fused_windowed_masked_kernel(const float* __restrict__ eps, float* __restrict__ x, int B, long long n,
+                                                                                 int cfg, float g, const float* __restrict__ coef, int* __restrict__ step_idx,
+                                                                                 bf16* __restrict__ x_in, uint32_t* __restrict__ rng, const float* __restrict__ table,
+                                                                                 long long row_elems, float* __restrict__ rowbias, const float* __restrict__ timesteps,
+                                                                                 int n_steps, float* __restrict__ t_out, unsigned* __restrict__ ticket,
+                                                                                 const int* offset, const int* cover, const float* weight, int K, int KC, int rows,
+                                                                                 int hw, long long wc, const float* __restrict__ x0, const float* __restrict__ noise,
+                                                                                 const float* __restrict__ mask, const float* __restrict__ blend, int C) {
+  step_fused_body<RepaintSolver, VEC, true, true>(eps, x, B, n, cfg, g, coef, step_idx, x_in, RepaintSolver{rng}, table, row_elems, rowbias, timesteps,
       n_steps, t_out, ticket, (long long)blockIdx.x * blockDim.x + threadIdx.x, Inpaint{x0, noise, mask, blend, C},
       Windows{offset, cover, weight, K, KC, rows, hw, wc});
 }
@@ -1044,7 +1154,7 @@ static int launch_step_fused(const char* name, Kernel k4, Kernel k1, const float
   ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
                  "%s: table needs ticket, rowbias and row_elems %% 4 == 0", name);
   if constexpr (MASKED)
-    ALDM_CHECK_ARG(ip.x0 && ip.noise && ip.mask && ip.blend && ip.C > 0 && n_per_sample % ip.C == 0 && (long long)B * n_per_sample < (1ll << 31),
+    ALDM_CHECK_ARG(ip.x0 && (ip.noise || Solver::DRAWS_BLEND_NOISE) && ip.mask && ip.blend && ip.C > 0 && n_per_sample % ip.C == 0 && (long long)B * n_per_sample < (1ll << 31),
                    "%s: bad inpainting args", name);
   if (!table) row_elems = 0;
   const long long total = (long long)B * n_per_sample;
@@ -1116,6 +1226,19 @@ extern "C" int aldm_euler_a_step_fused_masked(const float* eps, float* x, int B,
                                                euler_a_step_fused_masked_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef, step_idx,
                                                x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
                                                Inpaint{x0, noise, mask, blend, channels}, stream, rng_state);
+}
+
+// the RePaint fused step: aldm_euler_a_step_fused_masked's argument list; `noise` is not read (the blend's noise is drawn in the
+// kernel) and may be NULL
+extern "C" int aldm_repaint_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                              const float* coef, int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table,
+                                              long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                              unsigned* ticket, const float* x0, const float* noise, const float* mask, const float* blend,
+                                              int channels, void* stream) {
+  return launch_step_fused<RepaintSolver, true>("repaint_step_fused_masked", repaint_step_fused_masked_kernel<4>,
+                                                repaint_step_fused_masked_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef, step_idx,
+                                                x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket,
+                                                Inpaint{x0, noise, mask, blend, channels}, stream, rng_state);
 }
 
 // the UniPC fused steps: aldm_dpm_step_fused's argument list with the solver state [3][B][n] (UniPCSolver) in the place of the history
@@ -1263,7 +1386,7 @@ static int launch_step_fused_windowed_masked(const char* name, Kernel k4, Kernel
   ALDM_CHECK_ARG(!ticket || (timesteps && t_out), "%s: the counter advance needs timesteps and t_out", name);
   ALDM_CHECK_ARG(!table || (ticket && rowbias && row_elems > 0 && row_elems % 4 == 0),
                  "%s: table needs ticket, rowbias and row_elems %% 4 == 0", name);
-  ALDM_CHECK_ARG(ip.x0 && ip.noise && ip.mask && ip.blend && ip.C > 0 && n_per_sample % ip.C == 0 && (long long)B * n_per_sample < (1ll << 31),
+  ALDM_CHECK_ARG(ip.x0 && (ip.noise || Solver::DRAWS_BLEND_NOISE) && ip.mask && ip.blend && ip.C > 0 && n_per_sample % ip.C == 0 && (long long)B * n_per_sample < (1ll << 31),
                  "%s: bad inpainting args", name);
   long long wc;
   if (const int rc = check_window_plan(name, plan, B, n_per_sample, true, &wc)) return rc;
@@ -1307,6 +1430,17 @@ extern "C" int aldm_euler_a_step_fused_windowed_masked(const float* eps, float* 
                                                        const float* mask, const float* blend, int channels, void* stream) {
   return launch_step_fused_windowed_masked<EulerASolver>("euler_a_step_fused_windowed_masked", euler_a_step_fused_windowed_masked_kernel<4>,
                                                 euler_a_step_fused_windowed_masked_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef,
+                                                step_idx, x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan,
+                                                Inpaint{x0, noise, mask, blend, channels}, stream, rng_state);
+}
+
+extern "C" int aldm_repaint_step_fused_windowed_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                                       const float* coef, int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table,
+                                                       long long row_elems, float* rowbias, const float* timesteps, int n_steps, float* t_out,
+                                                       unsigned* ticket, const aldm_window_plan_t* plan, const float* x0, const float* noise,
+                                                       const float* mask, const float* blend, int channels, void* stream) {
+  return launch_step_fused_windowed_masked<RepaintSolver>("repaint_step_fused_windowed_masked", repaint_step_fused_windowed_masked_kernel<4>,
+                                                repaint_step_fused_windowed_masked_kernel<1>, eps, x, B, n_per_sample, cfg, guidance, coef,
                                                 step_idx, x_in_bf16, table, row_elems, rowbias, timesteps, n_steps, t_out, ticket, plan,
                                                 Inpaint{x0, noise, mask, blend, channels}, stream, rng_state);
 }

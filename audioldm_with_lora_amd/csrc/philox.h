@@ -15,6 +15,14 @@
 //   d + 2  B*C*H*W normals    n, the diffusion noise                           (the same indexing)
 //   d + 3  B*C normals        o, the noise offset's per-(sample, channel) normal
 // Element i of each draw is element i of aldm_philox_u32 / aldm_randn for the same state with the ordinal set to that draw.
+//
+// RePaint-step stream contract (aldm_repaint_step_fused[_windowed]_masked, elementwise.hip).  A step that finds the ordinal at d uses
+// TWO draws and, with a ticket, its last workgroup leaves the ordinal at d + 2 -- always two, on rows without a jump and on the last
+// row too, so streams stay aligned whatever the walk:
+//   d      B*n normals        zk, the noise of the known part a x0 + s zk      (RePaint Algorithm 1, line 4)
+//   d + 1  B*n normals        zj, the noise of the jump back up c1 xb + c2 zj  (line 10; not generated on rows with c2 == 0)
+// Element i of the [B][n] latent -- the LONG latent [B][rows][wc] when windowed -- is element i of each draw, and the bits are
+// aldm_randn's for the same state with the ordinal set to that draw.  With ticket == NULL the counter and the ordinal stay.
 #pragma once
 #include "common.h"
 

@@ -19,6 +19,9 @@ With an EulerAncestralDiscreteScheduler the update is the
 draws its noise inside the launch from a Philox stream whose state {seed, draw ordinal} is one more device buffer: the last workgroup
 moves the ordinal with the step counter, so every replay draws fresh noise.  In sigma space `x` is the unscaled sample and `x_in` holds
 x / sqrt(sigma^2 + 1).
+With a RePaintScheduler a masked engine runs RePaint's folded walk: n_steps is the number of UNet calls L, and
+the step (ops.repaint_step_fused_masked) draws the known part's noise and the jump's noise inside the launch from the same kind of
+Philox state, whose ordinal moves by 2 per step.
 Multi-adapter LoRA: a gated engine's UNet launches read a per-sample gate table from one more device buffer
 (set_adapters): another routing, other weights or no adapter at all is a copy into that buffer -- no repack, no re-capture.
 Long-form generation: WindowedDenoiseEngine keeps ONE long latent [B, rows, W, C] and runs the UNet on K
@@ -30,7 +33,7 @@ inpainting blend on the long latent inside the same launch (ops.*_step_fused_win
 import torch
 
 from . import ops
-from .scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, UniPCMultistepScheduler, _fresh_seed
+from .scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, RePaintScheduler, UniPCMultistepScheduler, _fresh_seed
 
 
 class DenoiseEngine:
@@ -48,7 +51,13 @@ class DenoiseEngine:
         self.dpm = isinstance(scheduler, DPMSolverMultistepScheduler)
         self.euler = isinstance(scheduler, EulerAncestralDiscreteScheduler)
         self.unipc = isinstance(scheduler, UniPCMultistepScheduler)
+        self.repaint = isinstance(scheduler, RePaintScheduler)
         self.begin_index, self.masked = int(begin_index), bool(masked)
+        if self.repaint and not self.masked:
+            raise ValueError("RePaintScheduler needs a mask: RePaint resamples a masked region against the kept one (build the engine "
+                             "with masked=True, or call the audio-to-audio pipeline with mask=...)")
+        if self.repaint and self.begin_index:
+            raise NotImplementedError("begin_index > 0 with a RePaintScheduler: RePaint runs its whole walk (strength 1.0)")
         if not 0 <= self.begin_index < len(scheduler.timesteps):
             raise ValueError(f"begin_index {begin_index} outside the schedule of {len(scheduler.timesteps)} steps")
         # (the defaults keep the full schedule and the scheduler's own table call, launch for launch)
@@ -63,7 +72,7 @@ class DenoiseEngine:
         # default stays a single chain.
         if chains is None:
             chains = 1
-        if chains > 1 and (self.dpm or self.euler or self.unipc):
+        if chains > 1 and (self.dpm or self.euler or self.unipc or self.repaint):
             raise NotImplementedError("chains > 1 runs the DDIM update only")
         if chains > 1 and self.masked:
             raise NotImplementedError("chains > 1 runs the unmasked update only")
@@ -79,7 +88,8 @@ class DenoiseEngine:
         self.state = torch.zeros(3, *self.x.shape, dtype=torch.float32, device=dev) if self.unipc else None
         # Euler-ancestral: the Philox state {seed_lo, seed_hi, draw_lo, draw_hi} of the in-loop noise (set_seed; set_latents puts the
         # draw ordinal back to 0) and the input scale of the first row, which set_latents applies (the later rows' are in the table)
-        self.rng = ops.philox_state(_fresh_seed(), 0, dev) if self.euler else None
+        # RePaint: the same state; every step uses two draws (the known part's noise, the jump's)
+        self.rng = ops.philox_state(_fresh_seed(), 0, dev) if self.euler or self.repaint else None
         self.in_scale0 = float(scheduler.input_scale(self.begin_index)) if self.euler else 1.0
         # masked: the known latents (x0 * scaling_factor), the eps the loop started from (both NHWC fp32), the mask [B, h, w] fp32
         # (1 = regenerate) and the blend rows (a, s) of the suffix [n_steps, 2] -- set_inpaint fills the first three
@@ -89,8 +99,8 @@ class DenoiseEngine:
             self.mask = torch.ones(batch, height, width, dtype=torch.float32, device=dev)
             self.blend = scheduler.blend_table(self.begin_index).contiguous().to(dev)
         # the single-chain step's last launch (ops.{ddim,dpm,unipc,euler_a}_step_fused[_masked]) and what it takes beside the frame's operands
-        self._step = getattr(ops, ("euler_a" if self.euler else "dpm" if self.dpm else "unipc" if self.unipc else "ddim") + "_step_fused" + ("_masked" if self.masked else ""))
-        self._solver_args = (self.rng,) if self.euler else (self.hist,) if self.dpm else (self.state,) if self.unipc else ()
+        self._step = getattr(ops, self._solver_name() + "_step_fused" + ("_masked" if self.masked else ""))
+        self._solver_args = (self.rng,) if self.euler or self.repaint else (self.hist,) if self.dpm else (self.state,) if self.unipc else ()
         self._inpaint_args = (self.x0, self.noise, self.mask, self.blend) if self.masked else ()
         self.t_buf = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -111,6 +121,9 @@ class DenoiseEngine:
         # noticed instead of replaying the old weights -- or freed memory.
         self._plan_ref = None
         self.plan_version = None
+
+    def _solver_name(self):
+        return "euler_a" if self.euler else "dpm" if self.dpm else "unipc" if self.unipc else "repaint" if self.repaint else "ddim"
 
     def stale(self):
         """True when the UNet's packed operands changed after this engine captured its graph."""
@@ -186,10 +199,11 @@ class DenoiseEngine:
         return None if self.gate is None else self.gate[i]
 
     def set_seed(self, seed):
-        """Euler-ancestral engines: the 64-bit seed of the in-loop noise stream, written into the device state (draw ordinal 0), so a
-        captured graph replays with the new stream.  Same seed + same latents = the same bits, replayed or eager."""
-        if not self.euler:
-            raise ValueError("set_seed needs an engine built with an EulerAncestralDiscreteScheduler (the other updates draw no noise)")
+        """Euler-ancestral and RePaint engines: the 64-bit seed of the in-loop noise stream, written into the device state (draw ordinal
+        0), so a captured graph replays with the new stream.  Same seed + same latents = the same bits, replayed or eager."""
+        if self.rng is None:
+            raise ValueError("set_seed needs an engine built with an EulerAncestralDiscreteScheduler or a RePaintScheduler (the other "
+                             "updates draw no noise)")
         self.rng.copy_(ops.philox_state(seed, 0, self.dev))
 
     def set_latents(self, latents_nchw):
@@ -328,8 +342,7 @@ class WindowedDenoiseEngine(DenoiseEngine):
         self.bc = batch * self.K                                  # rows per CFG half of everything the UNet sees
         self.x_in = [torch.zeros((2 if self.cfg else 1) * self.bc, self.hw, width, self.C, dtype=torch.bfloat16, device=self.dev)]
         self._win = plan.device(self.dev)                         # offset / cover / weight tables (the plan keeps them alive)
-        solver = "euler_a" if self.euler else "dpm" if self.dpm else "unipc" if self.unipc else "ddim"
-        self._step = getattr(ops, solver + "_step_fused_windowed" + ("_masked" if self.masked else ""))
+        self._step = getattr(ops, self._solver_name() + "_step_fused_windowed" + ("_masked" if self.masked else ""))
 
     def _per_window(self, entries, what):
         """one entry per clip, or one per (clip, window) in that order -> one per (clip, window)"""

@@ -1237,21 +1237,24 @@ def cfg_ddim_step(eps, x, cfg, guidance, coef, step_idx, x_in):
                                                           _stream())), "aldm_cfg_ddim_step")
 
 
-def _inpaint_args(x, x0, noise, mask, blend, n_steps):
-    """checks the masked steps' extra operands; returns the channel count (x is channels-last [B, h, w, C])"""
+def _inpaint_args(x, x0, noise, mask, blend, n_steps, noise_optional=False):
+    """checks the masked steps' extra operands; returns the channel count (x is channels-last [B, h, w, C]).  noise_optional: the
+    solver draws the blend's noise itself (RePaint), so `noise` may be None"""
     C = x.shape[-1]
-    for t in (x0, noise, mask, blend):
+    assert noise is not None or noise_optional, "noise: the eps the loop started from"
+    for t in (x0, mask, blend) + (() if noise is None else (noise,)):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device
-    assert x0.numel() == x.numel() and noise.numel() == x.numel() and mask.numel() * C == x.numel(), "x0 / noise / mask geometry"
+    assert x0.numel() == x.numel() and (noise is None or noise.numel() == x.numel()) and mask.numel() * C == x.numel(), "x0 / noise / mask geometry"
     assert blend.dim() == 2 and blend.shape == (n_steps, 2), "blend rows [n_steps, 2]"
     return C
 
 
 # solver -> (columns of its coefficient table, flops per element, bytes per element beside the frame's, ticket may be None)
 #   dpm: hist read/write (upper bound: second-order rows); euler_a: ~100 flops for ten Philox rounds and a Box-Muller, no noise tensor;
-#   unipc: last, m0, m1 read and last, m_t written (upper bound: second-order corrector rows)
+#   unipc: last, m0, m1 read and last, m_t written (upper bound: second-order corrector rows); repaint (masked only): two Philox
+#   blocks and Box-Mullers on rows with a jump, one on the others (upper bound), and the blend's noise is not read (-4 B)
 _STEP_SOLVERS = {"ddim": (4, 6.0, 0.0, False), "dpm": (8, 10.0, 8.0, True), "euler_a": (4, 110.0, 0.0, True),
-                 "unipc": (16, 22.0, 20.0, True)}
+                 "unipc": (16, 22.0, 20.0, True), "repaint": (8, 212.0, -4.0, True)}
 
 
 def _step_fused(solver, eps, x, cfg, guidance, coef, step_idx, x_in, operand, table, rowbias, timesteps_f32, t_out, ticket, inpaint=None):
@@ -1273,7 +1276,7 @@ def _step_fused(solver, eps, x, cfg, guidance, coef, step_idx, x_in, operand, ta
     per_elem = 4.0 * halves + 8.0 + solver_bytes
     tail = ()
     if inpaint is not None:
-        C = _inpaint_args(x, *inpaint, n_steps)
+        C = _inpaint_args(x, *inpaint, n_steps, noise_optional=solver == "repaint")
         name, flops = name + "_masked", flops + 4.0
         per_elem = per_elem + 8.0 + 4.0 / C                  # x0 and noise (4 B each) and the mask (4 B per pixel)
         tail = (*map(_p, inpaint), C)
@@ -1411,6 +1414,18 @@ def euler_a_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, rng_s
                 (x0, noise, mask, blend))
 
 
+def repaint_step_fused_masked(eps, x, cfg, guidance, coef, step_idx, x_in, rng_state, table, rowbias, timesteps_f32, t_out, ticket, x0, noise,
+                              mask, blend):
+    """CFG + one RePaint step as one launch (aldm_repaint_step_fused_masked): the DDIM update, the inpainting
+    blend whose known part is noised with FRESH noise zk, and the closed-form jump x' = c1 xb + c2 zj.  coef fp32 [n_steps, 8]
+    (RePaintScheduler.coefficient_table), blend fp32 [n_steps, 2] (RePaintScheduler.blend_table).  With the ordinal of rng_state at
+    d, zk is draw d and zj draw d + 1 (the bits of ops.randn); with a ticket the ordinal ends at d + 2, on every row.  `noise` is not
+    read and may be None.  mask: 1 = regenerate.  ticket None: the counter and the ordinal stay (table must be None then)."""
+    _check_state(rng_state)
+    _step_fused("repaint", eps, x, cfg, guidance, coef, step_idx, x_in, (rng_state,), table, rowbias, timesteps_f32, t_out, ticket,
+                (x0, noise, mask, blend))
+
+
 # ---- windowed denoising: long-form and loopable generation (csrc/elementwise.hip, longform.py, DESIGN.md section 18) ------------
 def _window_plan(plan):
     """aldm_window_plan_t of a plan's device tables (longform.WindowPlan.device(): offset int32 [K], cover int32 [rows, KC], weight
@@ -1483,7 +1498,7 @@ def _step_fused_windowed(solver, eps, x, cfg, guidance, coef, step_idx, x_in, op
     tail = ()
     if inpaint is not None:
         assert x.dim() >= 2, "x: channels-last [B, rows, W, C]"
-        ch = _inpaint_args(x, *inpaint, n_steps)
+        ch = _inpaint_args(x, *inpaint, n_steps, noise_optional=solver == "repaint")
         name, flops = name + "_masked", flops + 4.0
         long_bytes = long_bytes + 8.0 + 4.0 / ch             # the three extra long reads: x0 and noise (4 B each), the mask (4 B per pixel)
         tail = (*map(_p, inpaint), ch)
@@ -1548,6 +1563,15 @@ def euler_a_step_fused_windowed_masked(eps, x, cfg, guidance, coef, step_idx, x_
     """euler_a_step_fused_windowed with the inpainting blend (aldm_euler_a_step_fused_windowed_masked); blend rows (1, sigma_next)."""
     _check_state(rng_state)
     _step_fused_windowed("euler_a", eps, x, cfg, guidance, coef, step_idx, x_in, (rng_state,), table, rowbias, timesteps_f32, t_out, ticket, plan,
+                         (x0, noise, mask, blend))
+
+
+def repaint_step_fused_windowed_masked(eps, x, cfg, guidance, coef, step_idx, x_in, rng_state, table, rowbias, timesteps_f32, t_out, ticket, plan,
+                                       x0, noise, mask, blend):
+    """repaint_step_fused_masked on a long latent (aldm_repaint_step_fused_windowed_masked): element i of the LONG latent is element i
+    of both draws; `noise` may be None."""
+    _check_state(rng_state)
+    _step_fused_windowed("repaint", eps, x, cfg, guidance, coef, step_idx, x_in, (rng_state,), table, rowbias, timesteps_f32, t_out, ticket, plan,
                          (x0, noise, mask, blend))
 
 

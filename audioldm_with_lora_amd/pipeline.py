@@ -262,11 +262,11 @@ class AudioLDMPipeline:
 
     @staticmethod
     def _seed_engine(eng, generator):
-        """Stochastic samplers (EulerAncestralDiscreteScheduler) draw their per-step noise on the device, inside the replayed graph, from
+        """Stochastic samplers (EulerAncestralDiscreteScheduler, RePaintScheduler) draw their per-step noise on the device, inside the replayed graph, from
         a Philox stream of this library's own.  Its seed is `generator.initial_seed()` when a generator is passed -- only that number is
         read, the generator's stream is neither used nor advanced by the loop -- else a fresh one from torch's global CPU generator (new
         on every call, reproducible after torch.manual_seed).  Deterministic samplers draw nothing: no-op."""
-        if eng.euler:
+        if eng.euler or eng.repaint:
             eng.set_seed(generator.initial_seed() if generator is not None else _fresh_seed())
 
     def decode_latents_nhwc(self, x_nhwc_f32):

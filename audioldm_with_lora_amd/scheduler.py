@@ -1,4 +1,4 @@
-"""DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler and EulerAncestralDiscreteScheduler for the HIP path (host-side integer logic + device step kernels).
+"""DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler, EulerAncestralDiscreteScheduler and RePaintScheduler for the HIP path (host-side integer logic + device step kernels).
 
 Same surface the reference touches: `from_pretrained(id, subfolder="scheduler")`, `.config.num_train_timesteps`,
 `.add_noise` [REF script/train/train_audioldm_lora.py:367,503-504] and, through the pipeline,
@@ -11,6 +11,8 @@ UniPCMultistepScheduler is diffusers 0.32.2's multistep predictor-corrector (DES
 sampler for 5-10 steps.
 EulerAncestralDiscreteScheduler is diffusers 0.32.2's stochastic sampler, swapped in the same way; its per-step
 noise is drawn on the device by the step kernel itself (a Philox stream, ops.philox_state).
+RePaintScheduler is RePaint's resampling loop for inpainting, swapped in the same way on the audio-to-audio
+pipeline; its two noises per step come from the same kind of stream.
 """
 import json
 import os
@@ -825,3 +827,238 @@ class EulerAncestralDiscreteScheduler(_SuffixMixin):
             raise ValueError(f"add_noise: {len(idx)} timesteps for a batch of {B}")
         coef = torch.stack([torch.stack(self.add_noise_coefficients(i)) for i in idx]).float().contiguous()
         return ops.add_noise(original_samples, noise, coef.to(original_samples.device))
+
+
+# diffusers 0.32.2 RePaintScheduler's own keys (jump_length and jump_n_sample are arguments of its set_timesteps; here they are
+# configuration, so that a pipeline's engine cache is keyed by them); the keys shared with DDIMScheduler default to the AudioLDM
+# scheduler configuration, as the other classes' do here
+REPAINT_CONFIG = dict(SCHEDULER, trained_betas=None, jump_length=10, jump_n_sample=10, eta=0.0)
+
+
+class RePaintScheduler(_SuffixMixin):
+    """RePaint resampling for inpainting (Lugmayr et al., CVPR 2022, Algorithm 1; diffusers 0.32.2 RePaintScheduler / RePaintPipeline)
+    on DDIMScheduler's grid, eta = 0.
+
+    THE MASK MEANS 1 = REGENERATE, 0 = KEEP, as everywhere in this library.  diffusers' RePaint uses the opposite (1 = keep).
+
+    set_timesteps(N) builds diffusers' walk over the grid levels N - 1 .. 0: it falls one level per UNet call and, `jump_n_sample - 1`
+    times at every level that is a multiple of `jump_length` below N - jump_length, climbs `jump_length` levels back up.  Level l is
+    DDIM's timestep l * (T // N) + steps_offset.  The walk is FOLDED: every falling (or first) entry is one UNet call, and the run of J
+    rising entries behind it is that call's jump.  `timesteps` lists the UNet calls; `coefficient_table()` has one fp32 row
+        {sa, sb, sap, sbp, c1, c2, 0, 0}
+    per call: DDIMScheduler.step_coefficients of its timestep, then the jump over J levels from level l - 1, where the step lands, as
+    ONE Gaussian:  r = abar(l - 1 + J) / abar(l - 1),  c1 = sqrt(r),  c2 = sqrt(1 - r)  (abar(-1) = final_alpha_cumprod; exactly (1, 0)
+    where J == 0).  diffusers applies J * (T // N) single-beta `undo_step`s, each with noise of its own; their composition is one
+    Gaussian too, so no launch without a UNet call is needed.  The device step (aldm_repaint_step_fused_masked) is then
+        xu = DDIM's update ;  xb = (1 - m) (a x0 + s zk) + m xu ;  x' = c1 xb + c2 zj
+    with (a, s) the row of blend_table() and zk, zj two FRESH normals per element from a Philox stream in device memory (draws d and
+    d + 1; the ordinal moves by 2 per step).  The noise stream is this library's own: a seed reproduces this library's samples."""
+
+    def __init__(self, **over):
+        cfg = dict(REPAINT_CONFIG)
+        cfg.update({k: v for k, v in over.items() if k in REPAINT_CONFIG})
+        self.config = SimpleNamespace(**cfg)
+        self._check(cfg)
+        n = cfg["num_train_timesteps"]
+        self.betas = torch.linspace(cfg["beta_start"] ** 0.5, cfg["beta_end"] ** 0.5, n, dtype=torch.float32) ** 2
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.final_alpha_cumprod = torch.tensor(1.0) if cfg["set_alpha_to_one"] else self.alphas_cumprod[0]
+        self.init_noise_sigma = 1.0
+        self.num_inference_steps = None
+        self.walk, self.folded = [], []
+        self.timesteps = torch.from_numpy(np.arange(0, n)[::-1].copy().astype(np.int64))
+        self._rng = {}
+        self._dev = {}
+
+    @staticmethod
+    def _check(cfg):
+        if cfg["eta"] != 0:
+            raise NotImplementedError(f"eta={cfg['eta']}: only the deterministic reverse step (eta = 0) is implemented")
+        if cfg["clip_sample"]:
+            raise NotImplementedError("clip_sample=True")
+        if cfg["prediction_type"] != "epsilon":
+            raise NotImplementedError(f"prediction_type={cfg['prediction_type']!r}: only epsilon prediction is implemented")
+        if cfg["beta_schedule"] != "scaled_linear" or cfg["trained_betas"] is not None:
+            raise NotImplementedError(f"beta_schedule={cfg['beta_schedule']!r} / trained_betas: only scaled_linear is implemented")
+        if cfg["timestep_spacing"] != "leading":
+            raise NotImplementedError(f"timestep_spacing={cfg['timestep_spacing']!r}: only DDIMScheduler's leading grid is implemented")
+        RePaintScheduler._check_jumps(cfg["jump_length"], cfg["jump_n_sample"])
+
+    @staticmethod
+    def _check_jumps(jump_length, jump_n_sample):
+        if int(jump_length) != jump_length or jump_length < 1:
+            raise ValueError(f"jump_length must be an integer >= 1, got {jump_length}")
+        if int(jump_n_sample) != jump_n_sample or jump_n_sample < 1:
+            raise ValueError(f"jump_n_sample must be an integer >= 1, got {jump_n_sample}")
+
+    @classmethod
+    def from_pretrained(cls, path, subfolder=None, **kw):
+        return cls(**_read_config(path, subfolder))
+
+    @classmethod
+    def from_config(cls, config, **over):
+        """dict or SimpleNamespace (e.g. DDIMScheduler's `.config`), then overrides such as jump_length=5, jump_n_sample=3; keys this
+        class does not know (solver_order, ...) are ignored."""
+        return cls(**_config_dict(config, over))
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    @staticmethod
+    def walk_levels(N, jump_length, jump_n_sample):
+        """diffusers' RePaintScheduler.set_timesteps list, in grid levels"""
+        jumps = {j: jump_n_sample - 1 for j in range(0, N - jump_length, jump_length)}
+        walk, t = [], N
+        while t >= 1:
+            t -= 1
+            walk.append(t)
+            if jumps.get(t, 0) > 0:
+                jumps[t] -= 1
+                for _ in range(jump_length):
+                    t += 1
+                    walk.append(t)
+        return walk
+
+    @staticmethod
+    def fold(walk):
+        """[(level, J)]: the falling (or first) entries of a walk, each with the number of rising entries behind it"""
+        folded = []
+        for i, l in enumerate(walk):
+            if i == 0 or l < walk[i - 1]:
+                folded.append([l, 0])
+            else:
+                folded[-1][1] += 1
+        return [tuple(f) for f in folded]
+
+    def set_timesteps(self, num_inference_steps, jump_length=None, jump_n_sample=None, device=None):
+        """jump_length / jump_n_sample None: the configuration's.  timesteps: int64, one per UNet call."""
+        n, N = self.config.num_train_timesteps, int(num_inference_steps)
+        if not 0 < N <= n:
+            raise ValueError("need 0 < num_inference_steps <= num_train_timesteps")
+        jl = self.config.jump_length if jump_length is None else jump_length
+        js = self.config.jump_n_sample if jump_n_sample is None else jump_n_sample
+        self._check_jumps(jl, js)
+        self.num_inference_steps = N
+        self.walk = self.walk_levels(N, int(jl), int(js))
+        self.folded = self.fold(self.walk)
+        ts = np.array([l for l, _ in self.folded], dtype=np.int64) * (n // N) + self.config.steps_offset
+        self.timesteps = torch.from_numpy(ts)
+        if device is not None:
+            self.timesteps = self.timesteps.to(device)
+        self._rng = {}
+
+    def _need_schedule(self):
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() first")
+
+    def get_timesteps(self, num_inference_steps, strength):
+        if float(strength) != 1.0:
+            raise ValueError(f"strength {strength}: RePaint regenerates the masked region from noise, only strength 1.0 is accepted")
+        self.set_timesteps(num_inference_steps)
+        return self.timesteps, 0
+
+    def prev_timestep(self, t):
+        return int(t) - self.config.num_train_timesteps // self.num_inference_steps
+
+    def _abar(self, t):
+        """fp32 alpha-bar at timestep t; final_alpha_cumprod below the grid (the level -1 a step from level 0 lands on)"""
+        return self.alphas_cumprod[int(t)] if t >= 0 else self.final_alpha_cumprod
+
+    def _level_timestep(self, level):
+        return level * (self.config.num_train_timesteps // self.num_inference_steps) + self.config.steps_offset if level >= 0 else -1
+
+    def step_coefficients(self, t):
+        """DDIMScheduler.step_coefficients, the same fp32 ops"""
+        a_t, a_p = self.alphas_cumprod[int(t)], self._abar(self.prev_timestep(t))
+        return torch.stack([a_t ** 0.5, (1 - a_t) ** 0.5, a_p ** 0.5, (1 - a_p) ** 0.5]).float()
+
+    def jump_coefficients(self, t_from, t_to):
+        """fp32 (c1, c2) of the forward jump from timestep t_from up to t_to as one Gaussian: r = abar(t_to) / abar(t_from) in float64
+        on the fp32 table (1 - r cancels in fp32), rounded once"""
+        r = self._abar(t_to).double() / self._abar(t_from).double()
+        return torch.stack([r ** 0.5, (1 - r) ** 0.5]).float()
+
+    def coefficient_table(self, begin_index=0):
+        self._need_schedule()
+        if begin_index:
+            raise NotImplementedError("begin_index > 0: RePaint runs its whole walk (strength 1.0)")
+        rows = []
+        for l, J in self.folded:
+            jump = self.jump_coefficients(self._level_timestep(l - 1), self._level_timestep(l - 1 + J)) if J else torch.tensor([1.0, 0.0])
+            rows.append(torch.cat([self.step_coefficients(self._level_timestep(l)), jump, torch.zeros(2)]))
+        return torch.stack(rows).float().contiguous()
+
+    def blend_table(self, begin_index=0):
+        """fp32 [L, 2]: row k noises the known latents to the level call k's step lands on, (sqrt(abar), sqrt(1 - abar)) of level
+        l_k - 1 (before the jump; final_alpha_cumprod at level -1); the last row is exactly (1, 0)"""
+        self._need_schedule()
+        if begin_index:
+            raise NotImplementedError("begin_index > 0: RePaint runs its whole walk (strength 1.0)")
+        rows = []
+        for l, _ in self.folded[:-1]:
+            a = self._abar(self._level_timestep(l - 1))
+            rows.append(torch.stack([a ** 0.5, (1 - a) ** 0.5]))
+        rows.append(torch.tensor([1.0, 0.0], dtype=torch.float32))
+        return torch.stack(rows).float().contiguous()
+
+    def add_noise_coefficients(self, i):
+        """fp32 (sqrt(abar[t_i]), sqrt(1 - abar[t_i])) of UNet call i of the folded list"""
+        a = self.alphas_cumprod[int(self.timesteps[i])]
+        return a ** 0.5, (1 - a) ** 0.5
+
+    def add_noise(self, original_samples, noise, timesteps):
+        dev = original_samples.device
+        ac = self._dev.get(("ac", dev))
+        if ac is None:
+            ac = self._dev[("ac", dev)] = self.alphas_cumprod.to(dev, torch.float32).contiguous()
+        return ops.add_noise_t(original_samples, noise, ac, timesteps.to(dev, torch.int64).reshape(-1))
+
+    _state_for = EulerAncestralDiscreteScheduler._state_for
+
+    def _scratch(self, dev):
+        """the one-row schedule an eager launch runs on: counter, ticket, its timestep list and t_out"""
+        s = self._dev.get(("scratch", dev))
+        if s is None:
+            s = self._dev[("scratch", dev)] = (torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
+                                               torch.zeros(1, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev))
+        return s
+
+    def step(self, model_output, timestep, sample, original_image, mask, generator=None, return_dict=True, **kw):
+        """One row WITHOUT a jump through the device kernel (aldm_repaint_step_fused_masked, eager): the DDIM update from `timestep`,
+        then the known part a x0 + s zk (a, s of the timestep the update lands on; final_alpha_cumprod below the grid) where the mask
+        keeps it.  mask: 1 = REGENERATE, 0 = keep (the opposite of diffusers' RePaintScheduler.step), anything that broadcasts to the
+        sample; fp32 tensors of any layout.  zk is drawn inside the kernel from the Philox stream `generator` names -- an int seed, a
+        torch.Generator (only its initial_seed() is read) or an ops.philox_state -- whose draw ordinal grows by 2."""
+        self._need_schedule()
+        dev = sample.device
+        x = sample.detach().float().contiguous().clone()
+        ops._require_gpu(x)
+        B = x.shape[0]
+        a = self._abar(self.prev_timestep(timestep))
+        coef = torch.cat([self.step_coefficients(timestep), torch.tensor([1.0, 0.0, 0.0, 0.0])]).view(1, 8).to(dev)
+        blend = torch.stack([a ** 0.5, (1 - a) ** 0.5]).float().view(1, 2).to(dev)
+        m = torch.as_tensor(mask).to(dev, torch.float32).expand_as(x).reshape(B, -1).contiguous()
+        x0 = original_image.detach().to(dev, torch.float32).expand_as(x).reshape(B, -1, 1).contiguous()
+        idx, ticket, t1, t_out = self._scratch(dev)
+        # (every element its own pixel: one channel, so the mask may vary along any axis of the sample's layout)
+        ops.repaint_step_fused_masked(model_output.detach().float().contiguous(), x.view(B, -1, 1), False, 0.0, coef, idx, None,
+                                      self._state_for(generator, dev), None, None, t1, t_out, ticket, x0, None, m, blend)
+        prev = x.to(sample.dtype)
+        if not return_dict:
+            return (prev,)
+        return SimpleNamespace(prev_sample=prev)
+
+    def undo_step(self, sample, timestep, generator=None):
+        """The closed-form jump up ONE grid level, from `timestep` to timestep + T // N: sqrt(r) x + sqrt(1 - r) z with
+        r = abar(timestep + T // N) / abar(timestep); diffusers' undo_step composes T // N single-beta steps instead.  z is one draw
+        of the Philox stream `generator` names (as in step), generated and applied on the device."""
+        self._need_schedule()
+        dev = sample.device
+        up = int(timestep) + self.config.num_train_timesteps // self.num_inference_steps
+        if up >= self.config.num_train_timesteps:
+            raise ValueError(f"undo_step: timestep {int(timestep)} has no grid level above it")
+        x = sample.detach().float().contiguous()
+        z = ops.randn(tuple(x.shape), self._state_for(generator, dev), advance=True)
+        coef = self.jump_coefficients(int(timestep), up).view(1, 2).expand(x.shape[0], 2).contiguous().to(dev)
+        return ops.add_noise(x, z, coef).to(sample.dtype)

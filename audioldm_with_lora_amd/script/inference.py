@@ -23,6 +23,9 @@ on itself (the length is rounded up to a whole number of window strides); `--win
 `--init-audio in.wav --window-seconds 10.24` restyles or inpaints a recording of any length the same way (`--strength`,
 `--regenerate-seconds`, `--regenerate-bands`, `--loop` and `--window-prompts` apply); `--extend-to-seconds T` keeps the recording and
 generates what follows it up to T seconds.
+`--repaint JUMP_LENGTH,JUMP_N_SAMPLE` (with --init-audio and a --regenerate-* or --extend-to-seconds mask, with or without
+--window-seconds) inpaints with RePaint's resampling loop (RePaintScheduler) instead of the legacy blend: more UNet calls, and a
+regenerated region that agrees better with what is kept; it runs from noise (--strength 1.0).
 """
 import argparse
 import os
@@ -33,7 +36,7 @@ import torch
 from ..lora import LoraConfig, get_peft_model
 from ..audio2audio import AudioLDMAudioToAudioPipeline, continuation_mask, regeneration_mask
 from ..pipeline import AudioLDMPipeline
-from ..scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, UniPCMultistepScheduler
+from ..scheduler import DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, RePaintScheduler, UniPCMultistepScheduler
 from ..unet import UNet2DConditionModel
 
 
@@ -94,7 +97,11 @@ def parse_args(argv=None):
                          "nothing, quirk Q5)")
     ap.add_argument("--init-audio", default=None, help="wav to start from (audio-to-audio), any rate: resampled to the model's on the device; read with scipy")
     ap.add_argument("--output-sampling-rate", type=int, default=None, metavar="R", help="write the wav files at R Hz (default: the model's 16000)")
-    ap.add_argument("--strength", type=float, default=0.5, help="with --init-audio: how much of the schedule to run (1 = from noise)")
+    ap.add_argument("--strength", type=float, default=None,
+                    help="with --init-audio: how much of the schedule to run (1 = from noise; default 0.5, with --repaint 1.0)")
+    ap.add_argument("--repaint", default=None, metavar="JUMP_LENGTH,JUMP_N_SAMPLE",
+                    help="with --init-audio and a --regenerate-* / --extend-to-seconds mask: RePaint resampling (RePaintScheduler on the "
+                         "DDIM grid of --steps levels) instead of the legacy inpaint blend")
     ap.add_argument("--regenerate-seconds", default=None, help="with --init-audio: T0,T1 -- regenerate only this time span")
     ap.add_argument("--regenerate-bands", default=None, help="with --init-audio: F0,F1 -- regenerate only this fraction of the mel bins")
     ap.add_argument("--extend-to-seconds", type=float, default=None, metavar="T",
@@ -119,6 +126,24 @@ def parse_args(argv=None):
             ap.error("--extend-to-seconds builds its own mask (no --regenerate-seconds / --regenerate-bands)")
         if args.extend_to_seconds <= 0:
             ap.error("--extend-to-seconds expects a positive number of seconds")
+    if args.repaint is not None:
+        try:
+            args.repaint = tuple(int(v) for v in args.repaint.split(","))
+        except ValueError:
+            args.repaint = ()
+        if len(args.repaint) != 2 or min(args.repaint) < 1:
+            ap.error("--repaint expects JUMP_LENGTH,JUMP_N_SAMPLE: two integers >= 1")
+        if args.init_audio is None or not (args.regenerate_seconds or args.regenerate_bands or args.extend_to_seconds is not None):
+            ap.error("--repaint needs --init-audio and a mask (--regenerate-seconds / --regenerate-bands / --extend-to-seconds)")
+        if args.scheduler != "ddim":
+            ap.error("--repaint brings its own sampler (RePaintScheduler on the DDIM grid): no --scheduler with it")
+        if args.adapters is not None and args.window_seconds is None:
+            ap.error("--repaint with --adapters needs --window-seconds (routed calls start from a recording only when windowed)")
+        if args.strength not in (None, 1.0):
+            ap.error("--repaint regenerates from noise: --strength must be 1.0 with it")
+        args.strength = 1.0
+    if args.strength is None:
+        args.strength = 0.5
     for item in args.lora:
         name, sep, path = item.partition("=")
         if not sep or not name or not path:
@@ -219,6 +244,8 @@ def _audio_to_audio(pipe, args, generator, windowed=None, **routed):
     an --adapters call (one clip per routing entry, all from the same recording), and output_sampling_rate="""
     sr, wav = read_wav(args.init_audio)
     a2a = AudioLDMAudioToAudioPipeline.from_pipe(pipe)
+    if args.repaint is not None:
+        a2a.scheduler = RePaintScheduler.from_config(pipe.scheduler.config, jump_length=args.repaint[0], jump_n_sample=args.repaint[1])
     model_rate = int(a2a.vocoder.config.sampling_rate)
     if sr != model_rate:
         print(f"Resampling {args.init_audio}: {sr} Hz -> {model_rate} Hz")

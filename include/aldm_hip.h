@@ -467,6 +467,20 @@ int aldm_euler_a_step_fused_masked(const float* eps, float* x, int B, long long 
                                    int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table, long long row_elems,
                                    float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0,
                                    const float* noise, const float* mask, const float* blend, int channels, void* stream);
+/* classifier-free guidance + one RePaint step (Lugmayr et al., CVPR 2022, Algorithm 1; the mask means 1 = regenerate, the opposite of
+   diffusers' RePaintScheduler): the DDIM update (eta = 0), the inpainting blend with FRESH noise for the known part, and the
+   closed-form jump back up the schedule, elementwise over channels-last fp32 latents:
+     xu = aldm_ddim_step_fused's x' ;  known = a x0 + s zk ;  xb = (1 - m) known + m xu ;  x' = c1 xb + c2 zj ;  x_in = bf16(x')
+   coef: device fp32 table [n_steps][8] = {sa, sb, sap, sbp, c1, c2, 0, 0}, blend fp32 [n_steps][2] rows (a, s), both selected ON
+   DEVICE by step_idx[0]; (c1, c2) == (1, 0) on rows without a jump, where x' = xb bit for bit.  zk and zj are generated in the
+   kernel: with the draw ordinal of rng_state at d, zk is element i of draw d and zj element i of draw d + 1 (i the element's index
+   in [B][n]; bit for bit what aldm_randn gives for the same state).  `noise` is not read and may be NULL.  Counter, next
+   time-embedding row and ticket as in aldm_ddim_step_fused; the last workgroup also leaves the draw ordinal at d + 2, on every row.
+   ticket == NULL leaves step_idx and rng_state alone (table NULL, timesteps/t_out unused).  There is no unmasked form. */
+int aldm_repaint_step_fused_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance, const float* coef,
+                                   int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table, long long row_elems,
+                                   float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket, const float* x0,
+                                   const float* noise, const float* mask, const float* blend, int channels, void* stream);
 /* classifier-free guidance + UniPC multistep predictor-corrector update (orders 1 and 2, bh1 / bh2), the loop body of
    AudioLDMPipeline.__call__ [REF script/inference/generate_audio.py:47-52] with diffusers' UniPCMultistepScheduler swapped in:
      e = cfg ? eu + g (et - eu) : eu ;  m_t = convert ? (x - sig_s e) / alpha_s : e
@@ -549,6 +563,12 @@ int aldm_dpm_step_fused_windowed_masked(const float* eps, float* x, int B, long 
                                         const aldm_window_plan_t* plan, const float* x0, const float* noise, const float* mask,
                                         const float* blend, int channels, void* stream);
 int aldm_euler_a_step_fused_windowed_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
+                                            const float* coef, int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table, long long row_elems,
+                                            float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket,
+                                            const aldm_window_plan_t* plan, const float* x0, const float* noise, const float* mask,
+                                            const float* blend, int channels, void* stream);
+/* aldm_repaint_step_fused_masked on a long latent: element i of the LONG latent is element i of both draws */
+int aldm_repaint_step_fused_windowed_masked(const float* eps, float* x, int B, long long n_per_sample, int cfg, float guidance,
                                             const float* coef, int* step_idx, void* x_in_bf16, unsigned* rng_state, const float* table, long long row_elems,
                                             float* rowbias, const float* timesteps, int n_steps, float* t_out, unsigned* ticket,
                                             const aldm_window_plan_t* plan, const float* x0, const float* noise, const float* mask,

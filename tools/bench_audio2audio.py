@@ -7,6 +7,13 @@ decode (VAE decode + vocoder).
 
 ms_per_step: a begun (strength 0.5) engine after one set_latents, `run()` timed with device synchronisation around the host clock,
 median of `repeats`, divided by the suffix length.  masked and unmasked engines run the same suffix.  Prints one JSON line.
+
+    python tools/bench_audio2audio.py --repaint [--repeats 5] [--steps 50]
+
+measures RePaint instead and prints one JSON line of its own: the in-graph time of the masked fused-step launch
+alone for DDIM, Euler-ancestral and RePaint on the same eps (a graph of 200 launches walking each solver's own table, device events
+around 20 replays, median of `repeats`, the three solvers alternating), and one inpainting call (3 s of 10 s regenerated, strength 1.0)
+at `steps` grid levels with RePaintScheduler(jump_length=5, jump_n_sample=3) against the same call on DDIM.
 """
 import argparse
 import json
@@ -33,11 +40,99 @@ def timed(fn, repeats):
     return out[len(out) // 2]
 
 
+def repaint_numbers(args):
+    from audioldm_with_lora_amd import ops
+    from audioldm_with_lora_amd.audio2audio import AudioLDMAudioToAudioPipeline, reduce_mask, regeneration_mask
+    from audioldm_with_lora_amd.pipeline import AudioLDMPipeline
+    from audioldm_with_lora_amd.scheduler import DDIMScheduler, EulerAncestralDiscreteScheduler, RePaintScheduler
+    from audioldm_with_lora_amd.vae import AutoencoderKL
+    from audioldm_with_lora_amd.vocoder import SpeechT5HifiGan
+    batch, seconds, guidance, N = 4, 10.0, 2.5, args.steps
+    height = int(seconds * 100)
+    h, w = height // 4, 16
+    g = torch.Generator().manual_seed(5)
+    mask = reduce_mask(regeneration_mask(height, 64, seconds=(3.0, 6.0))[None].expand(batch, -1, -1), 4)
+
+    # ---- the masked launch alone, inside a graph ----
+    dims = (batch, h, w, 8)
+    eps = torch.randn((2 * batch,) + dims[1:], generator=g).cuda()
+    x0, nz, md = torch.randn(dims, generator=g).cuda(), torch.randn(dims, generator=g).cuda(), mask.cuda()
+    scheds = {"ddim": DDIMScheduler(), "euler_a": EulerAncestralDiscreteScheduler.from_config(DDIMScheduler().config),
+              "repaint": RePaintScheduler.from_config(DDIMScheduler().config, jump_length=5, jump_n_sample=3)}
+    tables = {}
+    for name, sch in scheds.items():
+        sch.set_timesteps(N)
+        tables[name] = (name, sch.coefficient_table().cuda(), sch.blend_table(0).cuda(), sch.timesteps.float().cuda())
+    name, coef, blend, ts = tables["repaint"]
+    jump = coef[coef[:, 5] > 0][:1].expand(len(coef), 8).contiguous()       # every row the first jump row: the launch's upper end
+    tables["repaint_every_row_jumps"] = (name, jump, blend, ts)
+    LAUNCHES, REPLAYS = 200, 20
+    graphs = {}
+    for key, (name, coef, blend, ts) in tables.items():
+        x = torch.randn(dims, generator=g).cuda()
+        buf = dict(x=x, x_in=torch.zeros((2 * batch,) + dims[1:], dtype=torch.bfloat16, device="cuda"), idx=torch.zeros(1, dtype=torch.int32, device="cuda"),
+                   t=torch.zeros(1, device="cuda"), ticket=torch.zeros(1, dtype=torch.int32, device="cuda"))
+        operand = () if name == "ddim" else (ops.philox_state(1, 0),)
+        fn = getattr(ops, name + "_step_fused_masked")
+
+        def launch(buf=buf, coef=coef, blend=blend, ts=ts, operand=operand, fn=fn):
+            fn(eps, buf["x"], True, guidance, coef, buf["idx"], buf["x_in"], *operand, None, None, ts, buf["t"], buf["ticket"], x0, nz, md, blend)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            launch()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            for _ in range(LAUNCHES):
+                launch()
+        graphs[key] = (graph, buf)
+    times = {key: [] for key in graphs}
+    for rep_i in range(args.repeats + 1):
+        for key, (graph, buf) in graphs.items():
+            buf["x"].normal_()                                       # (the values do not change the work; keeps them finite)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(REPLAYS):
+                graph.replay()
+            b.record()
+            torch.cuda.synchronize()
+            if rep_i:                                                # the first round warms up
+                times[key].append(a.elapsed_time(b) * 1e3 / (REPLAYS * LAUNCHES))
+    launch_us = {key: round(sorted(v)[len(v) // 2], 3) for key, v in times.items()}
+
+    # ---- one inpainting call ----
+    unet, _ = build_unet(4)
+    torch.manual_seed(99)
+    base = AudioLDMPipeline(AutoencoderKL(), None, None, unet, DDIMScheduler(), SpeechT5HifiGan())
+    base.device = torch.device("cuda")
+    base.vae.cuda(); base.vocoder.cuda()
+    pipe = AudioLDMAudioToAudioPipeline.from_pipe(base)
+    _, pe, ne = synth_inputs(batch, h, w)
+    audio = 0.1 * torch.randn(batch, int(seconds * 16000), generator=g)
+    call = dict(prompt_embeds=pe, negative_prompt_embeds=ne, audio=audio, strength=1.0, mask=regeneration_mask(height, 64, seconds=(3.0, 6.0)),
+                num_inference_steps=N, guidance_scale=guidance)
+    calls = {}
+    for name in ("ddim", "repaint"):
+        pipe.scheduler = scheds[name]
+        pipe(generator=torch.Generator().manual_seed(1), **call)                    # warm-up: engine build + capture
+        ms = timed(lambda: pipe(generator=torch.Generator().manual_seed(1), **call), args.repeats)
+        calls[name] = {"unet_calls": len(pipe.scheduler.timesteps), "ms_per_call": round(ms, 1)}
+    print(json.dumps({"what": "RePaint at config 2 (4 x 10 s, CFG 2.5, rank-4 LoRA, random-init weights, 3 s of 10 s regenerated): "
+                              "masked_launch_us = the masked fused step alone inside a graph, per launch; inpaint_call = one a2a call at "
+                              f"strength 1.0, {N} grid levels, RePaint jump_length 5 x jump_n_sample 3 against DDIM's legacy blend",
+                      "masked_launch_us": launch_us, "inpaint_call": calls}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--repaint", action="store_true", help="measure the RePaint launch and call instead (DESIGN.md section 23)")
     args = ap.parse_args()
+    if args.repaint:
+        return repaint_numbers(args)
     from audioldm_with_lora_amd import ops
     from audioldm_with_lora_amd.audio2audio import AudioLDMAudioToAudioPipeline, reduce_mask, regeneration_mask
     from audioldm_with_lora_amd.mel import LogMelFrontEnd
