@@ -23,6 +23,16 @@
 //   d + 1  B*n normals        zj, the noise of the jump back up c1 xb + c2 zj  (line 10; not generated on rows with c2 == 0)
 // Element i of the [B][n] latent -- the LONG latent [B][rows][wc] when windowed -- is element i of each draw, and the bits are
 // aldm_randn's for the same state with the ordinal set to that draw.  With ticket == NULL the counter and the ordinal stay.
+//
+// Clip-segment stream contract (aldm_clip_segment, clip_prep.hip).  One LOGICAL batch of recordings that finds the ordinal at d uses
+// ONE draw and leaves the ordinal at d + 1 -- always one, and always ten words per row, whether a row is shorter than the segment
+// (no word is looked at) or its first candidate already holds a sound (the other nine stay unused), so streams stay aligned whatever
+// the recordings hold:
+//   d      10 * (rows of the logical batch) raw words     w = element ordinals[b] * 10 + c is candidate c = 0 .. 9 of row b:
+//                                                          start_c = ((w >> 8) * (L - S)) >> 24 in 64-bit integers
+// Element i is element i of aldm_philox_u32 for the same state.  A logical batch may be split over several calls (one per sampling
+// rate), each with its rows' ordinals: they all read draw d, and only the last one passes advance != 0 -- a trailing one-thread
+// launch, behind every reader in stream order, stores d + 1.
 #pragma once
 #include "common.h"
 

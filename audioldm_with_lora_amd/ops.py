@@ -1628,10 +1628,77 @@ def resample_poly(x, up, down, lens=None, table=None):
         raise ValueError(f"resample_poly: table must be contiguous fp32 [{up}, {K}] on {x.device}")
     T_out = R.output_length(T, up, down)
     y = torch.empty(B, T_out, dtype=torch.float32, device=x.device)
-    dl = lens.to(x.device)
+    dl = _h2d(lens, x.device)
     check(_lib.load().aldm_resample_poly(_p(x), _p(dl), B, T, _p(table), up, down, K, half, _p(y), T_out, _stream()),
           "aldm_resample_poly")
     return y, ((lens.to(torch.int64) * up + down - 1) // down).to(torch.int32)
+
+
+def _h2d(t, device):
+    """A small host tensor -> `device` from pinned memory, without blocking the host: a pageable `.to(device)` on the current stream
+    waits for everything queued there (the previous training step's graph), a pinned non-blocking copy is only enqueued.  torch's
+    pinned-memory cache keeps the staging block alive until the copy has run."""
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def clip_segment(pool, offsets, lens, ordinals, S, state, max_len, advance=True):
+    """A random, non-silent window of S samples per recording (aldm_clip_segment; the rule is in include/aldm_hip.h, the stream
+    contract in csrc/philox.h).  pool: fp32 1-D on the device; row b is the lens[b] samples from pool[offsets[b]] on.  offsets int64
+    [B], lens int32 [B], ordinals int32 [B]: device tensors (a captured graph reads them), or anything torch.as_tensor takes, which
+    is then checked against the pool on the host and copied over.  max_len: a host-side upper bound of lens.  advance: leave the
+    draw ordinal one further (False for every call but the last of a batch that is split by sampling rate).
+    Returns (seg fp32 [B, S], start int32 [B] on the device)."""
+    _check_state(state)
+    _require_gpu(pool)
+    if pool.dtype != torch.float32 or pool.dim() != 1 or pool.numel() == 0 or not pool.is_contiguous():
+        raise ValueError("clip_segment: the pool must be a non-empty contiguous fp32 1-D tensor")
+    S, max_len = int(S), int(max_len)
+    if S <= 0 or max_len <= 0:
+        raise ValueError(f"clip_segment: S and max_len must be positive (got {S}, {max_len})")
+    on_dev = [torch.is_tensor(t) and t.is_cuda for t in (offsets, lens, ordinals)]
+    if not all(on_dev):
+        if any(on_dev):
+            raise ValueError("clip_segment: offsets, lens and ordinals must all be on the device or all on the host")
+        offsets = torch.as_tensor(offsets, dtype=torch.int64).reshape(-1)
+        lens = torch.as_tensor(lens, dtype=torch.int32).reshape(-1)
+        ordinals = torch.as_tensor(ordinals, dtype=torch.int32).reshape(-1)
+        if not (offsets.numel() == lens.numel() == ordinals.numel() > 0):
+            raise ValueError("clip_segment: offsets, lens and ordinals must hold one entry per row")
+        if int(lens.min()) < 0 or int(lens.max()) > max_len or int(offsets.min()) < 0 or int((offsets + lens).max()) > pool.numel():
+            raise ValueError("clip_segment: a row leaves the pool or is longer than max_len")
+        if int(ordinals.min()) < 0:
+            raise ValueError("clip_segment: ordinals must not be negative")
+        offsets, lens, ordinals = _h2d(offsets, pool.device), _h2d(lens, pool.device), _h2d(ordinals, pool.device)
+    B = lens.numel()
+    for t, dt in ((offsets, torch.int64), (lens, torch.int32), (ordinals, torch.int32)):
+        assert t.dtype == dt and t.numel() == B and t.is_contiguous() and t.device == pool.device, "clip_segment: int64 / int32 / int32 [B]"
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.aldm_clip_segment_workspace_floats(B, max_len)), dtype=torch.float32, device=pool.device)
+    seg = torch.empty(B, S, dtype=torch.float32, device=pool.device)
+    start = torch.empty(B, dtype=torch.int32, device=pool.device)
+    check(lib.aldm_clip_segment(_p(pool), pool.numel(), _p(offsets), _p(lens), _p(ordinals), B, S, max_len, _p(state), int(bool(advance)),
+                                _p(ws), _p(seg), _p(start), _stream()), "aldm_clip_segment")
+    return seg, start
+
+
+def clip_normalize(y, n, target):
+    """Mean removal, peak normalisation to 0.5 and zero padding / cropping to `target` samples (aldm_clip_normalize): y fp32 [B, T]
+    whose row b holds n[b] samples (int32 [B]; a host tensor or list is copied over) -> fp32 [B, target]."""
+    _require_gpu(y)
+    if y.dtype != torch.float32 or y.dim() != 2 or y.numel() == 0 or not y.is_contiguous():
+        raise ValueError("clip_normalize: y must be a non-empty contiguous fp32 [B, T]")
+    B, T = y.shape
+    target = int(target)
+    if target <= 0:
+        raise ValueError(f"clip_normalize: target must be positive (got {target})")
+    if not (torch.is_tensor(n) and n.is_cuda):
+        n = _h2d(torch.as_tensor(n, dtype=torch.int32).reshape(-1), y.device)
+    assert n.dtype == torch.int32 and n.numel() == B and n.is_contiguous() and n.device == y.device, "clip_normalize: n int32 [B]"
+    lib = _lib.load()
+    ws = torch.empty(3 * B * lib.aldm_clip_normalize_parts(T, target), dtype=torch.float64, device=y.device)
+    out = torch.empty(B, target, dtype=torch.float32, device=y.device)
+    check(lib.aldm_clip_normalize(_p(y), _p(n), B, T, target, _p(ws), _p(out), _stream()), "aldm_clip_normalize")
+    return out
 
 
 def train_noise_fused(state, alphas_cumprod, moments=None, latents=None, scaling_factor=1.0, noise_offset=0.0, ticket=None,

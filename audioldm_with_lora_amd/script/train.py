@@ -14,8 +14,18 @@ Two input contracts:
                              does, `vae.encode(mel).latent_dist.sample() * scaling_factor` [REF train:495-496] and
                              `normalize(text_encoder(ids, mask).text_embeds)` [REF train:510-524] on the HIP kernels
                              (vae.py, clap_text.py).  `--batches-file` loads a .pt dict of those three tensors.
-Without a file the driver trains on synthetic tensors of the same shapes (no datasets or checkpoints are available
-offline).  The dataset classes, the librosa mel front end and the CLAP / KAD metrics stay out of scope.
+  --audio-dir DIR            recordings: a folder in the Hugging Face audiofolder layout (wav files of any rate and a
+                             metadata.jsonl / metadata.csv with file_name and caption).  data.py decodes them once, keeps them on
+                             the device and cuts, resamples, normalises and log-mels each batch there into the
+                             `--input mel` batch above; `--duration` is the clip length in seconds, `--data-seed` (default
+                             `--seed` + 1) seeds the segment stream and the epoch permutations.  The tokeniser comes from
+                             `--model-dir`; `--tiny` without one uses data.ByteTokenizer.  A checkpoint carries the segment stream's
+                             position and the loader's (epoch, cursor) in `data.bin`; `--resume-from-checkpoint` restores both
+                             (rank 0's: with several processes the resumed run is exact only when the clip count divides by
+                             their number; a checkpoint without `data.bin` starts the recordings over, with a warning).
+Without a file or a folder the driver trains on synthetic tensors of the same shapes.  The reference's dataset class has its mirror
+in data.py (HfAudioDataset for rows already in memory, AudioFolder for a folder); its dead code (trim_wav, mixup, frequency / time
+masking) is not built.
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m audioldm_with_lora_amd.script.train \
         --max-train-steps 100
@@ -73,12 +83,40 @@ def synthetic_batch(B, g, vocab=50265, max_len=512, pad=1):
     return {"log_mel_spec": mel, "input_ids": ids, "attention_mask": mask}
 
 
+def build_audio_data(args, device, rank, world, tokenizer):
+    """--audio-dir: the resident dataset, the device front end and the loader (data.py); the seeds come from --data-seed"""
+    from ..data import AudioFolder, ClipFrontEnd, ClipLoader
+    seed = args.seed + 1 if args.data_seed is None else args.data_seed
+    front_end = ClipFrontEnd(device, duration=args.duration, seed=seed, rank=rank)
+    return ClipLoader(AudioFolder(args.audio_dir, tokenizer, device), front_end, args.train_batch_size, seed=seed, rank=rank, world=world)
+
+
+def save_data_state(path, loader):
+    torch.save({"front_end": loader.front_end.state_dict(), "loader": loader.state_dict()}, os.path.join(path, "data.bin"))
+
+
+def load_data_state(path, loader):
+    """Restores the data position a checkpoint carries; a checkpoint without one (written without --audio-dir, or before the data
+    path existed) leaves the loader at (epoch 0, cursor 0) with a warning.  Returns whether a position was restored."""
+    f = os.path.join(path, "data.bin")
+    if not os.path.isfile(f):
+        print(f"[train] warning: {path} holds no data.bin: the recordings start over at epoch 0 with the stream of --data-seed", flush=True)
+        return False
+    sd = torch.load(f)
+    loader.front_end.load_state_dict(sd["front_end"])
+    loader.load_state_dict(sd["loader"])
+    return True
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model-dir", default=None, help="local diffusers-format directory of cvssp/audioldm-s-full-v2")
     ap.add_argument("--input", choices=("latents", "mel"), default="latents")
     ap.add_argument("--latents-file", default=None)
     ap.add_argument("--batches-file", default=None)
+    ap.add_argument("--audio-dir", default=None, metavar="DIR", help="train from recordings: wav files + metadata.jsonl / metadata.csv")
+    ap.add_argument("--duration", type=float, default=10.24, help="clip length in seconds (--audio-dir)")
+    ap.add_argument("--data-seed", type=int, default=None, help="segment stream and epoch permutations (default: --seed + 1)")
     ap.add_argument("--output-dir", default="data/LoRA_weight/r2_alpha2")
     ap.add_argument("--rank", type=int, default=2)
     ap.add_argument("--lora-alpha", type=int, default=2)
@@ -104,6 +142,10 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.noise_offset != 0.0 and not args.device_noise:
         parser.error("--noise-offset applies to noise drawn on the device: add --device-noise")
+    if args.audio_dir:
+        if args.latents_file or args.batches_file:
+            parser.error("--audio-dir replaces --latents-file / --batches-file")
+        args.input = "mel"                                        # the loader yields the collate_fn batch
 
     accelerator = dp.Accelerator(gradient_accumulation_steps=1, mixed_precision=None)     # (the trainer itself accumulates)
     device = accelerator.device
@@ -136,13 +178,29 @@ def main(argv=None):
             text_encoder = ClapTextModelWithProjection.from_pretrained(args.model_dir, subfolder="text_encoder")
         elif args.tiny:
             vae = AutoencoderKL(**configs.tiny_vae())
-            text_encoder = ClapTextModelWithProjection(**dict(configs.tiny_clap_text(), max_position_embeddings=514,
-                                                              projection_dim=unet.cfg["class_embed_input_dim"]))
+            tiny_text = dict(configs.tiny_clap_text(), max_position_embeddings=514, projection_dim=unet.cfg["class_embed_input_dim"])
+            if args.audio_dir:                                    # room for every id of the byte-level stand-in tokeniser
+                from ..data import ByteTokenizer
+                tiny_text["vocab_size"] = max(tiny_text["vocab_size"], ByteTokenizer.vocab_size)
+            text_encoder = ClapTextModelWithProjection(**tiny_text)
         else:
             vae, text_encoder = AutoencoderKL(), ClapTextModelWithProjection()
         vae.requires_grad_(False).to(device)
         text_encoder.requires_grad_(False).to(device)
     data = torch.load(args.latents_file) if args.latents_file else (torch.load(args.batches_file) if args.batches_file else None)
+    loader = None
+    if args.audio_dir:
+        if args.model_dir:
+            from transformers import RobertaTokenizerFast          # host-side string -> ids only
+            tokenizer = RobertaTokenizerFast.from_pretrained(os.path.join(args.model_dir, "tokenizer"))
+        elif args.tiny:
+            from ..data import ByteTokenizer
+            tokenizer = ByteTokenizer()
+        else:
+            parser.error("--audio-dir needs the tokeniser of --model-dir (or --tiny)")
+        loader = build_audio_data(args, device, accelerator.process_index, accelerator.num_processes, tokenizer)
+        if args.resume_from_checkpoint:
+            load_data_state(args.resume_from_checkpoint, loader)
     # per-rank noise / timesteps drawn on the host; a resumed run draws a fresh stream, keyed by the step it resumes from.  With
     # --device-noise these generators only pick the data: noise and timesteps come from the trainer's Philox stream, whose position
     # load_state has just restored, so the resumed run continues the saved stream.
@@ -152,7 +210,9 @@ def main(argv=None):
     t0, train_loss, first_step = time.time(), 0.0, trainer.step_count + 1
     for micro_step in range(trainer.micro_step + 1, args.max_train_steps * K + 1):
         if args.input == "mel":
-            if data is not None:
+            if loader is not None:
+                batch = loader.next_batch()
+            elif data is not None:
                 idx = torch.randint(0, data["log_mel_spec"].shape[0], (B,), generator=g)
                 batch = {k: data[k][idx] for k in ("log_mel_spec", "input_ids", "attention_mask")}
             else:
@@ -169,7 +229,8 @@ def main(argv=None):
             prompt_embeds = torch.nn.functional.normalize(torch.randn(B, unet.cfg["class_embed_input_dim"], generator=g), dim=-1)
         if not args.device_noise:
             noise = torch.randn(latents.shape, generator=g)
-            timesteps = torch.randint(0, noise_scheduler.config.num_train_timesteps, (B,), generator=g).long()
+            # (sized by the batch at hand [REF train:501-503]: the last batch of an epoch of recordings may be short)
+            timesteps = torch.randint(0, noise_scheduler.config.num_train_timesteps, (latents.shape[0],), generator=g).long()
             loss = trainer.step(latents, noise, timesteps, prompt_embeds)
         elif args.input != "mel":
             loss = trainer.step(latents, None, None, prompt_embeds)
@@ -187,9 +248,13 @@ def main(argv=None):
                 print(json.dumps(rec), flush=True)
         if global_step % args.checkpointing_steps == 0 and accelerator.is_main_process:
             accelerator.save_state(os.path.join(args.output_dir, f"checkpoint-{global_step}"), trainer)
+            if loader is not None:
+                save_data_state(os.path.join(args.output_dir, f"checkpoint-{global_step}"), loader)
     accelerator.wait_for_everyone()
     if accelerator.is_main_process:
         accelerator.save_state(os.path.join(args.output_dir, f"checkpoint-{args.max_train_steps}"), trainer)
+        if loader is not None:
+            save_data_state(os.path.join(args.output_dir, f"checkpoint-{args.max_train_steps}"), loader)
     accelerator.end_training()
     return train_loss
 

@@ -745,6 +745,36 @@ int aldm_token_mean(const void* x, int B, int N, int C, float* out_f32, void* ou
 int aldm_resample_poly(const float* x, const int* lens, int B, int T_in, const float* table, int up, int down, int K, int half,
                        float* y, int T_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Clip front end of the training data path (csrc/clip_prep.hip): the dataset's read_hf_audio
+ * [REF script/data/datasets.py:174-195,494-522] on recordings that stay resident on the device.  fp32 in and out, no
+ * floating-point atomics, no host synchronisation: every call can be captured in a graph, and a row's result depends
+ * neither on B nor on the row's place in the batch.
+ * ------------------------------------------------------------------------------------------ */
+/* A random, non-silent window of S samples of each recording.  Row b is the lens[b] samples from x + offsets[b] on (x: a pool
+   of pool_len floats; a row that would leave the pool, or lens[b] > max_len, is cut short on the device; offsets int64 [B],
+   lens / ordinals int32 [B], all on the device).  With L = lens[b]:
+     L <= S      start = 0, seg = x[0 .. L) then zeros
+     otherwise   R = L - S; candidate c = 0 .. 9 starts at ((w >> 8) * R) >> 24 in 64-bit integers, w = element
+                 ordinals[b] * 10 + c of the current draw of rng_state (4 words, see aldm_randn; the word aldm_philox_u32
+                 returns for that element) -- int(R * torch.rand(1)) with torch's 24-bit uniform.  The row takes the first
+                 candidate whose window [start, start + S) holds a sample with |x| > 1e-4f (strictly), the tenth if none does.
+   seg fp32 [B][S], start int32 [B] (device).  ordinals: the row's index in the LOGICAL batch, so that a batch may be split over
+   several calls (one per sampling rate) that read the same draw: every call but the last passes advance = 0; advance != 0
+   appends a one-thread launch that leaves the draw ordinal one further.  One logical batch = exactly one draw.
+   workspace: aldm_clip_segment_workspace_floats of (B, max_len) floats (per-chunk maxima; contents need not survive). */
+long long aldm_clip_segment_workspace_floats(int B, int max_len);
+int aldm_clip_segment(const float* x, long long pool_len, const long long* offsets, const int* lens, const int* ordinals, int B,
+                      int S, int max_len, unsigned* rng_state, int advance, float* workspace, float* seg, int* start,
+                      void* stream);
+/* normalize_wav + pad_wav [REF script/data/datasets.py:174-212]: over the first m = min(n[b], target, T) samples of row b of
+   y fp32 [B][T] (n int32 [B] on the device):  mean = sum / m (the sum in float64),  peak = max |y - mean|,
+     out[b][i] = (y[b][i] - mean) / (peak + 1e-8f) * 0.5f  for i < m,  exactly 0 for m <= i < target        out fp32 [B][target]
+   A row with m == 0 is all zeros; a constant row gives exact zeros.  workspace: 3 * B * aldm_clip_normalize_parts of (T, target)
+   doubles (per-slice sum / max / min; several workgroups share a row). */
+int aldm_clip_normalize_parts(int T, int target);
+int aldm_clip_normalize(const float* y, const int* n, int B, int T, int target, double* workspace, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
