@@ -314,6 +314,11 @@ __global__ __launch_bounds__(64 * NW) void pgemm_kernel(const bf16* __restrict__
             *reinterpret_cast<bf16x4*>(p.lora_t + (long long)mrow[i] * p.Rp + 16 * rt + 4 * q) =
                 bf16x4{tf[i][4 * rt], tf[i][4 * rt + 1], tf[i][4 * rt + 2], tf[i][4 * rt + 3]};
         }
+        // the copy is [M][Rp] WHOLE, as aldm_igemm's: columns from 16 RT on hold no rank (ranks_used <= 16 RT) and are zeros -- left
+        // unwritten they were whatever the caller's buffer held (tests/test_gpu_pgemm_edges.py: a NaN arena)
+        if (p.lora_t && nr == 0 && mrow[i] < M)
+          for (int col = 16 * RT + 4 * q; col < p.Rp; col += 16)
+            *reinterpret_cast<bf16x4*>(p.lora_t + (long long)mrow[i] * p.Rp + col) = bf16x4{0, 0, 0, 0};
       }
     }
     PG_STAMP(2)
