@@ -10,7 +10,9 @@ LIB_PATH = os.environ.get("ALDM_LIB") or os.path.join(_HERE, "libaldm_hip.so")  
 
 ACT_NONE, ACT_SILU, ACT_LRELU, ACT_TANH, ACT_GELU = 0, 1, 2, 3, 4
 OUT_BF16, OUT_F32 = 0, 1
-TILE_AUTO, TILE_128x128, TILE_64x64, TILE_128x64, TILE_64x128 = 0, 1, 2, 3, 4
+TILE_AUTO, TILE_128x128, TILE_64x64, TILE_128x64, TILE_64x128 = 0, 1, 2, 3, 4    # ALDM_TILE_* (igemm_plan.TILES says what each one is)
+TILE_128x128_W8, TILE_HALO_128x128, TILE_HALO_64x128, TILE_256x128_W8, TILE_64x128_W8, TILE_128x64_W8 = 6, 7, 8, 9, 10, 11
+TILE_256x128_WS, TILE_64x128_WS, TILE_128x64_WS, TILE_HALO_128x128_WS, TILE_HALO_64x128_WS = 12, 13, 14, 15, 16
 EPI_AUTO, EPI_LDS, EPI_DIRECT = 0, 0x10, 0x20                    # aldm_igemm_t.xcd_map bits 4-5: form of the standard epilogue
 DEFER_ROWMAJOR, DEFER_PLANAR, DEFER_WRITE_THROUGH = 1, 2, 4     # aldm_igemm_t.defer_reduce flags
 SLAB_ROWMAJOR, SLAB_PLANAR = 0, 1                               # slab layout as aldm_groupnorm_partials_layout is told it

@@ -7,7 +7,6 @@ import ctypes as C
 import json
 import math
 import os
-import sys
 from dataclasses import dataclass
 from typing import Optional
 
@@ -54,6 +53,10 @@ class PackedW:
     @property
     def Kpad(self):
         return self.w.shape[1]
+
+    @property
+    def ln(self):
+        return self.ln_s is not None
 
 
 def _pad_k(w2d: torch.Tensor) -> torch.Tensor:
@@ -181,55 +184,16 @@ def attach_lora(pw: PackedW, parts, layout=None):
     return pw
 
 
-def auto_splits(M, N, ktiles):
-    """Split-K heuristic (tools/bench_igemm.py sweep): the low-resolution UNet levels have few 64x64 output
-    tiles but deep K; split until ~512 workgroups are in flight, at most 4 ways, >= 8 K-tiles per split."""
-    tiles = math.ceil(M / 64) * math.ceil(N / 64)
-    if tiles >= 256 or ktiles < 16:
-        return 1
-    return max(1, min(4, math.ceil(512 / tiles), ktiles // 8))
-
-
-def pick_tile(M, N):
-    """Tile heuristic from tools/bench_igemm.py sweeps on MI355X: the 8-wave 128x128 tile once it still yields ~2
-    workgroups per CU (256 CUs), 128x64 down to ~2 per CU, else 64x64 (more, smaller workgroups hide the short K loops
-    of the low-resolution levels)."""
-    if N >= 256 and N % 128 == 0 and math.ceil(M / 128) * (N // 128) >= 448:
-        return 6
-    if N > 64 and math.ceil(M / 128) * math.ceil(N / 64) >= 448:
-        return _lib.TILE_128x64
-    if N <= 64 and M >= 4096:
-        return _lib.TILE_128x64
-    return _lib.TILE_64x64
-
-
-def pick_ring(tile, bm, bn, rp, nwg, ktiles):
-    """LDS-DMA ring depth (2..4 K-tiles in flight).  Rule from tools/bench_igemm.py --ring sweeps on MI355X:
-    residency first -- the ring must leave room for ceil(nwg / 256 CUs) workgroups per CU inside the 160 KiB of LDS,
-    otherwise the grid runs in two rounds (128x64 tile, 500 workgroups: ring 4 = 98 KiB/WG -> 38.9 us, ring 3 -> 23.9 us);
-    then depth -- few workgroups (low-resolution levels) have nothing else to hide the weight stream's latency behind, so
-    they take the deepest ring that fits; big grids gain nothing past 2-3."""
-    if tile in (6, 9):
-        return 2
-    if tile == 12:
-        return 3
-    stage = (bm + bn + rp) * 128
-    extra = (bn * 128 if rp else 0) + 2 * bm * 4
-    per_cu = min(8, max(1, math.ceil(nwg / 256)))
-    fit = ((160 * 1024) // per_cu - extra) // stage
-    want = 4 if nwg <= 512 else (2 if ktiles <= 24 else 3)
-    return max(2, min(want, fit))
-
-
-TILE_DIMS = {1: (128, 128), 2: (64, 64), 3: (128, 64), 4: (64, 128), 6: (128, 128), 7: (128, 128), 8: (64, 128), 9: (256, 128), 10: (64, 128), 11: (128, 64), 12: (256, 128), 13: (64, 128), 14: (128, 64), 15: (128, 128), 16: (64, 128)}
-HALO_ROWS = {7: 320, 8: 128, 15: 320, 16: 128}          # LDS halo capacity (rows) of the two halo tiles (csrc/igemm_halo.hip; 128x128: three or five DMA passes)
+# How a convolution is launched (tile table, halo rule, tuning key, heuristics, plan()) lives in igemm_plan.py; these names stay
+# importable from here.
+from . import igemm_plan
+from .igemm_plan import (HALO_ROWS, TILE_DIMS, TILE_NAMES, TILES, auto_splits, halo_candidates, heuristic_cfg, parse_key,  # noqa: E402,F401
+                         pick_ring, pick_tile, tune_key)
 
 
 def halo_tiles(OW, eligible):
     """Halo tiles able to take a 3x3/s1/p1 conv whose output is OW wide: BM a multiple of OW and the halo within capacity."""
-    if not eligible:
-        return []
-    return [t for t in (7, 8, 15, 16) if TILE_DIMS[t][0] % OW == 0 and (TILE_DIMS[t][0] // OW + 2) * (OW + 2) <= HALO_ROWS[t]]
+    return halo_candidates(igemm_plan.Geom(B=1, IH=OW, IW=OW, C1=64, OH=OW, OW=OW, N=64, Kpad=576, Cin=64, KH=3, KW=3, pad=(1, 1))) if eligible else []
 
 # ---- measured launch configurations ------------------------------------------------------------------------------
 # "Measure, don't guess": tools/autotune.py picks (tile, ring, splits) per distinct GEMM in two stages and writes
@@ -251,28 +215,6 @@ if os.environ.get("ALDM_TUNED_PATCH"):                           # A/B aid: a JS
 TUNED_LEGACY_KEYS = any(" k3x3 " in k and " ow" not in k for k in TUNED)
 
 
-def tune_key(M, N, c1, c2, kh, kw, stride, up, dilate, rp, vt, geglu, ln, fast, ow=None, pad=None, dil=None):
-    """Key of one GEMM in the measured table.  The geometry suffix (output width, padding, filter dilation) is part of the key for
-    every filter larger than 1x1: two convolutions with equal M / N / C can differ in OW (UNet level 0 is 16 wide, the VAE
-    decoder's last level 64) and then differ in which tiles are even legal (the halo tiles need BM % OW == 0)."""
-    key = (f"M{M} N{N} C{c1}+{c2} k{kh}x{kw} s{stride[0]} up{int(up)} d{dilate} r{rp} vt{int(vt)} g{int(bool(geglu))} "
-           f"ln{int(ln)} f{int(fast)}")
-    if ow is not None and (kh > 1 or kw > 1):
-        key += f" ow{ow} p{pad[0]}x{pad[1]} dl{dil[0]}x{dil[1]}"
-    return key
-
-
-def heuristic_cfg(M, pw, ktiles, can_split, fast_path, has_vt, splits=None):
-    if splits is None:
-        splits = auto_splits(M, pw.N, ktiles) if can_split else 1
-    tile = _lib.TILE_64x64 if pw.Rp else pick_tile(M, pw.N)      # LoRA GEMMs are short-K: favour many workgroups
-    if tile == 6 and (not fast_path or has_vt or ktiles < 16):
-        tile = _lib.TILE_128x64           # the 8-wave tile only exists on the LDS-DMA path and only pays on deep K loops
-    bm, bn = TILE_DIMS[tile]
-    nwg = math.ceil(M / bm) * math.ceil(pw.N / bn) * max(1, splits)
-    return tile, pick_ring(tile, bm, bn, pw.Rp, nwg, ktiles), splits
-
-
 class Tuner:
     """Two-stage launch-configuration search driven by tools/autotune.py."""
 
@@ -283,38 +225,35 @@ class Tuner:
         self.slot = None         # stage 2: which shortlist slot this pass runs
 
     # ---- stage 1 ----
-    def isolated(self, a, key, M, pw, ktiles, can_split, forced_splits, fast_path, has_vt, device, halo=()):
+    def isolated(self, key, g, forced_splits, make_args, device, halo=()):
+        """g: the launch's igemm_plan.Geom; make_args(): its argument struct, filled except for the launch configuration"""
         lib = _lib.load()
-        default = heuristic_cfg(M, pw, ktiles, can_split, fast_path, has_vt, forced_splits)
+        a = make_args()
+        M, N, ktiles = g.M, g.N, g.ktiles
+        can_split = g.can_split and forced_splits is None
+        default = heuristic_cfg(M, g, ktiles, can_split, g.fast_path, g.vt, forced_splits)
         cands = []
-        for t in [2, 3, 1, 4] + ([6] if (fast_path and not has_vt and ktiles >= 8) else []) + (
-                [9, 12] if (fast_path and not has_vt and not pw.Rp and ktiles >= 8 and M >= 32768 and pw.N % 128 == 0 and pw.ln_s is None
-                            and not pw.geglu and not pw.Cext) else []) + (
-                [10, 11] if (fast_path and not has_vt and not pw.Rp and ktiles >= 8 and M <= 8192) else []) + (
-                [13, 14] if (fast_path and not has_vt and not pw.Rp and ktiles >= 8 and M <= 8192 and pw.ln_s is None and not pw.geglu) else []):
-            bm, bn = TILE_DIMS[t]
-            if has_vt and a.vt_col0 % bn:
+        for t in map(TILES.get, igemm_plan.generic_candidates(g)):
+            if g.vt and g.vt_col0 % t.bn:
                 continue
-            base = math.ceil(M / bm) * math.ceil(pw.N / bn)
+            base = math.ceil(M / t.bm) * math.ceil(N / t.bn)
             sp_list = [forced_splits or 1]
             if can_split and base <= 640:
                 sp_list += [sp for sp in (2, 3, 4, 6, 8, 12, 16)
-                            if sp <= ktiles // 2 and base * sp <= 2560 and sp * M * pw.N * 4 <= (1 << 28)]
-            for sp in sp_list:
-                for rg in ((3,) if t == 12 else (3, 4) if t in (13, 14) else (2, 3) if t in (6, 9) else (2, 3, 4)):
-                    cands.append((t, rg, sp))
+                            if sp <= ktiles // 2 and base * sp <= 2560 and sp * M * N * 4 <= (1 << 28)]
+            cands += [(t.id, rg, sp) for sp in sp_list for rg in t.rings]
         if forced_splits in (None, 1):
-            cands += [(t, rg, 1) for t in halo for rg in (2, 3, 4)]
+            cands += [(t, rg, 1) for t in halo for rg in TILES[t].rings]
             if can_split and " gi" not in key:              # the halo tiles split by 64-channel chunk (csrc/igemm_halo.hip)
                 nch = ktiles // 9
-                for t in halo:
-                    base = math.ceil(M / TILE_DIMS[t][0]) * math.ceil(pw.N / TILE_DIMS[t][1])
-                    cands += [(t, rg, sp) for sp in (2, 3, 4, 5, 6, 8, 10) for rg in (3, 4)
-                              if sp <= nch and base * sp <= 2560 and sp * M * pw.N * 4 <= (1 << 28)]
+                for t in map(TILES.get, halo):
+                    base = math.ceil(M / t.bm) * math.ceil(N / t.bn)
+                    cands += [(t.id, rg, sp) for sp in (2, 3, 4, 5, 6, 8, 10) for rg in t.rings[1:]    # (split: the two deeper rings)
+                              if sp <= nch and base * sp <= 2560 and sp * M * N * 4 <= (1 << 28)]
         max_sp = max(c[2] for c in cands)
         defer_flags = (_lib.DEFER_ROWMAJOR | (_lib.DEFER_PLANAR if SLAB_LAYOUT == _lib.SLAB_PLANAR else 0)
                        | (_lib.DEFER_WRITE_THROUGH if SLAB_WT else 0))
-        ws = _workspace(max_sp * M * pw.N * 4, device) if max_sp > 1 else None
+        ws = _workspace(max_sp * M * N * 4, device) if max_sp > 1 else None
         results = []
         for t, rg, sp in cands:
             a.tile, a.ring, a.splits = t, rg, sp
@@ -341,7 +280,7 @@ class Tuner:
     # ---- called by conv() ----
     def choose(self, key, *args):
         if key not in self.cands:
-            return self.isolated(args[0], key, *args[1:])
+            return self.isolated(key, *args)
         c = self.cands[key]
         return c[self.slot % len(c)] if self.slot is not None else c[0]
 
@@ -368,8 +307,6 @@ def save_tuned(path=TUNED_PATH):
         json.dump({"device": "MI355X gfx950", "format": "key -> [tile, ring, splits]",
                    "igemm": {k: list(v) for k, v in sorted(TUNED.items())}}, f, indent=0)
 
-
-TILE_NAMES = {1: "128x128", 2: "64x64", 3: "128x64", 4: "64x128", 6: "128x128w8", 7: "halo128x128", 8: "halo64x128", 9: "256x128w8", 10: "64x128w8", 11: "128x64w8", 12: "256x128ws", 13: "64x128ws", 14: "128x64ws", 15: "halo128x128ws", 16: "halo64x128ws"}
 
 # Optional launch profiler (bench.py): a list that receives (label, flops, bytes, start_event, end_event, site) per C-ABI call.
 # Events are recorded on the stream the kernel is launched on.  SITE tags the launches of one fused-LoRA attention module
@@ -452,10 +389,7 @@ class QStats:
     tpi: int
 
 
-# Stand-alone GroupNorms read the statistics their producer handed over where that pays: big images (the strip-per-workgroup kernel
-# is L2-request-bound there) -- below this many pixels per image the register-resident kernel is as fast (HW = 1000: 6.7 us against
-# 10.0 us for fold + apply) and the producers' epilogues stay free of the statistics code.
-QSTATS_MIN_HW = 2048
+QSTATS_MIN_HW = igemm_plan.QSTATS_MIN_HW                   # (read per call: tests lower it)
 
 
 # aldm_igemm_t.xcd_map: 0 = the library decides per launch which operand an XCD's L2 keeps (weight-stationary where the weight matrix
@@ -540,6 +474,84 @@ def tensor_of(x):
     return x.out if isinstance(x, Deferred) else x
 
 
+def _has_qstats(x, x2):
+    """Is every source of a gn_in launch a raw convolution output with a statistics table the launch can read?"""
+    if not isinstance(x, torch.Tensor) or getattr(x, "qstats", None) is None or x.dim() != 4:
+        return False
+    if x2 is not None and (not isinstance(x2, torch.Tensor) or getattr(x2, "qstats", None) is None):
+        return False
+    hw = x.shape[1] * x.shape[2]
+    return all(q.tpi > 0 or q.bm <= hw for q in (x.qstats, x2.qstats if x2 is not None else None) if q is not None)
+
+
+def _igemm_args(g, x, x2, x3, x4, pw, out, *, in_slope, rowbias, rowbias_ld, out_slope, res, res2, post_slope, out2, vt, vt_ld,
+                vt_batch_stride, lora_t_out, lora_gate, ln_parts, gn_in):
+    """conv()'s aldm_igemm_t with every operand in place; the launch configuration (tile, ring, splits, workspace, statistics tables,
+    xcd_map, defer_reduce) is left to the caller.  g: the call's igemm_plan.Geom."""
+    a = IgemmArgs()
+    if x3 is not None:
+        for t in (x3, x4):
+            assert t is None or (t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape[:3]) == (g.B, g.OH, g.OW))
+        a.x3, a.Cin3 = x3.data_ptr(), g.C3
+        if x4 is not None:
+            a.x4, a.Cin4 = x4.data_ptr(), g.C4
+    a.x, a.x2 = x.data_ptr(), (x2.data_ptr() if x2 is not None else None)
+    a.B, a.IH, a.IW, a.Cin, a.Cin2 = g.B, g.IH, g.IW, g.C1, g.C2
+    a.UH, a.UW = (g.up_size if g.up_size is not None else (0, 0))
+    a.in_dilate = g.in_dilate
+    a.w, a.Kpad = pw.w.data_ptr(), pw.Kpad
+    a.KH, a.KW = g.KH, g.KW
+    a.stride_h, a.stride_w = g.stride
+    a.pad_h, a.pad_w = g.pad
+    a.dil_h, a.dil_w = g.dil
+    a.OH, a.OW, a.Cout = g.OH, g.OW, pw.N
+    a.in_act, a.in_slope = g.in_act, in_slope
+    if pw.Rp:
+        a.lora_a, a.lora_b, a.Rp = pw.lora_a.data_ptr(), pw.lora_b.data_ptr(), pw.Rp
+        a.lora_t_out = lora_t_out.data_ptr() if lora_t_out is not None else None
+    gate, gate_rows = _gate_for(pw, g.M, lora_gate, lora_t_out)
+    if gate is not None:
+        a.lora_gate, a.gate_rows = gate.data_ptr(), gate_rows
+    a.bias = pw.bias.data_ptr() if pw.bias is not None else None
+    if pw.ln_s is not None:
+        a.ln_s, a.ln_eps = pw.ln_s.data_ptr(), pw.ln_eps
+        if pw.Rp:
+            a.ln_sa, a.ln_ca = pw.ln_sa.data_ptr(), pw.ln_ca.data_ptr()
+        if ln_parts is not None:
+            assert ln_parts.dtype == torch.float32 and ln_parts.is_contiguous() and ln_parts.dim() == 3 and ln_parts.shape[2] == 2
+            assert ln_parts.shape[0] == g.B * g.IH * g.IW and g.KH == 1 and g.KW == 1, "ln_parts: one row of partials per GEMM row"
+            a.ln_parts, a.ln_nparts = ln_parts.data_ptr(), ln_parts.shape[1]
+    elif ln_parts is not None:
+        raise _lib.AldmError("conv: ln_parts without a LayerNorm-folded weight pack (pack_linear_ln)")
+    if g.rowstats and (g.vt or g.geglu or g.out_f32 or g.out2 or g.N % 64 or g.gn_groups is not None or g.defer):
+        raise _lib.AldmError("conv: rowstats needs the standard bf16 epilogue and N % 64 == 0")
+    if rowbias is not None:
+        assert rowbias.dtype == torch.float32
+        a.rowbias, a.rowbias_ld = rowbias.data_ptr(), rowbias_ld
+    a.geglu = 1 if pw.geglu else 0
+    a.out_act, a.out_slope = g.out_act, out_slope
+    a.res = res.data_ptr() if res is not None else None
+    a.res2 = res2.data_ptr() if res2 is not None else None
+    a.alpha = g.alpha
+    a.post_act, a.post_slope = g.post_act, post_slope
+    a.out2 = out2.data_ptr() if out2 is not None else None
+    a.out, a.out_dtype, a.out_ld = out.data_ptr(), g.out_dtype, g.out_ld
+    a.out_batch_stride = g.out_batch_stride
+    a.out_pix_stride, a.out_pix_offset = g.out_pix_stride, g.out_pix_offset
+    if vt is not None:
+        a.vt, a.vt_col0, a.vt_ld, a.vt_batch_stride = vt.data_ptr(), g.vt_col0, vt_ld, vt_batch_stride
+        a.vt_dual = 1 if g.vt_dual else 0
+    if gn_in is not None:
+        # GroupNorm of the input inside the launch: statistics from the producers' tables
+        q1, q2 = x.qstats, (x2.qstats if x2 is not None else None)
+        gm_, bt_, a.gnin_groups, a.gnin_eps, a.gnin_act = gn_in
+        a.gnin_gamma, a.gnin_beta = gm_.data_ptr(), bt_.data_ptr()
+        a.gnin_q1, a.gnin_bm1, a.gnin_tpi1 = q1.table.data_ptr(), q1.bm, q1.tpi
+        if q2 is not None:
+            a.gnin_q2, a.gnin_bm2, a.gnin_tpi2 = q2.table.data_ptr(), q2.bm, q2.tpi
+    return a
+
+
 def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, stride=(1, 1), pad=(0, 0), dil=(1, 1),
          up_size=None, in_dilate=0, out_hw=None, in_act=ACT_NONE, in_slope=0.0, rowbias=None, rowbias_ld=0, out_act=ACT_NONE,
          out_slope=0.0, res=None, res2=None, alpha=1.0, post_act=ACT_NONE, post_slope=0.0, out2=None, out=None, out_f32=False, out_ld=None, out_batch_stride=None,
@@ -571,6 +583,7 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
     launch the direct form cannot take; EPI_AUTO walks the LDS image there).
 
     lora_gate (default: ops.LORA_GATE): fp32 [samples][Rp] per-sample gates of the LoRA side channel's columns (multi-adapter routing)."""
+    # ---- checks on the operands
     _require_gpu(x)
     if _pending_get(x) is not None:
         raise _lib.AldmError("conv: a deferred split-K reduce is pending on this stream -- its consumer groupnorm() must be the next launch")
@@ -584,187 +597,50 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
     C3 = x3.shape[3] if x3 is not None else 0
     C4 = x4.shape[3] if x4 is not None else 0
     assert C3 + C4 == pw.Cext, f"conv: fused 1x1 segment channels {C3}+{C4} != packed {pw.Cext}"
-    KH, KW = pw.KH, pw.KW
-    VH, VW = (up_size if up_size is not None else (IH, IW))
-    if out_hw is None:
-        OH = (VH + 2 * pad[0] - dil[0] * (KH - 1) - 1) // stride[0] + 1
-        OW = (VW + 2 * pad[1] - dil[1] * (KW - 1) - 1) // stride[1] + 1
-    else:
-        OH, OW = out_hw
-    ncols = pw.N // 2 if pw.geglu else pw.N
-    if vt is not None and not vt_dual:
-        ncols = vt_col0
-    if out_ld is None:
-        out_ld = ncols
+    assert out_batch_stride is not None or (out_pix_stride == 1 and out_pix_offset == 0), "strided output rows need an explicit batch stride"
+    # ---- geometry: the call without its tensors
+    g = igemm_plan.geometry(
+        (B, IH, IW, C1), pw, C2=C2, C3=C3, C4=C4, x2=x2 is not None, x3=x3 is not None, stride=stride, pad=pad, dil=dil, up_size=up_size,
+        in_dilate=in_dilate, out_hw=out_hw, in_act=in_act, vt=vt is not None, vt_dual=bool(vt_dual), vt_col0=vt_col0, rowbias=rowbias is not None,
+        res=res is not None, res_numel=(res.numel() if res is not None and res.is_contiguous() else None), res2=res2 is not None,
+        out2=out2 is not None, out_act=out_act, post_act=post_act, alpha=alpha, lora_t_out=lora_t_out is not None,
+        ln_parts=None if ln_parts is None else ln_parts.shape[1], rowstats=bool(rowstats), qstats=qstats, qstats_min_hw=QSTATS_MIN_HW,
+        gn_groups=None if gn is None else gn[2], defer=defer, gn_in=gn_in is not None, tile=tile, ring=ring, splits=splits, out_f32=out_f32,
+        out_dtype=None if out is None else (OUT_F32 if out.dtype == torch.float32 else OUT_BF16), out_ld=out_ld,
+        out_batch_stride=out_batch_stride, out_pix_stride=out_pix_stride, out_pix_offset=out_pix_offset)
+    OH, OW, M = g.OH, g.OW, g.M
     if out is None:
-        out = torch.empty(B, OH, OW, out_ld, dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
-    if out_batch_stride is None:
-        assert out_pix_stride == 1 and out_pix_offset == 0, "strided output rows need an explicit batch stride"
-        out_batch_stride = OH * OW * out_ld
-    if (PGEMM and tile == 0 and ring == 0 and KH == 1 and KW == 1 and stride == (1, 1) and pad == (0, 0) and up_size is None
-            and not in_dilate and in_act == ACT_NONE and x2 is None and x3 is None and pw.Kpad == C1 and C1 in PGEMM_K
-            and pw.N % 64 == 0 and out.dtype == torch.bfloat16 and out_pix_stride == 1 and out_pix_offset == 0
-            and out_batch_stride == OH * OW * out_ld and out_ld % 8 == 0 and rowbias is None and out_act == ACT_NONE
-            and post_act == ACT_NONE and res2 is None and out2 is None and alpha == 1.0 and (lora_t_out is None or pw.Rp)
-            and splits in (None, 1) and gn is None and (not vt_dual or vt is not None)
-            and not (qstats and OH * OW >= QSTATS_MIN_HW)
-            and (not pw.Rp or getattr(pw, "ranks_used", 99) <= 32)
-            and (pw.ln_s is None or (ln_parts is not None and ln_parts.shape[1] <= 16 and (vt is not None or pw.geglu)))   # (aldm_pgemm folds a
-            #                     LayerNorm in its V^T and GEGLU forms only: a plain LayerNorm-folded linear stays on aldm_igemm)
-            and not (pw.geglu and (res is not None or vt is not None or pw.Rp or rowstats))
-            and not (vt is not None and (res is not None or rowstats or vt_col0 % 32 or (vt_col0 <= 0 and not vt_dual) or vt_col0 < 0))
-            and (res is None or (res.is_contiguous() and res.numel() == B * OH * OW * out_ld))
-            and PGEMM_CFG.get(_pgemm_key(B * OH * OW, pw, C1, res, vt, rowstats, lora_t_out is not None, vt_dual)) != PGEMM_USE_IGEMM):
-        return _pgemm(x, pw, out, out_ld, B * OH * OW, C1, OH * OW, res, vt, vt_col0, vt_ld, vt_batch_stride, rowstats, ln_parts, lora_t_out, vt_dual,
+        out = torch.empty(B, OH, OW, g.out_ld, dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
+    if gn_in is not None and not (_has_qstats(x, x2) and halo_candidates(g)):
+        raise _lib.AldmError("conv: gn_in needs a 3x3 / stride 1 / pad 1 launch that fits a halo tile and inputs with .qstats (gn_in_ok)")
+    # ---- plan: route, tile, ring, splits, the statistics tables (igemm_plan.py)
+
+    def fill():
+        return _igemm_args(g, x, x2, x3, x4, pw, out, in_slope=in_slope, rowbias=rowbias, rowbias_ld=rowbias_ld, out_slope=out_slope, res=res,
+                           res2=res2, post_slope=post_slope, out2=out2, vt=vt, vt_ld=vt_ld, vt_batch_stride=vt_batch_stride,
+                           lora_t_out=lora_t_out, lora_gate=lora_gate, ln_parts=ln_parts, gn_in=gn_in)
+
+    tuning = TUNER is not None and not tile and not ring and not torch.cuda.is_current_stream_capturing()
+    p = igemm_plan.plan(g, TUNED, (lambda key, gg, sp, halo: TUNER.choose(key, gg, sp, fill, x.device, halo)) if tuning else None,
+                        PGEMM_CFG if PGEMM else None, TUNED_LEGACY_KEYS)
+    if p.route == "pgemm":
+        return _pgemm(x, pw, out, g.out_ld, M, C1, OH * OW, res, vt, vt_col0, vt_ld, vt_batch_stride, rowstats, ln_parts, lora_t_out, vt_dual,
                       lora_gate=lora_gate)
-    a = IgemmArgs()
-    if x3 is not None:
-        for t in (x3, x4):
-            assert t is None or (t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape[:3]) == (B, OH, OW))
-        a.x3, a.Cin3 = x3.data_ptr(), C3
-        if x4 is not None:
-            a.x4, a.Cin4 = x4.data_ptr(), C4
-    a.x, a.x2 = x.data_ptr(), (x2.data_ptr() if x2 is not None else None)
-    a.B, a.IH, a.IW, a.Cin, a.Cin2 = B, IH, IW, C1, C2
-    a.UH, a.UW = (up_size if up_size is not None else (0, 0))
-    a.in_dilate = in_dilate
-    a.w, a.Kpad = pw.w.data_ptr(), pw.Kpad
-    a.KH, a.KW = KH, KW
-    a.stride_h, a.stride_w = stride
-    a.pad_h, a.pad_w = pad
-    a.dil_h, a.dil_w = dil
-    a.OH, a.OW, a.Cout = OH, OW, pw.N
-    a.in_act, a.in_slope = in_act, in_slope
-    if pw.Rp:
-        a.lora_a, a.lora_b, a.Rp = pw.lora_a.data_ptr(), pw.lora_b.data_ptr(), pw.Rp
-        a.lora_t_out = lora_t_out.data_ptr() if lora_t_out is not None else None
-    gate, gate_rows = _gate_for(pw, B * OH * OW, lora_gate, lora_t_out)
-    if gate is not None:
-        a.lora_gate, a.gate_rows = gate.data_ptr(), gate_rows
-    a.bias = pw.bias.data_ptr() if pw.bias is not None else None
-    if pw.ln_s is not None:
-        a.ln_s, a.ln_eps = pw.ln_s.data_ptr(), pw.ln_eps
-        if pw.Rp:
-            a.ln_sa, a.ln_ca = pw.ln_sa.data_ptr(), pw.ln_ca.data_ptr()
-        if ln_parts is not None:
-            assert ln_parts.dtype == torch.float32 and ln_parts.is_contiguous() and ln_parts.dim() == 3 and ln_parts.shape[2] == 2
-            assert ln_parts.shape[0] == B * IH * IW and KH == 1 and KW == 1, "ln_parts: one row of partials per GEMM row"
-            a.ln_parts, a.ln_nparts = ln_parts.data_ptr(), ln_parts.shape[1]
-    elif ln_parts is not None:
-        raise _lib.AldmError("conv: ln_parts without a LayerNorm-folded weight pack (pack_linear_ln)")
-    if rowstats:
-        if vt is not None or pw.geglu or out_f32 or out2 is not None or pw.N % 64 or gn is not None or defer:
-            raise _lib.AldmError("conv: rowstats needs the standard bf16 epilogue and N % 64 == 0")
-        if splits is None:
-            splits = 1                                   # the statistics come out of the (single) epilogue
-    if rowbias is not None:
-        assert rowbias.dtype == torch.float32
-        a.rowbias, a.rowbias_ld = rowbias.data_ptr(), rowbias_ld
-    a.geglu = 1 if pw.geglu else 0
-    a.out_act, a.out_slope = out_act, out_slope
-    a.res = res.data_ptr() if res is not None else None
-    a.res2 = res2.data_ptr() if res2 is not None else None
-    a.alpha = alpha
-    a.post_act, a.post_slope = post_act, post_slope
-    a.out2 = out2.data_ptr() if out2 is not None else None
-    a.out, a.out_dtype, a.out_ld = out.data_ptr(), (OUT_F32 if out.dtype == torch.float32 else OUT_BF16), out_ld
-    a.out_batch_stride = out_batch_stride
-    a.out_pix_stride, a.out_pix_offset = out_pix_stride, out_pix_offset
-    if vt is not None:
-        a.vt, a.vt_col0, a.vt_ld, a.vt_batch_stride = vt.data_ptr(), vt_col0, vt_ld, vt_batch_stride
-        a.vt_dual = 1 if vt_dual else 0
-    M = B * OH * OW
-    ktiles = pw.Kpad // BK
-    can_split = not (vt is not None or pw.N % 4 or pw.ln_s is not None)
-    gn_defer = ((gn is not None or defer) and can_split and not pw.geglu and res2 is None and out2 is None
-                and out_act == ACT_NONE and post_act == ACT_NONE and alpha == 1.0 and out.dtype == torch.bfloat16
-                and out_ld == pw.N and out_pix_stride == 1)
-    if gn_defer and gn is not None:
-        gn_defer = pw.N % gn[2] == 0 and (pw.N // gn[2]) % 4 == 0 and OH * OW * (pw.N // gn[2] // 4) <= 4096
-    elif gn_defer:                                         # defer = (channels, groups) of the consuming norm (it may append a skip tensor)
-        ct, ng = defer if isinstance(defer, tuple) else (pw.N, 32)
-        cg = ct // ng
-        gn_defer = ct % ng == 0 and cg % 4 == 0 and pw.N % cg == 0 and OH * OW * (cg // 4) <= 4096
-    fast_path = not (pw.Cin % 64 or (x2 is not None and x2.shape[3] % 64) or in_act)
-    tuning = False
-    key = None
-    if tile == 0 and ring == 0:
-        # launch configuration: the measured table (tuned_gfx950.json, written by tools/autotune.py) where it has this
-        # GEMM, else the heuristics below.  A caller-fixed split count stays fixed (it is part of the key).
-        sfx = (("" if splits is None else f" sp{splits}") + (" gn" if gn_defer else "") + (" rs" if rowstats else "")
-               + (" lp" if ln_parts is not None else "") + (f" e{C3}+{C4}" if x3 is not None else "") + (" vd" if vt_dual else "")
-               + (" gi" if gn_in is not None else ""))
-        key = tune_key(M, pw.N, C1, C2, KH, KW, stride, up_size is not None, in_dilate, pw.Rp, vt is not None, pw.geglu,
-                       pw.ln_s is not None, fast_path, OW, pad, dil) + sfx
-        halo = halo_tiles(OW, KH == 3 and KW == 3 and stride == (1, 1) and pad == (1, 1) and dil == (1, 1) and fast_path
-                          and not in_dilate and not pw.Rp and vt is None and not pw.geglu and pw.ln_s is None)   # (any nearest up-sampling size)
-        if (KH == 1 and IH == 1 and KW % 2 == 1 and KW > 1 and stride == (1, 1) and pad == (0, (KW - 1) * dil[1] // 2) and dil[0] == 1 and fast_path
-                and not in_dilate and not pw.Rp and vt is None and not pw.geglu and pw.ln_s is None and up_size is None and x3 is None and gn_in is None):
-            # conv1d (the vocoder): the wave-specialised halo tiles read it as a KW x 1 filter over a T x 1 image (csrc/igemm_halo.hip)
-            halo = [t for t in (15, 16) if TILE_DIMS[t][0] + (KW - 1) * dil[1] <= HALO_ROWS[t]]
-        if x3 is not None:      # conv2 + conv_shortcut as one GEMM: the wave-specialised halo tiles only, three-pass halo, no up-sampling
-            halo = [t for t in halo if t in (15, 16) and up_size is None and C3 % 64 == 0 and C4 % 64 == 0
-                    and (TILE_DIMS[t][0] // OW + 2) * (OW + 2) <= (192 if t == 15 else 128)]
-        cfg = TUNED.get(key)
-        if cfg is None and TUNED_LEGACY_KEYS:           # tables written before the geometry suffix existed
-            cfg = TUNED.get(tune_key(M, pw.N, C1, C2, KH, KW, stride, up_size is not None, in_dilate, pw.Rp, vt is not None,
-                                     pw.geglu, pw.ln_s is not None, fast_path) + sfx)
-        if cfg is not None and cfg[0] in HALO_ROWS and cfg[0] not in halo:
-            if os.environ.get("ALDM_VERBOSE_TUNED") == "1":
-                print(f"[ops] table entry {cfg} of '{key}' names a halo tile this geometry cannot take: heuristics instead", file=sys.stderr)
-            cfg = None                                  # never trust a table entry into a tile this geometry cannot take
-        tuning = TUNER is not None and not torch.cuda.is_current_stream_capturing()
-        if tuning:
-            cfg = TUNER.choose(key, a, M, pw, ktiles, can_split and splits is None, splits, fast_path, vt is not None, x.device, halo)
-        if cfg is not None:
-            tile, ring, splits = cfg
-            if x3 is not None and tile in HALO_ROWS:
-                ring = 3                                    # (the fused-shortcut form of the halo tiles has one ring depth)
-    if gn_in is not None:
-        # GroupNorm of the input inside the launch: halo tiles only (the tile is normalised once in LDS); statistics from the producers
-        q1, q2 = getattr(x, "qstats", None), (getattr(x2, "qstats", None) if x2 is not None else None)
-        if not gn_in_ok(x, x2, pw, stride, pad, dil, up_size, x3):
-            raise _lib.AldmError("conv: gn_in needs a 3x3 / stride 1 / pad 1 launch that fits a halo tile and inputs with .qstats (gn_in_ok)")
-        if tile not in HALO_ROWS:
-            tile, ring = (15 if (128 % OW == 0 and (128 // OW + 2) * (OW + 2) <= HALO_ROWS[15]) else 16), GNIN_RING   # the loader waves normalise
-        splits = 1
-        gm_, bt_, a.gnin_groups, a.gnin_eps, a.gnin_act = gn_in
-        a.gnin_gamma, a.gnin_beta = gm_.data_ptr(), bt_.data_ptr()
-        a.gnin_q1, a.gnin_bm1, a.gnin_tpi1 = q1.table.data_ptr(), q1.bm, q1.tpi
-        if q2 is not None:
-            a.gnin_q2, a.gnin_bm2, a.gnin_tpi2 = q2.table.data_ptr(), q2.bm, q2.tpi
-    if splits is None:
-        splits = auto_splits(M, pw.N, ktiles) if (can_split and tile not in HALO_ROWS) else 1
-    if tile == 0:
-        tile = heuristic_cfg(M, pw, ktiles, can_split, fast_path, vt is not None, splits)[0]
-    if not ring:
-        bm, bn = TILE_DIMS[tile]
-        ring = pick_ring(tile, bm, bn, pw.Rp, math.ceil(M / bm) * math.ceil(pw.N / bn) * max(1, splits), ktiles)
-    qs = None
-    if (qstats and splits == 1 and vt is None and not pw.geglu and not out_f32 and out2 is None and out_pix_stride == 1
-            and not pw.Rp and pw.ln_s is None and not rowstats
-            and pw.N % 8 == 0 and pw.N % TILE_DIMS[tile][1] == 0 and out_ld == pw.N and OH * OW >= QSTATS_MIN_HW):
-        bm = TILE_DIMS[tile][0]
-        if tile in HALO_ROWS:
-            tpi = math.ceil(OH / (bm // OW))
-            qs = QStats(torch.empty(B * tpi, 2, pw.N // 4, 2, dtype=torch.float32, device=x.device), 0, tpi)
-        elif OH * OW >= bm:
-            qs = QStats(torch.empty(math.ceil(M / bm), 2, pw.N // 4, 2, dtype=torch.float32, device=x.device), bm, 0)
-        if qs is not None:
-            a.qstat_out = qs.table.data_ptr()
-    stats = None
-    if rowstats:
-        if tile in HALO_ROWS or pw.N % TILE_DIMS[tile][1] or splits != 1:
-            tile, splits = _lib.TILE_64x64, 1             # always legal: N % 64 == 0 was checked above
-            ring = pick_ring(tile, 64, 64, pw.Rp, math.ceil(M / 64) * (pw.N // 64), ktiles)
-        stats = torch.empty(M, pw.N // TILE_DIMS[tile][1], 2, dtype=torch.float32, device=x.device)
+    key, tile, ring, splits, gn_defer = p.key, p.tile, p.ring, p.splits, p.gn_defer
+    # ---- the argument struct: operands, then what the plan decided
+    a = fill()
+    a.tile, a.ring, a.splits = tile, ring, splits
+    a.xcd_map = XCD_MAP | (EPI_FORM if epi is None else epi)
+    qs = stats = None
+    if p.qstats is not None:
+        rows, bm, tpi = p.qstats
+        qs = QStats(torch.empty(rows, 2, pw.N // 4, 2, dtype=torch.float32, device=x.device), bm, tpi)
+        a.qstat_out = qs.table.data_ptr()
+    if p.rowstats_cols is not None:
+        stats = torch.empty(M, p.rowstats_cols, 2, dtype=torch.float32, device=x.device)
         a.rowstat_out = stats.data_ptr()
-    a.splits = splits
     if splits > 1:
         a.workspace = _workspace(splits * M * pw.N * 4, x.device).data_ptr()
-    a.tile = tile
-    a.ring = ring
-    a.xcd_map = XCD_MAP | (EPI_FORM if epi is None else epi)
     lib = _lib.load()
     eff = lib.aldm_igemm_effective_splits(C.byref(a)) if (gn_defer and splits > 1) else 1
     layout = _lib.SLAB_ROWMAJOR
@@ -774,7 +650,8 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
                        | (_lib.DEFER_WRITE_THROUGH if (SLAB_WT if slab_wt is None else slab_wt) else 0)) if eff > 1 else 0)
     if EPI_TRACE is not None:
         EPI_TRACE.append(lib.aldm_igemm_epilogue_form(C.byref(a)))
-    ktot = KH * KW * pw.Cin + pw.Cext
+    ncols = vt_col0 if (vt is not None and not vt_dual) else (pw.N // 2 if pw.geglu else pw.N)
+    ktot = pw.KH * pw.KW * pw.Cin + pw.Cext
     flops = 2.0 * M * pw.N * ktot + (2.0 * M * pw.Rp * (ktot + pw.N) if pw.Rp else 0.0)
     nbytes = 2.0 * (B * IH * IW * pw.Cin + M * pw.Cext + pw.N * ktot + M * ncols)
     label = (f"igemm_{TILE_NAMES[tile]}_r{pw.Rp}{'_vt' if vt is not None else ''}{'_sk' if splits > 1 else ''}"
@@ -804,6 +681,7 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
             groups, eps, _p(gamma), _p(beta), act, _p(y), layout, _stream())), "aldm_groupnorm_partials")
         return (out, y) if gn_keep else y
 
+    # ---- launch and finish
     if tuning and TUNER.slot is not None:                      # stage 2 of the tuner: time this launch in context
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -821,7 +699,7 @@ def conv(x: torch.Tensor, pw: PackedW, *, x2: Optional[torch.Tensor] = None, str
 
 # ---- the transformer blocks' projection GEMMs (csrc/pgemm.hip) ---------------------------------------------------------------
 PGEMM = os.environ.get("ALDM_NO_PGEMM") != "1"
-PGEMM_K = (256, 384, 640)
+PGEMM_K = igemm_plan.PGEMM_K
 PGEMM_CFG = {}                                               # (M, N, K, kind) -> (mi, nt, tiles_per_range): tools/tune_pgemm.py
 PGEMM_TUNED_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "pgemm_gfx950.json")
 if os.path.exists(PGEMM_TUNED_PATH) and os.environ.get("ALDM_NO_TUNED") != "1":
@@ -839,13 +717,11 @@ if os.environ.get("ALDM_PGEMM_PATCH"):                        # A/B aid: {"M|N|K
                 PGEMM_CFG.pop((int(_m), int(_n), int(_kk), _kind), None)
             else:
                 PGEMM_CFG[(int(_m), int(_n), int(_kk), _kind)] = tuple(_v)
-PGEMM_USE_IGEMM = (0, 0, 0, 0)                               # table entry: this GEMM measured faster on aldm_igemm, keep it there
+PGEMM_USE_IGEMM = igemm_plan.PGEMM_USE_IGEMM                 # table entry: this GEMM measured faster on aldm_igemm, keep it there
 
 
 def _pgemm_key(M, pw, K, res, vt, rowstats=False, lora_t=False, dual=False):
-    kind = (("g" if pw.geglu else "") + ("v" if vt is not None else "") + ("r" if res is not None else "") + (f"l{pw.Rp}" if pw.Rp else "")
-            + ("s" if rowstats else "") + ("t" if lora_t else "") + ("d" if dual else ""))
-    return (M, pw.N, K, kind)
+    return igemm_plan.pgemm_key(M, pw.N, K, pw.geglu, vt is not None, res is not None, pw.Rp, rowstats, lora_t, dual)
 
 
 def _pgemm(x, pw, out, out_ld, M, K, OHW, res, vt, vt_col0, vt_ld, vt_bs, rowstats, ln_parts, lora_t_out=None, vt_dual=False, lora_gate=None):
@@ -956,26 +832,15 @@ def groupnorm(x, gamma, beta, groups, eps, act=ACT_NONE, x2=None):
     return y
 
 
-GNIN_RING = int(os.environ.get("ALDM_GNIN_RING", "0"))     # LDS-DMA ring depth of the input-norm-folding halo launches (0: pick_ring); tuning aid
-
-
 def gn_in_ok(x, x2, pw, stride=(1, 1), pad=(1, 1), dil=(1, 1), up_size=None, x3=None):
-    """Can a convolution apply the GroupNorm of its input itself (conv(gn_in=))?  3x3 / stride 1 / pad 1 on a halo tile, every source a
-    raw convolution output with its statistics table, channel counts multiples of 64, at most 512 input channels."""
-    if not isinstance(x, torch.Tensor) or getattr(x, "qstats", None) is None or x.dim() != 4:
+    """Can a convolution apply the GroupNorm of its input itself (conv(gn_in=))?  Every source a raw convolution output with its statistics
+    table, and the launch one a halo tile takes in its gn_in form (igemm_plan.halo_candidates: 3x3 / stride 1 / pad 1, channel counts
+    multiples of 64, at most 512 input channels)."""
+    if not _has_qstats(x, x2):
         return False
-    if x2 is not None and (not isinstance(x2, torch.Tensor) or getattr(x2, "qstats", None) is None):
-        return False
-    B, IH, IW, C1 = x.shape
     C2 = x2.shape[3] if x2 is not None else 0
-    hw = IH * IW
-    for q in (x.qstats, x2.qstats if x2 is not None else None):
-        if q is not None and not (q.tpi > 0 or q.bm <= hw):
-            return False
-    fits = any(bm % IW == 0 and (bm // IW + 2) * (IW + 2) <= HALO_ROWS[t] for t, bm in ((7, 128), (8, 64)))
-    return (pw.KH == 3 and pw.KW == 3 and tuple(stride) == (1, 1) and tuple(pad) == (1, 1) and tuple(dil) == (1, 1) and up_size is None
-            and x3 is None and not pw.Rp and not pw.geglu and pw.ln_s is None and C1 % 64 == 0 and C2 % 64 == 0 and C1 + C2 <= 512
-            and pw.Cin == C1 + C2 and fits)
+    return bool(halo_candidates(igemm_plan.geometry(tuple(x.shape), pw, C2=C2, x3=x3 is not None, stride=stride, pad=pad, dil=dil,
+                                                    up_size=up_size, gn_in=True)))
 
 
 def gn_silu_conv_out_ok(x, pw, groups):

@@ -269,7 +269,7 @@ def test_unfused_chain_launches(ops, C, K):
         for d in (1, 3, 5):
             tiles = [0]
             if C == 128:                                           # ops.conv's conv1d halo rule: the wave-specialised halo tiles where the run fits their LDS rows
-                tiles += [tl for tl in (15, 16) if ops.TILE_DIMS[tl][0] + (K - 1) * d <= ops.HALO_ROWS[tl]]
+                tiles += ops.halo_candidates(ops.igemm_plan.geometry((B, 1, T, C), c1, pad=(0, (K * d - d) // 2), dil=(1, d)))
                 assert tiles == [0, 15, 16]
             else:
                 assert C % 64 != 0                                 # the generic gather: no halo tile, no LDS-DMA

@@ -8,7 +8,7 @@ launches) goes to an overlay JSON that ALDM_TUNED_PATCH or a merge into tuned_gf
 
 usage: python tools/ab_overlay.py out.json [small|big|all] [infer|train]     (train: config 3's LoRA step, batch 8, rank 8; per-key times
 from hipEvent pairs of an eager step queued behind a sleep kernel, totals from the replayed graph)"""
-import json, os, re, sys, torch
+import json, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from audioldm_with_lora_amd import ops
@@ -25,20 +25,19 @@ BASE = dict(ops.TUNED)
 USED = {}
 
 
-def key_m(key):
-    return int(re.match(r"M(\d+) ", key).group(1))
-
-
 def eligible(key):
-    if not re.match(r"M(\d+) N(\d+) ", key) or any(t not in key for t in (" f1", " r0 ", " vt0 ", " g0 ", " ln0 ")):
+    p = ops.parse_key(key)                                  # None: no igemm key (the "pg:" rows of KEYLOG)
+    if p is None or not p[0].fast_path or p[0].Rp or p[0].vt or p[0].geglu or p[0].ln:
         return False
-    if family == "halo" and " gi" in key and " d0 " in key:
+    g = p[0]
+    if family == "halo" and g.gn_in and not g.in_dilate:
         return True                                         # GroupNorm-of-the-input launches: halo tiles only, never split
-    conv1d = family == "halo" and re.search(r" k1x(3|5|7|11) s1 up0 d0 ", key) is not None
-    if any(t in key for t in (" gi", " lp", " rs", " vd")) or (family != "all" and " k3x3 s1 " not in key and not conv1d) or (family == "halo" and " d0 " not in key):
+    conv1d = family == "halo" and g.conv1d and g.KW in (3, 5, 7, 11) and g.stride == (1, 1) and g.up_size is None and not g.in_dilate
+    k3x3 = g.KH == 3 and g.KW == 3 and g.stride == (1, 1)
+    if (g.gn_in or g.ln_parts is not None or g.rowstats or g.vt_dual or (family != "all" and not k3x3 and not conv1d)
+            or (family == "halo" and g.in_dilate)):
         return False
-    M = key_m(key)
-    return (256 <= M <= 8192) if family == "small" else M > 8192 if family == "big" else M >= 256
+    return (256 <= g.M <= 8192) if family == "small" else g.M > 8192 if family == "big" else g.M >= 256
 
 
 def measure_train(overlay, total=False):
@@ -171,35 +170,32 @@ keys = [k for k in base_keys if eligible(k)]
 print(f"base: kernel time {base_tot:.1f} us, span {base_span:.1f} us; {len(keys)} eligible keys", flush=True)
 variants = {"base": (base_keys, {})}
 base_used = dict(USED)
-SMALL = [("64x128ws r3", 13, 3, 1), ("128x64ws r3", 14, 3, 1), ("128x64ws r4", 14, 4, 1), ("64x128ws r3 /2", 13, 3, 2), ("128x64ws r3 /2", 14, 3, 2),
-         ("128x64ws r4 /2", 14, 4, 2)]
-BIG = [("256x128ws", 12, 3, 1), ("64x128ws r3", 13, 3, 1), ("128x64ws r3", 14, 3, 1)]
+T = ops._lib
+SMALL = [("64x128ws r3", T.TILE_64x128_WS, 3, 1), ("128x64ws r3", T.TILE_128x64_WS, 3, 1), ("128x64ws r4", T.TILE_128x64_WS, 4, 1),
+         ("64x128ws r3 /2", T.TILE_64x128_WS, 3, 2), ("128x64ws r3 /2", T.TILE_128x64_WS, 3, 2), ("128x64ws r4 /2", T.TILE_128x64_WS, 4, 2)]
+BIG = [("256x128ws", T.TILE_256x128_WS, 3, 1), ("64x128ws r3", T.TILE_64x128_WS, 3, 1), ("128x64ws r3", T.TILE_128x64_WS, 3, 1)]
 # the halo tiles with split-K by channel chunk: the key's current split count, half of it, twice it
-HALO = [(f"{n}{sfx}", t, 3, d) for n, t in (("halo128ws", 15), ("halo64ws", 16), ("halo128", 7), ("halo64", 8))
-        for sfx, d in (("", 1), (" /2", 2), (" x2", 0.5), (" 1", 1000))] + [("halo128ws r4", 15, 4, 1), ("halo64ws r4", 16, 4, 1)]
-rules = SMALL if family == "small" else BIG if family == "big" else HALO if family == "halo" else SMALL + [("256x128ws", 12, 3, 1)]
+HALO = [(f"{n}{sfx}", t, 3, d) for n, t in (("halo128ws", T.TILE_HALO_128x128_WS), ("halo64ws", T.TILE_HALO_64x128_WS),
+                                            ("halo128", T.TILE_HALO_128x128), ("halo64", T.TILE_HALO_64x128))
+        for sfx, d in (("", 1), (" /2", 2), (" x2", 0.5), (" 1", 1000))] + [("halo128ws r4", T.TILE_HALO_128x128_WS, 4, 1),
+                                                                            ("halo64ws r4", T.TILE_HALO_64x128_WS, 4, 1)]
+rules = SMALL if family == "small" else BIG if family == "big" else HALO if family == "halo" else SMALL + [("256x128ws", T.TILE_256x128_WS, 3, 1)]
 for name, tile, ring, spdiv in rules:
     ov = {}
     for k in keys:
         sp = base_used[k][2]
-        if tile in (7, 8, 15, 16):
-            ow = int(re.search(r" ow(\d+)", k).group(1))
-            m1 = re.search(r" k1x(\d+) s1 .* dl1x(\d+)", k)
-            if m1:                                              # conv1d: the wave-specialised halo tiles, halo = BM + (K - 1) dil rows
-                if tile not in (15, 16) or ops.TILE_DIMS[tile][0] + (int(m1.group(1)) - 1) * int(m1.group(2)) > ops.HALO_ROWS[tile]:
-                    continue
-            elif tile not in ops.halo_tiles(ow, True):
+        g = ops.parse_key(k)[0]
+        if ops.TILES[tile].halo:
+            # the one halo rule (3x3, conv1d, fused shortcut, gn_in); the fused-shortcut form runs with one ring depth
+            if tile not in ops.halo_candidates(g) or (g.x3 and ring != ops.igemm_plan.FUSED_HALO_RING):
                 continue
-            if re.search(r" e\d+\+\d+", k):                # conv2 + conv_shortcut: wave-specialised halo tiles, three-pass halo, ring 3
-                if tile not in (15, 16) or ring != 3 or " up0 " not in k or (tile == 15 and (128 // ow + 2) * (ow + 2) > 192):
-                    continue
-            nch = sum(int(v) for v in re.search(r" C(\d+)\+(\d+) ", k).groups()) // 64
-            nsp = 1 if " gi" in k else max(1, min(nch, int(round(sp / spdiv))))
+            nch = (g.C1 + g.C2) // 64
+            nsp = 1 if g.gn_in else max(1, min(nch, int(round(sp / spdiv))))
             if (nsp == sp and spdiv != 1) or (tile, ring, nsp) == tuple(base_used[k]):
                 continue
             ov[k] = (tile, ring, nsp)
             continue
-        if (spdiv > 1 and sp < 2 * spdiv) or (tile == 12 and key_m(k) <= 8192):
+        if (spdiv > 1 and sp < 2 * spdiv) or (tile == T.TILE_256x128_WS and g.M <= 8192):
             continue
         ov[k] = (tile, ring, max(1, sp // spdiv))
     if not ov:
