@@ -101,7 +101,10 @@ __global__ __launch_bounds__(256) void clap_log_mel_kernel(const float* __restri
     }
     acc += __shfl_xor(acc, 1, 64);
     acc += __shfl_xor(acc, 2, 64);
-    if (m < n_mels && part == 0) orow[m] = 10.f * log10f(fmaxf(acc, 1e-10f));
+    // the logarithm alone runs in double (64 values per frame) and is rounded once, as the extractor's float64 spectrogram cast to
+    // float32 is: the device's log10f is good to ~2 ulp, which at 20 - 30 dB is 4x the fp32 FFT's error in the mel power, and it puts
+    // the clamp at -100.00001 dB instead of -100
+    if (m < n_mels && part == 0) orow[m] = (float)(10.0 * log10((double)fmaxf(acc, 1e-10f)));
   }
 }
 

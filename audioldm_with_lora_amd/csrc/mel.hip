@@ -7,7 +7,7 @@
 //
 // One 256-thread workgroup per frame.  The 1024-point transform is a radix-4 Stockham autosort FFT held entirely in LDS
 // (5 passes, one butterfly per thread per pass, ping-pong float2 images, twiddles exp(-2 pi i k / 1024) tabulated once
-// per workgroup with sincospif); fp32 throughout, as torch.stft is.  The mel projection uses each filter's non-zero
+// per workgroup with sincospif); fp32 throughout, as torch.stft is (the final logarithm alone in double).  The mel projection uses each filter's non-zero
 // bin range (triangles are <= 46 bins wide), four lanes per filter.  HBM traffic is the 4 KB of samples per frame
 // (overlapping hops hit L2) and 256 B of output: the kernel is latency / LDS bound, not an MFMA candidate.
 #include "common.h"
@@ -78,7 +78,9 @@ __global__ __launch_bounds__(256) void log_mel_kernel(const float* __restrict__ 
     }
     acc += __shfl_xor(acc, 1, 64);
     acc += __shfl_xor(acc, 2, 64);
-    if (m < n_mels && part == 0) orow[m] = logf(fmaxf(acc, clamp_min));
+    // the logarithm alone runs in double and is rounded once: a silent bin is then the float32 nearest to log(clamp_min), bit for bit
+    // what torch.log gives the reference (the device's logf is 1.6 ulp off there)
+    if (m < n_mels && part == 0) orow[m] = (float)log((double)fmaxf(acc, clamp_min));
   }
 }
 

@@ -20,6 +20,11 @@ TEXT = dict(vocab_size=200, hidden_size=64, num_hidden_layers=2, num_attention_h
 PROMPT_IDS = [0, 17, 45, 99, 3, 150, 2]
 CLIP_SECONDS = [4.0, 10.0, 2.5, 7.0]
 SEEDS = {"fused": 11, "unfused": 12, "narrow": 13, "text": 14}
+# tests/golden/clap_audio_mixed.npz: a batch of three for the narrow fused tower whose four mel channels per item come from four
+# different clips (seconds, wave16k seed), item 1 not "longer" -- the two arms the front end's own output never reaches
+MIXED_CLIPS = [(3.0, 20), (5.5, 21), (8.0, 22), (10.0, 23), (2.0, 24), (4.5, 25), (6.0, 26), (9.0, 27), (1.5, 28), (7.5, 29), (3.5, 30),
+               (10.0, 31)]
+MIXED_LONGER = [True, False, True]
 
 
 def _fill(template, seed, bn_input=None):

@@ -7,6 +7,11 @@ clip; the fused and unfused input_features of clip 0 (one channel); is_longer; t
 for the first 512 tokens of clip 0.  Also the resample_poly output of a short clip and the CLAP text embedding of PROMPT_IDS
 under the tiny text tower of the recipe.
 Run:  python tests/golden/make_golden_clap_audio.py
+
+With --mixed it writes tests/golden/clap_audio_mixed.npz instead: the narrow fused tower on a batch of three whose four mel channels per
+item are the extractor's spectrograms of four DIFFERENT clips (clap_audio_weights.MIXED_CLIPS) with is_longer = [True, False, True].
+Stored are the clips' (seconds, seed) pairs, is_longer, audio_embeds and pooler_output; the features are rebuilt from the seeds.
+Run:  python tests/golden/make_golden_clap_audio.py --mixed
 """
 import os
 import sys
@@ -67,8 +72,32 @@ def build():
     return out
 
 
+def build_mixed():
+    from scipy.signal import resample_poly
+    from transformers import ClapAudioConfig, ClapAudioModelWithProjection, ClapFeatureExtractor
+    import clap_audio_weights as W
+    torch.manual_seed(0)
+    cfg = ClapAudioConfig(**W.audio_config("narrow"))
+    m = ClapAudioModelWithProjection(cfg).eval()
+    m.load_state_dict(W.audio_state_dict("narrow"), strict=True)
+    fe = ClapFeatureExtractor(truncation="fusion")
+    chans = []
+    for seconds, seed in W.MIXED_CLIPS:
+        np.random.seed(0)
+        f = fe(resample_poly(W.wave16k(seconds, seed), 3, 1).astype(np.float32), sampling_rate=48000, return_tensors="pt")
+        chans.append(f["input_features"].float()[0, 0])                     # a clip of <= 10 s: four identical channels
+    feats = torch.stack(chans).reshape(len(W.MIXED_LONGER), 4, 1001, 64)
+    longer = torch.tensor(W.MIXED_LONGER)[:, None]
+    with torch.no_grad():
+        o = m(input_features=feats, is_longer=longer)
+        po = m.audio_model(input_features=feats, is_longer=longer).pooler_output
+    return {"clips": np.array(W.MIXED_CLIPS, dtype=np.float64), "is_longer": np.array(W.MIXED_LONGER),
+            "audio_embeds": o.audio_embeds.numpy(), "pooler_output": po.numpy()}
+
+
 if __name__ == "__main__":
-    data = build()
-    path = os.path.join(HERE, "clap_audio.npz")
+    mixed = "--mixed" in sys.argv[1:]
+    data = build_mixed() if mixed else build()
+    path = os.path.join(HERE, "clap_audio_mixed.npz" if mixed else "clap_audio.npz")
     np.savez_compressed(path, **data)
     print(path, os.path.getsize(path), "bytes")

@@ -11,6 +11,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 GOLDEN = os.path.join(HERE, "golden", "clap_audio.npz")
+GOLDEN_MIXED = os.path.join(HERE, "golden", "clap_audio_mixed.npz")
 
 
 def test_fixture_exists_and_is_small():
@@ -30,6 +31,14 @@ def test_fixture_regenerates_from_transformers():
             np.testing.assert_array_equal(new[k], old[k], err_msg=k)
         else:
             np.testing.assert_allclose(new[k], old[k], rtol=1e-4, atol=1e-4, err_msg=k)
+    new, old = mk.build_mixed(), np.load(GOLDEN_MIXED)
+    assert sorted(new) == sorted(old.files) and os.path.getsize(GOLDEN_MIXED) < 1024 * 1024
+    for k in old.files:
+        if old[k].dtype.kind in "bi":
+            np.testing.assert_array_equal(new[k], old[k], err_msg=k)
+        else:
+            np.testing.assert_allclose(new[k], old[k], rtol=1e-4, atol=1e-4, err_msg=k)
+    assert old["is_longer"].tolist() == [True, False, True] and old["audio_embeds"].shape == (3, 512)
 
 
 @pytest.mark.parametrize("norm,scale,fmin,fmax", [(None, "htk", 0, 14000), ("slaney", "slaney", 0, 14000), (None, "htk", 50, 12000)])
