@@ -62,6 +62,23 @@ class IgemmArgs(C.Structure):
     ]
 
 
+class IgemmVariant(C.Structure):
+    """Mirror of aldm_igemm_variant_t: the kernel aldm_igemm would run (aldm_igemm_variant; no GPU needed)."""
+    _fields_ = [(n, C.c_int) for n in ("family", "tile", "bm", "bn", "wm", "wn", "rp", "vt", "gate", "ring", "epi", "nl", "rs", "hp", "gnin",
+                                       "ext", "transposed", "splits", "kt_per_split", "direct", "tiles_m", "tiles_n")] + \
+               [("grid", C.c_uint), ("block", C.c_uint), ("lds", C.c_uint), ("name", C.c_char * 192)]
+
+
+class IgemmTileInfo(C.Structure):
+    """Mirror of aldm_igemm_tile_info_t: one row of the library's tile table (aldm_igemm_tile_info)."""
+    _fields_ = [("tile", C.c_int), ("kind", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("wm", C.c_int), ("wn", C.c_int), ("blocks", C.c_int),
+                ("rings", C.c_uint), ("ring", C.c_int), ("ring_lora", C.c_int), ("halo_rows", C.c_int), ("halo_rows_fused", C.c_int)]
+
+
+IGEMM_TILE_KINDS = ("w4", "w8", "ws", "halo", "halo-ws")              # ALDM_IGEMM_KIND_*, as igemm_plan.Tile.kind spells them
+IGEMM_FAMILIES = ("igemm_kernel", "igemm_pipe_kernel", "igemm_ws_kernel", "igemm_halo_kernel", "igemm_halo_ws_kernel")   # ALDM_IGEMM_*
+
+
 class PgemmArgs(C.Structure):
     """Mirror of aldm_pgemm_t (include/aldm_hip.h) -- field order and types must match exactly."""
     _fields_ = [
@@ -103,6 +120,8 @@ PROTOTYPES = {
     "aldm_igemm_workspace_bytes": (C.c_size_t, [C.POINTER(IgemmArgs)]),
     "aldm_igemm_effective_splits": (C.c_int, [C.POINTER(IgemmArgs)]),
     "aldm_igemm_epilogue_form": (C.c_int, [C.POINTER(IgemmArgs)]),
+    "aldm_igemm_variant": (C.c_int, [C.POINTER(IgemmArgs), C.POINTER(IgemmVariant)]),
+    "aldm_igemm_tile_info": (C.c_int, [C.c_int, C.POINTER(IgemmTileInfo)]),
     "aldm_pgemm_supported": (C.c_int, [C.c_int]),
     "aldm_pgemm_plan": (C.c_int, [C.POINTER(PgemmArgs)]),
     "aldm_pgemm": (C.c_int, [C.POINTER(PgemmArgs), C.c_void_p]),

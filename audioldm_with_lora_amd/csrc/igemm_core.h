@@ -20,11 +20,9 @@
 #include <type_traits>
 
 #include "common.h"
+#include "igemm_select.h"
 
 namespace aldm_igemm_detail {
-
-constexpr int BK = 64;
-constexpr int THREADS = 256;
 
 // n / d for a runtime-constant d: q = (umulhi(n, mul) + n) >> shift  (round-up magic; exact for 0 <= n < 2^31).
 // A hardware integer division is ~50 instructions; the kernels divide by OH*OW and OW in their prologue AND epilogue.
@@ -1533,103 +1531,53 @@ static __global__ __launch_bounds__(256) void igemm_reduce_kernel(const IgemmDev
   }
 }
 
-// GATE: multi-adapter routing (igemm_gate4) as a compile-time variant of the Rp = 32 kernels -- the ungated instantiations are exactly
-// the kernels without it
-template <int BM, int BN, int WM, int WN, int RP, bool VT, int S, int EPI = 0, bool GATE = false>
-int launch_cfg(const IgemmDev& d, hipStream_t st) {
-  // S == 0: register-staged double buffer (needed when the gather applies an activation); else LDS-DMA ring
-  constexpr size_t lds_loop = (S == 0 ? 2 : S) * (size_t)(BM + BN + RP) * 128 + ((S != 0 && RP > 0) ? (size_t)BN * 128 : 0);
-  constexpr size_t lds = (lds_loop > (size_t)EpiCfg<BM, BN>::BYTES ? lds_loop : (size_t)EpiCfg<BM, BN>::BYTES) + 2 * BM * sizeof(float);
+// ---- from a selected variant (igemm_select.h) to its instantiation ----------------------------------------------------------------
+inline int igemm_not_instantiated() {
+  aldm_set_error("igemm: the selected kernel variant has no instantiation");
+  return ALDM_E_UNSUPPORTED;
+}
+// f(std::integral_constant<int, V>) for the V among Vs that equals v: the run-time value becomes a template argument
+template <int... Vs, class F>
+int with_constant(int v, F&& f) {
+  int rc = ALDM_E_UNSUPPORTED;
+  if (!(((v == Vs) && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...)) return igemm_not_instantiated();
+  return rc;
+}
+
+// one instantiation: its own LDS attribute state, then the launch as selected
+template <void (*KERN)(const IgemmDev)>
+int launch_variant(const aldm_igemm_variant_t& v, const IgemmDev& d, hipStream_t st, const char* what) {
   static unsigned long long attr_done = 0;   // per-device bit mask (aldm_set_max_lds); one-time, idempotent, races are benign
-  void (*kern)(const IgemmDev);
-  if constexpr (S == 0) kern = igemm_kernel<BM, BN, WM, WN, RP, VT, GATE>;
-  else kern = igemm_pipe_kernel<BM, BN, WM, WN, RP, VT, S, EPI, GATE>;
-  if (int rc = aldm_set_max_lds(reinterpret_cast<const void*>(kern), (int)lds, &attr_done, "igemm")) return rc;
-  if (d.qstat && !(EPI == 0 || EPI == 4)) {
-    aldm_set_error("igemm: qstat_out reached an epilogue instantiation without the statistics code (EPI %d)", EPI);
-    return ALDM_E_UNSUPPORTED;
-  }
-  if (d.qstat && d.N % BN != 0) {
-    aldm_set_error("igemm: qstat_out needs Cout %d to be a multiple of the tile width %d", d.N, BN);
-    return ALDM_E_ARG;
-  }
-  if (d.rowstat && d.N % BN != 0) {
-    aldm_set_error("igemm: rowstat_out needs Cout %d to be a multiple of the tile width %d", d.N, BN);
-    return ALDM_E_ARG;
-  }
-  if (VT && d.vt_col0 % BN != 0) {
-    aldm_set_error("igemm: vt_col0 %d must be a multiple of the tile width %d", d.vt_col0, BN);
-    return ALDM_E_ARG;
-  }
-  IgemmDev dd = d;
-  dd.tiles_n = cdiv(d.N, BN);
-  dd.fd_tiles_n = make_fastdiv((unsigned)dd.tiles_n);
-  dd.tiles_m = cdiv(d.M, BM);
-  dd.fd_tiles_m = make_fastdiv((unsigned)dd.tiles_m);
-  dd.fd_splits = make_fastdiv((unsigned)d.splits);
-  dd.nwg = dd.tiles_m * dd.tiles_n * d.splits;
-  dim3 grid(dd.nwg, 1, 1);
-  hipLaunchKernelGGL(kern, grid, dim3(S == 0 ? THREADS : 64 * WM * WN), lds, st, dd);
-  return aldm_launch_status("igemm");
+  if (int rc = aldm_set_max_lds(reinterpret_cast<const void*>(KERN), (int)v.lds, &attr_done, what)) return rc;
+  hipLaunchKernelGGL(KERN, dim3(v.grid), dim3(v.block), v.lds, st, d);
+  return aldm_launch_status(what);
 }
 
-template <int BM, int BN, int WM, int WN, int S>
-int launch_rp(const IgemmDev& d, int Rp, bool vt, hipStream_t st) {
-  if (vt) {
-    if constexpr (S != 0) {
-      if (d.splits <= 1 && !d.geglu && d.out_act == ALDM_ACT_NONE && d.post_act == ALDM_ACT_NONE) {   // LEAN V^T: no split / GEGLU / act code
-        if (Rp == 0) return launch_cfg<BM, BN, WM, WN, 0, true, S, 1>(d, st);
-        if (Rp == 32) return d.lora_gate ? launch_cfg<BM, BN, WM, WN, 32, true, S, 1, true>(d, st) : launch_cfg<BM, BN, WM, WN, 32, true, S, 1>(d, st);
-        return launch_cfg<BM, BN, WM, WN, 64, true, S, 1>(d, st);
-      }
-    }
-    if (Rp == 0) return launch_cfg<BM, BN, WM, WN, 0, true, S>(d, st);
-    if (Rp == 32) return d.lora_gate ? launch_cfg<BM, BN, WM, WN, 32, true, S, 0, true>(d, st) : launch_cfg<BM, BN, WM, WN, 32, true, S>(d, st);
-    return launch_cfg<BM, BN, WM, WN, 64, true, S>(d, st);
-  }
-  if constexpr (S != 0) {
-    if (d.splits > 1) {                                                   // split-K: only the partial-tile store is compiled in
-      if (Rp == 0) return launch_cfg<BM, BN, WM, WN, 0, false, S, 3>(d, st);
-      if (Rp == 32) return d.lora_gate ? launch_cfg<BM, BN, WM, WN, 32, false, S, 3, true>(d, st) : launch_cfg<BM, BN, WM, WN, 32, false, S, 3>(d, st);
-      return launch_cfg<BM, BN, WM, WN, 64, false, S, 3>(d, st);
-    }
-    if (Rp == 0 && d.geglu && d.splits <= 1 && !d.res && !d.res2 && !d.out_f32 && d.out_act == ALDM_ACT_NONE &&
-        d.post_act == ALDM_ACT_NONE && d.alpha == 1.f)
-      return launch_cfg<BM, BN, WM, WN, 0, false, S, 2>(d, st);          // GEGLU-only epilogue with a plain bf16 store
-    // the common case -- standard epilogue, no activation -- runs the LEAN instantiation (nothing else compiled in)
-    if (d.splits <= 1 && !d.geglu && d.out_act == ALDM_ACT_NONE && d.post_act == ALDM_ACT_NONE && !d.ln_s) {
-      if (Rp == 0 && d.qstat) return launch_cfg<BM, BN, WM, WN, 0, false, S, 4>(d, st);   // + GroupNorm statistics
-      if (Rp == 0) return launch_cfg<BM, BN, WM, WN, 0, false, S, 1>(d, st);
-      if (Rp == 32) return d.lora_gate ? launch_cfg<BM, BN, WM, WN, 32, false, S, 1, true>(d, st) : launch_cfg<BM, BN, WM, WN, 32, false, S, 1>(d, st);
-      return launch_cfg<BM, BN, WM, WN, 64, false, S, 1>(d, st);
-    }
-  }
-  if (Rp == 0) return launch_cfg<BM, BN, WM, WN, 0, false, S>(d, st);
-  if (Rp == 32) return d.lora_gate ? launch_cfg<BM, BN, WM, WN, 32, false, S, 0, true>(d, st) : launch_cfg<BM, BN, WM, WN, 32, false, S>(d, st);
-  return launch_cfg<BM, BN, WM, WN, 64, false, S>(d, st);
-}
-
-// S0 / SL = default ring depth without / with LoRA (the LoRA rows + B tile cost LDS; SL is chosen so that the
-// workgroups-per-CU count does not drop, which matters more than ring depth for the short-K projection GEMMs).
-// `ring` (2..4) overrides it (tuning: tools/bench_igemm.py --ring).
-template <int BM, int BN, int WM, int WN, int S0, int SL>
-int launch_tile(const IgemmDev& d, int Rp, bool vt, int ring, hipStream_t st) {
-  // LDS-DMA ring needs a scalar K cursor (64-channel K-tiles inside one tap of one source), no gather-side
-  // activation and < 2 GiB activations (32-bit buffer offsets, 0x80000000 = "padded tap").
-  const bool fast = d.in_act == ALDM_ACT_NONE && d.Cin % 64 == 0 && d.Cin2 % 64 == 0 && d.x_bytes < 0x80000000u &&
-                    d.x2_bytes < 0x80000000u;
-  if (!fast && (d.ln_s || d.x3)) {
-    aldm_set_error("igemm: the folded LayerNorm / the fused second-source segment need the LDS-DMA path (Cin %% 64 == 0, no gather activation)");
-    return ALDM_E_UNSUPPORTED;
-  }
-  if (!fast) return launch_rp<BM, BN, WM, WN, 0>(d, Rp, vt, st);
-  int S = ring ? ring : (Rp ? SL : S0);
-  // never ask for more than the 160 KiB of LDS a workgroup can own (ring + LoRA-B image + row statistics)
-  auto lds_need = [&](int s) { return (size_t)s * (BM + BN + Rp) * 128 + (Rp ? (size_t)BN * 128 : 0) + 2 * BM * sizeof(float); };
-  while (S > 2 && lds_need(S) > 160 * 1024) --S;
-  if (S == 2) return launch_rp<BM, BN, WM, WN, 2>(d, Rp, vt, st);
-  if (S == 3) return launch_rp<BM, BN, WM, WN, 3>(d, Rp, vt, st);
-  return launch_rp<BM, BN, WM, WN, 4>(d, Rp, vt, st);
+// The igemm_kernel / igemm_pipe_kernel instantiations of one tile: what its row of the table says it has.
+// GATE: multi-adapter routing (igemm_gate4) as a compile-time variant of the Rp = 32 kernels -- the ungated instantiations are exactly
+// the kernels without it.  EPI 2 / 4 exist without LoRA only, V^T with EPI 0 / 1 only, igemm_kernel (S == 0) has the one epilogue.
+template <int TILE>
+int launch_ring_tile(const aldm_igemm_variant_t& v, const IgemmDev& d, hipStream_t st) {
+  static constexpr IgemmTile T = *igemm_tile(TILE);
+  static_assert(EpiCfg<T.bm, T.bn>::BYTES == epi_image_bytes(T.bm, T.bn), "epilogue image");
+  return with_constant<0, 2, 3, 4>(v.ring, [&](auto s) {
+    return with_constant<0, 32, 64>(v.rp, [&](auto rp) {
+      return with_constant<0, 1, 2, 3, 4>(v.epi, [&](auto epi) {
+        return with_constant<0, 1>(v.vt, [&](auto vt) {
+          return with_constant<0, 1>(v.gate, [&](auto gate) {
+            constexpr int S = decltype(s)::value, RP = decltype(rp)::value, EPI = decltype(epi)::value;
+            constexpr bool VT = decltype(vt)::value != 0, GATE = decltype(gate)::value != 0;
+            constexpr bool ring_ok = S == 0 ? T.reg_staged && EPI == 0 : T.has_kernel_ring(S) && ((T.epis >> EPI) & 1u);
+            constexpr bool vt_ok = !VT || (T.vt && (EPI == 0 || (EPI == 1 && T.lean_vt)));
+            constexpr bool lora_ok = ((T.rps >> (RP / 32)) & 1u) && (!GATE || RP == 32) && (RP == 0 || (EPI != 2 && EPI != 4));
+            if constexpr (!(ring_ok && vt_ok && lora_ok)) return igemm_not_instantiated();
+            else if constexpr (S == 0) return launch_variant<igemm_kernel<T.bm, T.bn, T.wm, T.wn, RP, VT, GATE>>(v, d, st, "igemm");
+            else return launch_variant<igemm_pipe_kernel<T.bm, T.bn, T.wm, T.wn, RP, VT, S, EPI, GATE>>(v, d, st, "igemm");
+          });
+        });
+      });
+    });
+  });
 }
 
 }  // namespace aldm_igemm_detail

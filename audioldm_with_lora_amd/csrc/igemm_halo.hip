@@ -547,128 +547,38 @@ __global__ __launch_bounds__(768) void igemm_halo_ws_kernel(const IgemmDev p) {
 #endif
 }
 
-template <int BM, int BN, int WM, int WN, int HP, int S, int EPI, bool GNIN = false, bool WS = false, bool EXT = false>
-int launch_halo_v(const IgemmDev& d, hipStream_t st) {
-  static_assert(!EXT || WS, "the fused-shortcut form exists for the wave-specialised kernel only");
-  constexpr size_t lds_loop = (EXT ? 3 : 2) * (size_t)HP * 64 * 128 + (size_t)S * BN * 128 + (GNIN ? (1024 + 128) * sizeof(float) : 0);
-  constexpr size_t lds = lds_loop > (size_t)EpiCfg<BM, BN>::BYTES ? lds_loop : (size_t)EpiCfg<BM, BN>::BYTES;
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  static unsigned long long attr_done = 0;   // per-device bit mask (aldm_set_max_lds); one per instantiation (WS included)
-  void (*kern)(const IgemmDev);
-  if constexpr (EXT) kern = igemm_halo_ws_kernel<BM, BN, WM, WN, HP, S, EPI, false, true>;
-  else if constexpr (WS) kern = igemm_halo_ws_kernel<BM, BN, WM, WN, HP, S, EPI, GNIN>;
-  else kern = igemm_halo_kernel<BM, BN, WM, WN, HP, S, EPI, GNIN>;
-  if (int rc = aldm_set_max_lds(reinterpret_cast<const void*>(kern), (int)lds, &attr_done, "igemm_halo")) return rc;
-  const int rows_pt = BM / d.OW;
-  const int need = WS ? (rows_pt + (d.KH - 1) * d.dh) * (d.OW + (d.KW - 1) * d.dw) : (rows_pt + 2) * (d.OW + 2);
-  if (BM % d.OW != 0 || need > HP * 64) {
-    aldm_set_error("igemm_halo: image width %d / filter %dx%d does not fit the %dx%d halo tile (%d halo rows of %d)", d.OW, d.KH, d.KW, BM, BN, need, HP * 64);
-    return ALDM_E_UNSUPPORTED;
-  }
-  IgemmDev dd = d;
-  if (WS) dd.fd_kw = make_fastdiv((unsigned)(d.KH * d.KW));    // the wave-specialised kernel: kt_per_split / taps = chunks per split
-  dd.tiles_n = cdiv(d.N, BN);
-  dd.fd_tiles_n = make_fastdiv((unsigned)dd.tiles_n);
-  dd.fd_halo = make_fastdiv((unsigned)(WS ? d.OW + (d.KW - 1) * d.dw : d.OW + 2));
-  const int tpi = cdiv(d.OH, rows_pt);
-  dd.tiles_m = d.B * tpi * dd.tiles_n;                      // (split-K form) tiles per split: the divisor that peels the split off blockIdx.x
-  dd.fd_tiles_m = make_fastdiv((unsigned)dd.tiles_m);
-  dim3 grid(d.B * tpi * dd.tiles_n * (EPI == 3 ? d.splits : 1), 1, 1);
-  hipLaunchKernelGGL(kern, grid, dim3(WS ? 768 : 512), lds, st, dd);
-  return aldm_launch_status("igemm_halo");
+// The instantiations of one halo tile: its halo pass counts x its ring depths x the epilogue forms, GNIN with the lean epilogues
+// only; the fused-shortcut form (EXT) of the wave-specialised kernel at its one pass count and ring 3, without GNIN
+template <int TILE>
+int launch_halo_tile(const aldm_igemm_variant_t& v, const IgemmDev& d, hipStream_t st) {
+  static constexpr IgemmTile T = *igemm_tile(TILE);
+  constexpr bool WS = T.kind == HALO_WS;
+  return with_constant<2, 3, 5>(v.hp, [&](auto hp) {
+    return with_constant<2, 3, 4>(v.ring, [&](auto s) {
+      return with_constant<0, 1, 3, 4>(v.epi, [&](auto epi) {
+        return with_constant<0, 1>(v.gnin, [&](auto gnin) {
+          return with_constant<0, 1>(v.ext, [&](auto ext) {
+            constexpr int HP = decltype(hp)::value, S = decltype(s)::value, EPI = decltype(epi)::value;
+            constexpr bool GNIN = decltype(gnin)::value != 0, EXT = decltype(ext)::value != 0;
+            constexpr bool plain_ok = (HP == T.hp[0] || HP == T.hp[1]) && T.has_kernel_ring(S) && (!GNIN || EPI == 1 || EPI == 4);
+            constexpr bool ext_ok = WS && HP == T.hp_fused && S == 3 && !GNIN;
+            if constexpr (EXT ? ext_ok : plain_ok) {
+              static_assert(halo_lds_bytes(HP, S, T.bm, T.bn, GNIN, EXT) <= IGEMM_MAX_LDS, "LDS budget");
+              if constexpr (WS) return launch_variant<igemm_halo_ws_kernel<T.bm, T.bn, T.wm, T.wn, HP, S, EPI, GNIN, EXT>>(v, d, st, "igemm_halo");
+              else return launch_variant<igemm_halo_kernel<T.bm, T.bn, T.wm, T.wn, HP, S, EPI, GNIN>>(v, d, st, "igemm_halo");
+            } else {
+              return igemm_not_instantiated();
+            }
+          });
+        });
+      });
+    });
+  });
 }
 
-template <int BM, int BN, int WM, int WN, int HP, int S>
-int launch_halo_ext(const IgemmDev& d, hipStream_t st) {     // conv2 + conv_shortcut as one GEMM (x3 | x4 segment), wave-specialised form
-  if (d.gi_gamma) {
-    aldm_set_error("igemm_halo: gnin_* launches take no second-source segment");
-    return ALDM_E_UNSUPPORTED;
-  }
-  if (d.splits > 1) return launch_halo_v<BM, BN, WM, WN, HP, S, 3, false, true, true>(d, st);
-  if (d.out_act == ALDM_ACT_NONE && d.post_act == ALDM_ACT_NONE)
-    return d.qstat ? launch_halo_v<BM, BN, WM, WN, HP, S, 4, false, true, true>(d, st) : launch_halo_v<BM, BN, WM, WN, HP, S, 1, false, true, true>(d, st);
-  return launch_halo_v<BM, BN, WM, WN, HP, S, 0, false, true, true>(d, st);
-}
-
-template <int BM, int BN, int WM, int WN, int HP, int S, bool WS = false>
-int launch_halo(const IgemmDev& d, hipStream_t st) {
-  if (d.splits > 1) {
-    if (d.gi_gamma) {
-      aldm_set_error("igemm_halo: gnin_* launches are not split");
-      return ALDM_E_UNSUPPORTED;
-    }
-    return launch_halo_v<BM, BN, WM, WN, HP, S, 3, false, WS>(d, st);
-  }
-  if (d.gi_gamma) {                                          // GroupNorm of the input folded in: the ResnetBlock2D convolutions (lean epilogues)
-    if (d.out_act != ALDM_ACT_NONE || d.post_act != ALDM_ACT_NONE) {
-      aldm_set_error("igemm_halo: gnin_* launches take no output activation");
-      return ALDM_E_UNSUPPORTED;
-    }
-    return d.qstat ? launch_halo_v<BM, BN, WM, WN, HP, S, 4, true, WS>(d, st) : launch_halo_v<BM, BN, WM, WN, HP, S, 1, true, WS>(d, st);
-  }
-  if (d.out_act == ALDM_ACT_NONE && d.post_act == ALDM_ACT_NONE)
-    return d.qstat ? launch_halo_v<BM, BN, WM, WN, HP, S, 4, false, WS>(d, st) : launch_halo_v<BM, BN, WM, WN, HP, S, 1, false, WS>(d, st);
-  return launch_halo_v<BM, BN, WM, WN, HP, S, 0, false, WS>(d, st);
+int igemm_launch_halo(const aldm_igemm_variant_t& v, const IgemmDev& d, hipStream_t st) {
+  return with_constant<ALDM_TILE_HALO_128x128, ALDM_TILE_HALO_64x128, ALDM_TILE_HALO_128x128_WS, ALDM_TILE_HALO_64x128_WS>(
+      v.tile, [&](auto tile) { return launch_halo_tile<decltype(tile)::value>(v, d, st); });
 }
 
 }  // namespace aldm_igemm_detail
-
-// tile: ALDM_TILE_HALO_128x128 / _64x128 or their wave-specialised forms (_WS).  The caller (aldm_igemm) has validated the generic arguments.
-int aldm_launch_halo(const aldm_igemm_detail::IgemmDev& d0, int tile, int ring, hipStream_t st) {
-  using namespace aldm_igemm_detail;
-  IgemmDev d = d0;
-  const bool ws = tile == ALDM_TILE_HALO_128x128_WS || tile == ALDM_TILE_HALO_64x128_WS;
-  if (ws && d.KH == 1 && d.OH == 1 && d.IH == 1 && d.UH == 0 && d.ph == 0 && d.dh == 1 && d.sh == 1 && d.C3tot == 0 && !d.gi_gamma) {
-    // a 1-D convolution (conv1d = KH 1 over a 1 x T image): the same memory read as a T x 1 image under a KW x 1 filter -- the tile is then
-    // BM consecutive time steps, its halo BM + (KW - 1) dw rows, the weight layout [(tap, c)] is unchanged
-    d.KH = d.KW; d.KW = 1; d.dh = d.dw; d.dw = 1; d.ph = d.pw; d.pw = 0;
-    d.OH = d.OW; d.OW = 1; d.IH = d.IW; d.IW = 1; d.sh = d.sw; d.sw = 1;
-    d.fd_ow = make_fastdiv(1u);
-    d.fd_ohw = make_fastdiv((unsigned)d.OHW);
-  }
-  const bool same = ws ? (d.KH % 2 == 1 && d.KW % 2 == 1 && 2 * d.ph == (d.KH - 1) * d.dh && 2 * d.pw == (d.KW - 1) * d.dw &&
-                          ((d.KH == 3 && d.KW == 3 && d.dh == 1 && d.dw == 1) || (d.C3tot == 0 && !d.gi_gamma && d.UH == 0)))
-                       : (d.KH == 3 && d.KW == 3 && d.ph == 1 && d.pw == 1 && d.dh == 1 && d.dw == 1);
-  const bool ok = same && d.sh == 1 && d.sw == 1 &&
-                  d.in_act == ALDM_ACT_NONE && d.Cin % 64 == 0 && d.Cin2 % 64 == 0 && d.dilate == 0 &&
-                  !d.ln_s && !d.geglu && d.x_bytes < 0x80000000u && d.x2_bytes < 0x80000000u &&
-                  ((d.UH == 0 && d.UW == 0) || (d.UH > 0 && d.UW > 0)) && d.OH == (d.UH ? d.UH : d.IH) && d.OW == (d.UW ? d.UW : d.IW);
-  if (!ok) {
-    aldm_set_error("igemm_halo: needs a stride-1 'same' convolution on the LDS-DMA path (Cin %% 64 == 0, no gather activation): 3x3, or -- wave-specialised tiles -- any odd filter with dilation");
-    return ALDM_E_UNSUPPORTED;
-  }
-  if (d.C3tot > 0) {                                          // the fused 1x1 segment: wave-specialised tiles, three-pass halo at most
-    const bool fits = d.UH == 0 && d.C3tot % 64 == 0 && d.Cin3 % 64 == 0 && d.x3_bytes < 0x80000000u && d.x4_bytes < 0x80000000u;
-    if (fits && tile == ALDM_TILE_HALO_128x128_WS && (128 / d.OW + 2) * (d.OW + 2) <= 192) return launch_halo_ext<128, 128, 4, 2, 3, 3>(d, st);
-    if (fits && tile == ALDM_TILE_HALO_64x128_WS) return launch_halo_ext<64, 128, 2, 4, 2, 3>(d, st);
-    aldm_set_error("igemm_halo: the second-source segment needs a wave-specialised halo tile whose halo fits three DMA passes (OW >= 8 at 128 rows)");
-    return ALDM_E_UNSUPPORTED;
-  }
-  if (tile == ALDM_TILE_HALO_128x128_WS) {                  // 8 compute + 4 loader waves; ring 3 (4 where asked)
-    if ((128 / d.OW + (d.KH - 1) * d.dh) * (d.OW + (d.KW - 1) * d.dw) > 192) {
-      if (ring == 4) return launch_halo<128, 128, 4, 2, 5, 4, true>(d, st);
-      return launch_halo<128, 128, 4, 2, 5, 3, true>(d, st);
-    }
-    if (ring == 4) return launch_halo<128, 128, 4, 2, 3, 4, true>(d, st);
-    return launch_halo<128, 128, 4, 2, 3, 3, true>(d, st);
-  }
-  if (tile == ALDM_TILE_HALO_64x128_WS) {
-    if (ring == 4) return launch_halo<64, 128, 2, 4, 2, 4, true>(d, st);
-    return launch_halo<64, 128, 2, 4, 2, 3, true>(d, st);
-  }
-  if (tile == ALDM_TILE_HALO_128x128) {
-    // halo rows the tile needs: (128 / OW + 2) image rows of OW + 2 pixels.  192 (three DMA passes) covers OW <= 16 -- the UNet's
-    // latents; the VAE's 64-wide images need 264: five passes, 80 KB for the two halo buffers
-    if ((128 / d.OW + 2) * (d.OW + 2) > 192) {
-      if (ring == 2) return launch_halo<128, 128, 4, 2, 5, 2>(d, st);
-      if (ring == 4) return launch_halo<128, 128, 4, 2, 5, 4>(d, st);
-      return launch_halo<128, 128, 4, 2, 5, 3>(d, st);
-    }
-    if (ring == 2) return launch_halo<128, 128, 4, 2, 3, 2>(d, st);
-    if (ring == 4) return launch_halo<128, 128, 4, 2, 3, 4>(d, st);
-    return launch_halo<128, 128, 4, 2, 3, 3>(d, st);
-  }
-  if (ring == 2) return launch_halo<64, 128, 2, 4, 2, 2>(d, st);
-  if (ring == 4) return launch_halo<64, 128, 2, 4, 2, 4>(d, st);
-  return launch_halo<64, 128, 2, 4, 2, 3>(d, st);
-}

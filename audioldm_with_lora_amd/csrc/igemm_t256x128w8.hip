@@ -4,19 +4,5 @@
 // of workgroups), where neither launch latency nor workgroup count is the limit.  No LoRA / V^T forms: plain convolutions only.
 #include "igemm_core.h"
 namespace aldm_igemm_detail {
-template <int S>
-int launch_256(const IgemmDev& d, hipStream_t st) {
-  if (d.splits <= 1 && !d.geglu && d.out_act == ALDM_ACT_NONE && d.post_act == ALDM_ACT_NONE && !d.ln_s) {   // LEAN: see igemm_core.h
-    if (d.qstat) return launch_cfg<256, 128, 4, 2, 0, false, S, 4>(d, st);
-    return launch_cfg<256, 128, 4, 2, 0, false, S, 1>(d, st);
-  }
-  return launch_cfg<256, 128, 4, 2, 0, false, S>(d, st);
-}
+int igemm_launch_t256x128w8(const aldm_igemm_variant_t& v, const IgemmDev& d, hipStream_t st) { return launch_ring_tile<ALDM_TILE_256x128_W8>(v, d, st); }
 }  // namespace aldm_igemm_detail
-int aldm_launch_tile_256x128w8(const aldm_igemm_detail::IgemmDev& d, int Rp, bool vt, int ring, hipStream_t st) {
-  using namespace aldm_igemm_detail;
-  const bool fast = d.in_act == ALDM_ACT_NONE && d.Cin % 64 == 0 && d.Cin2 % 64 == 0 && d.x_bytes < 0x80000000u && d.x2_bytes < 0x80000000u;
-  if (!fast || Rp != 0 || vt) { aldm_set_error("igemm: the 256x128 tile needs the LDS-DMA path and takes no LoRA / V^T"); return ALDM_E_UNSUPPORTED; }
-  if (ring == 3) return launch_256<3>(d, st);
-  return launch_256<2>(d, st);
-}

@@ -1,5 +1,5 @@
 // Instantiates the implicit-GEMM kernels for the 64x64 workgroup tile (see igemm_core.h).
 #include "igemm_core.h"
-int aldm_launch_tile_64x64(const aldm_igemm_detail::IgemmDev& d, int Rp, bool vt, int ring, hipStream_t st) {
-  return aldm_igemm_detail::launch_tile<64, 64, 2, 2, 4, 3>(d, Rp, vt, ring, st);
-}
+namespace aldm_igemm_detail {
+int igemm_launch_t64x64(const aldm_igemm_variant_t& v, const IgemmDev& d, hipStream_t st) { return launch_ring_tile<ALDM_TILE_64x64>(v, d, st); }
+}  // namespace aldm_igemm_detail

@@ -251,67 +251,26 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void igemm_ws_kernel(const Ige
 #endif
 }
 
-template <int BM, int BN, int WM, int WN, int NL, int S, int EPI, bool RS = false>
-int launch_ws(const IgemmDev& d, hipStream_t st) {
-  constexpr size_t ring = (size_t)S * (BM + BN) * 128;
-  constexpr size_t lds = (ring > (size_t)EpiCfg<BM, BN>::BYTES ? ring : (size_t)EpiCfg<BM, BN>::BYTES) + 2 * BM * sizeof(float);
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  static unsigned long long attr_done = 0;
-  auto kern = igemm_ws_kernel<BM, BN, WM, WN, NL, S, EPI, RS>;
-  if (int rc = aldm_set_max_lds(reinterpret_cast<const void*>(kern), (int)lds, &attr_done, "igemm_ws")) return rc;
-  if ((d.qstat || d.rowstat) && d.N % BN != 0) {
-    aldm_set_error("igemm: qstat_out / rowstat_out need Cout %d to be a multiple of the tile width %d", d.N, BN);
-    return ALDM_E_ARG;
-  }
-  IgemmDev dd = d;
-  dd.tiles_n = cdiv(d.N, BN);
-  dd.fd_tiles_n = make_fastdiv((unsigned)dd.tiles_n);
-  dd.tiles_m = cdiv(d.M, BM);
-  dd.fd_tiles_m = make_fastdiv((unsigned)dd.tiles_m);
-  dd.fd_splits = make_fastdiv((unsigned)d.splits);
-  dd.nwg = dd.tiles_m * dd.tiles_n * d.splits;
-  hipLaunchKernelGGL(kern, dim3(dd.nwg), dim3(64 * (WM * WN + NL)), lds, st, dd);
-  return aldm_launch_status("igemm_ws");
+// The instantiations of one ws tile: its ring depths with the LDS-DMA loaders (ring 3, or 4 at 24 KB per stage on the small tiles),
+// ring 2 with the register-staged ones, each with the four epilogue forms of a plain launch
+template <int TILE>
+int launch_ws_tile(const aldm_igemm_variant_t& v, const IgemmDev& d, hipStream_t st) {
+  static constexpr IgemmTile T = *igemm_tile(TILE);
+  return with_constant<2, 3, 4>(v.ring, [&](auto s) {
+    return with_constant<0, 1, 3, 4>(v.epi, [&](auto epi) {
+      constexpr int S = decltype(s)::value, EPI = decltype(epi)::value;
+      if constexpr (T.has_kernel_ring(S) && ((T.epis >> EPI) & 1u)) {
+        static_assert(ring_lds_bytes(S, T.bm, T.bn, 0) <= IGEMM_MAX_LDS, "LDS budget");
+        return launch_variant<igemm_ws_kernel<T.bm, T.bn, T.wm, T.wn, T.nl, S, EPI, S == 2>>(v, d, st, "igemm_ws");
+      } else {
+        return igemm_not_instantiated();
+      }
+    });
+  });
 }
 
-template <int BM, int BN, int WM, int WN, int NL, int S, bool RS = false>
-int launch_ws_epi(const IgemmDev& d, hipStream_t st) {
-  const bool lean = d.splits <= 1 && d.out_act == ALDM_ACT_NONE && d.post_act == ALDM_ACT_NONE;
-  if (d.splits > 1) return launch_ws<BM, BN, WM, WN, NL, S, 3, RS>(d, st);
-  if (lean && d.qstat) return launch_ws<BM, BN, WM, WN, NL, S, 4, RS>(d, st);
-  if (lean) return launch_ws<BM, BN, WM, WN, NL, S, 1, RS>(d, st);
-  return launch_ws<BM, BN, WM, WN, NL, S, 0, RS>(d, st);
-}
-
-static int ws_refuse(const IgemmDev& d, int Rp, bool vt) {
-  const bool fast = d.in_act == ALDM_ACT_NONE && d.Cin % 64 == 0 && d.Cin2 % 64 == 0 && d.x_bytes < 0x80000000u && d.x2_bytes < 0x80000000u;
-  if (!fast || Rp != 0 || vt || d.ln_s || d.geglu) {
-    aldm_set_error("igemm: the wave-specialised tiles take plain launches only (LDS-DMA path, no LoRA / V^T / folded LayerNorm / GEGLU)");
-    return ALDM_E_UNSUPPORTED;
-  }
-  return ALDM_OK;
+int igemm_launch_ws(const aldm_igemm_variant_t& v, const IgemmDev& d, hipStream_t st) {
+  return with_constant<ALDM_TILE_256x128_WS, ALDM_TILE_64x128_WS, ALDM_TILE_128x64_WS>(v.tile, [&](auto tile) { return launch_ws_tile<decltype(tile)::value>(v, d, st); });
 }
 
 }  // namespace aldm_igemm_detail
-
-int aldm_launch_tile_256x128ws(const aldm_igemm_detail::IgemmDev& d, int Rp, bool vt, int ring, hipStream_t st) {
-  using namespace aldm_igemm_detail;
-  if (int rc = ws_refuse(d, Rp, vt)) return rc;
-  if (ring == 2) return launch_ws_epi<256, 128, 4, 2, 4, 2, true>(d, st);     // ring 2 = register-staged loaders
-  return launch_ws_epi<256, 128, 4, 2, 4, 3>(d, st);
-}
-// 4 compute waves + 4 loader waves on the small tiles; ring 3 or 4 (24 KB per stage)
-int aldm_launch_tile_64x128ws(const aldm_igemm_detail::IgemmDev& d, int Rp, bool vt, int ring, hipStream_t st) {
-  using namespace aldm_igemm_detail;
-  if (int rc = ws_refuse(d, Rp, vt)) return rc;
-  if (ring == 2) return launch_ws_epi<64, 128, 2, 2, 4, 2, true>(d, st);
-  if (ring == 4) return launch_ws_epi<64, 128, 2, 2, 4, 4>(d, st);
-  return launch_ws_epi<64, 128, 2, 2, 4, 3>(d, st);
-}
-int aldm_launch_tile_128x64ws(const aldm_igemm_detail::IgemmDev& d, int Rp, bool vt, int ring, hipStream_t st) {
-  using namespace aldm_igemm_detail;
-  if (int rc = ws_refuse(d, Rp, vt)) return rc;
-  if (ring == 2) return launch_ws_epi<128, 64, 2, 2, 4, 2, true>(d, st);
-  if (ring == 4) return launch_ws_epi<128, 64, 2, 2, 4, 4>(d, st);
-  return launch_ws_epi<128, 64, 2, 2, 4, 3>(d, st);
-}

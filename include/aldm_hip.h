@@ -775,6 +775,42 @@ int aldm_clip_segment(const float* x, long long pool_len, const long long* offse
 int aldm_clip_normalize_parts(int T, int target);
 int aldm_clip_normalize(const float* y, const int* n, int B, int T, int target, double* workspace, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * What aldm_igemm would run, answered on the host (no device needed; pointer fields of the argument are only tested for null).
+ * The dispatch itself reads these two answers: csrc/igemm_select.h holds the tile table and the selection.
+ * ------------------------------------------------------------------------------------------ */
+enum { ALDM_IGEMM_KERNEL = 0 /* igemm_kernel: register-staged double buffer */, ALDM_IGEMM_PIPE_KERNEL = 1 /* igemm_pipe_kernel: LDS-DMA ring */,
+       ALDM_IGEMM_WS_KERNEL = 2, ALDM_IGEMM_HALO_KERNEL = 3, ALDM_IGEMM_HALO_WS_KERNEL = 4 };
+enum { ALDM_IGEMM_KIND_W4 = 0, ALDM_IGEMM_KIND_W8 = 1, ALDM_IGEMM_KIND_WS = 2, ALDM_IGEMM_KIND_HALO = 3, ALDM_IGEMM_KIND_HALO_WS = 4 };
+typedef struct {
+  int family;                 /* ALDM_IGEMM_* */
+  int tile;                   /* the ALDM_TILE_* the launch runs (tile = 0 resolved) */
+  /* the template arguments of the instantiation; the ones its family does not have are 0 */
+  int bm, bn, wm, wn;         /* every family */
+  int rp, vt, gate;           /* igemm_kernel, igemm_pipe_kernel: RP, VT, GATE */
+  int ring;                   /* S; 0 with igemm_kernel */
+  int epi;                    /* EPI; 0 with igemm_kernel */
+  int nl, rs;                 /* igemm_ws_kernel: NL, RS */
+  int hp, gnin, ext;          /* halo kernels: HP, GNIN; EXT (igemm_halo_ws_kernel) */
+  int transposed;             /* 1: a conv1d read as a KW x 1 filter over an IW x 1 image (halo-ws tiles) */
+  int splits, kt_per_split;   /* the K-splits the launch really makes, K-tiles of each */
+  int direct;                 /* 1: register-direct epilogue (aldm_igemm_epilogue_form) */
+  int tiles_m, tiles_n;       /* as the kernel is told them (halo kernels: tiles_m = workgroups per split) */
+  unsigned grid, block, lds;  /* workgroups, threads of each, dynamic LDS bytes */
+  char name[192];             /* the kernel, as a demangler prints it */
+} aldm_igemm_variant_t;
+/* 0 and *v filled, or the ALDM_E_* code (and aldm_last_error text) aldm_igemm would return for these arguments before it launches */
+int aldm_igemm_variant(const aldm_igemm_t* p, aldm_igemm_variant_t* v);
+typedef struct {
+  int tile, kind;             /* ALDM_TILE_*, ALDM_IGEMM_KIND_* */
+  int bm, bn, wm, wn;
+  int blocks;                 /* 16x16 accumulator blocks per lane */
+  unsigned rings;             /* bit S: the LDS-DMA ring depth S can be asked for; ring, ring_lora: the depth ring = 0 gets without / with LoRA */
+  int ring, ring_lora;
+  int halo_rows, halo_rows_fused;   /* halo tiles: LDS halo capacity in rows, the same of the fused-shortcut form (x3 | x4; 0: no such form) */
+} aldm_igemm_tile_info_t;
+int aldm_igemm_tile_info(int tile, aldm_igemm_tile_info_t* info);   /* ALDM_E_UNSUPPORTED ("igemm: unknown tile") for a tile that cannot be launched */
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ from bwd_restatement import F64
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 NAN = float("nan")
-GENERIC_ANY = (1, 2, 3, 4)                                       # launch_tile: any input
+GENERIC_ANY = (1, 2, 3, 4)                                       # reg_staged rows of IGEMM_TILES: any input
 GENERIC_DMA = (6, 9, 10, 11, 12, 13, 14)                         # LDS-DMA path only: every source a multiple of 64 channels, no gather activation
 
 
@@ -290,7 +290,7 @@ def test_halo_fused_shortcut(ops, monkeypatch, tile):
 
 
 def ws_admits(c, tile):
-    """`same` of aldm_launch_halo for the wave-specialised tiles (no segment, no up-sampling): odd filter, 2 pad = (K - 1) dil, stride 1."""
+    """`same` of select_halo (igemm_select.hip) for the wave-specialised tiles (no segment, no up-sampling): odd filter, 2 pad = (K - 1) dil, stride 1."""
     d = dict(c)
     (KH, KW), (ph, pw), (dh, dw) = d["k"], d["pad"], d["dil"]
     return KH % 2 == 1 and KW % 2 == 1 and 2 * ph == (KH - 1) * dh and 2 * pw == (KW - 1) * dw and d["stride"] == (1, 1)

@@ -84,9 +84,9 @@ def nan_like(B, T, C):
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _igemm_tiles(cin):
     """Every non-halo tile aldm_igemm accepts for a launch of the transposed convolution (no LoRA, no V^T): ops.conv hands tile= straight
-    to the library, whose launchers refuse only by path -- 1, 2, 3, 4 (launch_tile) take any input; the 8-wave tiles 6, 9, 10, 11
-    (igemm_t128x128w8 / t256x128w8 / t64w8.hip) and the wave-specialised 12, 13, 14 (ws_refuse, igemm_ws.hip) need the LDS-DMA path,
-    Cin % 64 == 0.  No launcher has a condition on M, N or the number of K-tiles: 9 and 12 are the 256-row tiles."""
+    to the library, whose selection refuses only by path -- 1, 2, 3, 4 (reg_staged rows of IGEMM_TILES) take any input; the 8-wave tiles
+    6, 9, 10, 11 and the wave-specialised 12, 13, 14 (select_ring, igemm_select.hip) need the LDS-DMA path,
+    Cin % 64 == 0.  No row has a condition on M, N or the number of K-tiles: 9 and 12 are the 256-row tiles."""
     return [1, 2, 3, 4] + ([6, 9, 10, 11, 12, 13, 14] if cin % 64 == 0 else [])
 
 

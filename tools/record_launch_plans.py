@@ -18,7 +18,17 @@ when the package is imported: one process per mode, then
 writes the committed form (pack_fixture: one record list for both modes, struct values as lists in the order of `fields`, as gzipped
 JSON -- 0.6 MB of recorded numbers is nothing to read in a diff; load_fixture gives the two runs back).  To compare a commit with the fixture, record it the same way, then per mode
 
-    python tools/record_launch_plans.py --diff tests/golden/igemm_launch_plans.json.gz tuned|no_tuned RUN.json"""
+    python tools/record_launch_plans.py --diff tests/golden/igemm_launch_plans.json.gz tuned|no_tuned RUN.json
+
+--kernels (recording) also traces the recorded pass of every workload (kineto, as bench.trace_steps) and keeps, per distinct igemm record,
+what the GPU really ran: `kernel` = {"name": demangled kernel name, "grid", "block", "lds" where the tracer reports them}.  Every
+aldm_igemm call dispatches exactly one igemm_* kernel besides igemm_reduce_kernel, so launch order pairs the trace with the calls.
+
+    python tools/record_launch_plans.py --merge-kernels TUNED.json NO_TUNED.json tests/golden/igemm_launch_plans.json.gz \
+        tests/golden/igemm_kernel_variants.json.gz
+
+writes the committed form: one entry per record of the launch-plan fixture (null for pgemm records), names as indices into `names`.
+--diff with that file as a fifth argument also compares the kernels of RUN.json (recorded with --kernels) with it."""
 import ctypes as C
 import gzip
 import json
@@ -79,6 +89,7 @@ def describe_struct(a):
 class Recorder:
     def __init__(self):
         self.records, self.index, self.order, self.cur = [], {}, [], None
+        self.calls = []                                                  # per aldm_igemm call: position in self.order of the conv() that made it, or None
         self.real = _lib.load()
         self.conv = ops.conv
 
@@ -90,6 +101,8 @@ class Recorder:
 
         def launch(ref, stream):
             a = ref._obj
+            if name == "aldm_igemm":
+                self.calls.append(len(self.order) if self.cur is not None else None)
             if self.cur is not None:
                 vals, nonnull = describe_struct(a)
                 self.cur.update(route=name[5:], args=vals, nonnull=nonnull,
@@ -130,7 +143,7 @@ class Recorder:
         return False
 
     def take(self):
-        order, self.order = self.order, []
+        order, self.order, self.calls = self.order, [], []
         return order
 
 
@@ -208,24 +221,124 @@ def workloads(tiny, vocoder=True):
     yield pre + "train_step", lambda: tr.step(lat, noise, t, emb)
 
 
-def record(sizes=("tiny",), vocoder_full=True, timing=None):
-    """{"records": [...], "workloads": {name: [index, ...]}} of the given sizes, recorded in this process"""
-    out = {}
+_TRACER_WARM = False
+
+
+def traced_igemm_kernels(fn):
+    """fn() under the kernel tracer: [{"name", "grid", "block", "lds"}] of its igemm_* kernels (the split-K reduce left out) in launch order"""
+    import tempfile
+    from torch.profiler import ProfilerActivity, profile
+    global _TRACER_WARM
+    if not _TRACER_WARM:                                                 # the first session of a process loses its first kernels
+        with profile(activities=[ProfilerActivity.CUDA]):
+            torch.zeros(64, device="cuda").sum().item()
+        _TRACER_WARM = True
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    with tempfile.TemporaryDirectory() as tmp:
+        prof.export_chrome_trace(os.path.join(tmp, "trace.json"))
+        with open(os.path.join(tmp, "trace.json")) as f:
+            evs = [e for e in json.load(f)["traceEvents"] if e.get("cat") == "kernel"]
+    evs.sort(key=lambda e: e["ts"])
+    out = []
+    for e in evs:
+        if "igemm_" in e["name"] and "igemm_reduce_kernel" not in e["name"]:
+            a = e.get("args", {})
+            out.append({"name": e["name"], "grid": a.get("grid"), "block": a.get("block"), "lds": a.get("shared memory")})
+    return out
+
+
+def record(sizes=("tiny",), vocoder_full=True, timing=None, kernels=False):
+    """{"records": [...], "workloads": {name: [index, ...]}} of the given sizes, recorded in this process; kernels: every igemm record
+    also gets `kernel`, what the tracer saw its launch run"""
+    out, seen = {}, {}
     with Recorder() as rec:
+        def one_pass(name, fn):
+            """fn() once: its launches as indices into rec.records; with `kernels`, under the tracer (the warm-up pass too: it makes
+            launches no later pass repeats)"""
+            if kernels:
+                ran = traced_igemm_kernels(fn)
+            else:
+                fn()
+                torch.cuda.synchronize()
+            calls = rec.calls
+            order = rec.take()
+            if kernels:
+                if len(ran) != len(calls):
+                    raise RuntimeError(f"{name}: {len(calls)} aldm_igemm calls, {len(ran)} igemm kernels in the trace")
+                for pos, k in zip(calls, ran):
+                    if pos is not None and seen.setdefault(order[pos], k) != k:
+                        raise RuntimeError(f"{name}: record {order[pos]} ran {k} and {seen[order[pos]]}")
+            return order
+
         for size in sizes:
-            for name, fn in workloads(size == "tiny", vocoder_full):
+            gen = workloads(size == "tiny", vocoder_full)
+            while True:
+                made = []
+                one_pass("set-up", lambda: made.append(next(gen, None)))    # building a workload launches too (an engine's conditioning)
+                if made[0] is None:
+                    break
+                name, fn = made[0]
                 with torch.no_grad() if "train" not in name else torch.enable_grad():
-                    fn()                                                 # warm-up: packs the weights, sizes the workspace
-                    torch.cuda.synchronize()
-                    rec.take()
+                    one_pass(name, fn)                                   # warm-up: packs the weights, sizes the workspace
                     t0 = time.perf_counter()
-                    fn()
-                    torch.cuda.synchronize()
+                    out[name] = one_pass(name, fn)
                 if timing is not None:
                     timing[name] = round((time.perf_counter() - t0) * 1e3, 2)
-                out[name] = rec.take()
                 ops.drop_pending()
-        return {"records": rec.records, "workloads": out}
+        run = {"records": rec.records, "workloads": out}
+        if kernels:
+            missing = [i for i, r in enumerate(rec.records) if r["route"] == "igemm" and i not in seen]
+            if missing:
+                raise RuntimeError(f"no kernel traced for igemm records {missing[:10]}")
+            run["kernels"] = [seen.get(i) for i in range(len(rec.records))]
+        return run
+
+
+def pack_kernels(tuned, no_tuned, plans_path):
+    """The committed form of the `kernels` of two runs: one entry [name index, grid, block, lds] per record of the launch-plan fixture"""
+    with gzip.open(plans_path, "rt") as f:
+        d = json.load(f)
+    index = {json.dumps(r, sort_keys=True): i for i, r in enumerate(d["records"])}
+    names, variants = [], [None] * len(d["records"])
+    for run in (tuned, no_tuned):
+        for r, k in zip(run["records"], run["kernels"]):
+            i = index[json.dumps(dict(r, args=[r["args"][f] for f in d["fields"][r["route"]]]), sort_keys=True)]   # KeyError: not the fixture's runs
+            if k is None:
+                continue
+            if k["name"] not in names:
+                names.append(k["name"])
+            v = [names.index(k["name"]), k["grid"], k["block"], k["lds"]]
+            if variants[i] not in (None, v):
+                raise RuntimeError(f"record {i}: {variants[i]} and {v}")
+            variants[i] = v
+    return {"names": names, "variants": variants}
+
+
+def load_kernels(path, plans_path):
+    """{json text of a launch-plan fixture record: {"name", "grid", "block", "lds"}} from the committed forms"""
+    with gzip.open(path, "rt") as f:
+        k = json.load(f)
+    with gzip.open(plans_path, "rt") as f:
+        d = json.load(f)
+    return {json.dumps(r, sort_keys=True): dict(zip(("name", "grid", "block", "lds"), [k["names"][v[0]]] + v[1:]))
+            for r, v in zip(d["records"], k["variants"]) if v is not None}, d["fields"]
+
+
+def diff_kernels(path, plans_path, run):
+    """number of igemm records of a run (recorded with --kernels) whose kernel differs from the committed one"""
+    want, fields = load_kernels(path, plans_path)
+    bad = 0
+    for i, (r, k) in enumerate(zip(run["records"], run["kernels"])):
+        if r["route"] != "igemm":
+            continue
+        w = want.get(json.dumps(dict(r, args=[r["args"][f] for f in fields["igemm"]]), sort_keys=True))
+        if w != k:
+            bad += 1
+            if bad <= 10:
+                print(f"record {i} ({r['key']}): recorded {w}, now {k}")
+    return bad
 
 
 def pack_fixture(tuned, no_tuned):
@@ -287,17 +400,26 @@ def main():
     if sys.argv[1] == "--diff":                                          # --diff FIXTURE.json.gz tuned|no_tuned RUN.json
         with open(sys.argv[4]) as f:
             bad = diff(load_fixture(sys.argv[2])[sys.argv[3]], json.load(f))
+            if len(sys.argv) > 5:
+                f.seek(0)
+                bad += diff_kernels(sys.argv[5], sys.argv[2], json.load(f))
         print(f"{sys.argv[4]} against {sys.argv[2]} [{sys.argv[3]}]: " + ("no difference" if not bad else f"{bad} differences"))
         sys.exit(1 if bad else 0)
+    if sys.argv[1] == "--merge-kernels":                                 # --merge-kernels TUNED.json NO_TUNED.json PLANS.json.gz OUT.json.gz
+        with open(sys.argv[2]) as f1, open(sys.argv[3]) as f2:
+            text = json.dumps(pack_kernels(json.load(f1), json.load(f2), sys.argv[4]), separators=(",", ":"), sort_keys=True)
+        with open(sys.argv[5], "wb") as fo, gzip.GzipFile(fileobj=fo, mode="wb", mtime=0) as gz:
+            gz.write(text.encode())
+        return
     if sys.argv[1] == "--merge":
         with open(sys.argv[2]) as f1, open(sys.argv[3]) as f2:
             text = json.dumps(pack_fixture(json.load(f1), json.load(f2)), separators=(",", ":"), sort_keys=True)
         with open(sys.argv[4], "wb") as fo, gzip.GzipFile(fileobj=fo, mode="wb", mtime=0) as gz:   # (mtime 0: same runs, same bytes)
             gz.write(text.encode())
         return
-    which = sys.argv[2] if len(sys.argv) > 2 else "all"
+    which = sys.argv[2] if len(sys.argv) > 2 and not sys.argv[2].startswith("--") else "all"
     timing = {}
-    run = record(("tiny", "full") if which == "all" else (which,), "--no-vocoder-full" not in sys.argv, timing)
+    run = record(("tiny", "full") if which == "all" else (which,), "--no-vocoder-full" not in sys.argv, timing, "--kernels" in sys.argv)
     with open(sys.argv[1], "w") as f:
         json.dump(run, f, separators=(",", ":"), sort_keys=True)
     print(json.dumps({"distinct": len(run["records"]), "launches": {k: len(v) for k, v in run["workloads"].items()},
