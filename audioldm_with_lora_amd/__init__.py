@@ -29,6 +29,9 @@ def __getattr__(name):
     if name == "resample":                              # the function; resample.py makes its module callable as it (and keeps the name)
         import importlib
         return importlib.import_module(".resample", __name__)
+    if name in ("LoudnessMeter", "integrated_loudness", "normalize_loudness"):       # loudness.py: BS.1770 metering and normalisation
+        from . import loudness
+        return getattr(loudness, name)
     if name in ("ClipFrontEnd", "HfAudioDataset", "AudioFolder", "ClipLoader", "ByteTokenizer"):      # data.py: training from recordings
         from . import data
         return getattr(data, name)

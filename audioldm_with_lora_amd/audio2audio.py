@@ -26,6 +26,8 @@ import torch
 
 from . import ops
 from .engine import DenoiseEngine, WindowedAudioToAudioEngine
+from .loudness import check_rate as check_loudness_rate
+from .loudness import normalize_loudness
 from .mel import LogMelFrontEnd
 from .pipeline import AudioLDMPipeline, AudioPipelineOutput, _frozen_config
 from .resample import Resampler, ratio
@@ -148,10 +150,10 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
                  num_inference_steps=50, guidance_scale=2.5, negative_prompt=None, num_waveforms_per_prompt=1, generator=None,
                  latents=None, prompt_embeds=None, negative_prompt_embeds=None, return_dict=True, output_type="np", adapter_names=None,
                  adapter_weights=None, window_length_in_s=None, window_overlap_in_s=None, loop=False, window_prompts=None,
-                 window_prompt_embeds=None, resample=False, output_sampling_rate=None):
+                 window_prompt_embeds=None, resample=False, output_sampling_rate=None, loudness_lufs=None, peak_ceiling_dbfs=-1.0):
         """resample=True: a recording at another rate than the vocoder's 16 kHz is resampled on the device first (resample.py), on the
         plain and the windowed path alike, and everything downstream sees the 16 kHz clip; without it such a rate raises.
-        output_sampling_rate: as in AudioLDMPipeline.__call__ (not with output_type="latent").
+        output_sampling_rate, loudness_lufs / peak_ceiling_dbfs: as in AudioLDMPipeline.__call__ (not with output_type="latent").
         window_length_in_s / window_overlap_in_s / loop / window_prompts / window_prompt_embeds: as in AudioLDMPipeline.__call__
         (None: one clip at the recording's own length, as ever).  With windows, `mask` and `latents` are those of the LONG clip, whose
         length is audio_length_in_s or the recording's (a looped plan rounds it UP and the longer clip is returned)."""
@@ -174,6 +176,10 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
             if output_type == "latent":
                 raise ValueError("output_sampling_rate applies to a waveform, not to output_type='latent'")
             ratio(vc.sampling_rate, output_sampling_rate)
+        if loudness_lufs is not None:
+            if output_type == "latent":
+                raise ValueError("loudness_lufs applies to a waveform, not to output_type='latent'")
+            check_loudness_rate(vc.sampling_rate if output_sampling_rate is None else output_sampling_rate)
         _, begin = self.scheduler.get_timesteps(num_inference_steps, strength)    # raises on a strength that leaves no step
         if window_length_in_s is None:
             if loop or window_prompts is not None or window_prompt_embeds is not None or window_overlap_in_s is not None:
@@ -247,7 +253,7 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
         if eng.graph is None and eng.use_graph:
             eng.capture()
         eng.run()
-        mel_out = None
+        mel_out = loud = None
         rate = int(vc.sampling_rate)
         if output_type == "latent":
             out = eng.latents_nchw()
@@ -256,10 +262,13 @@ class AudioLDMAudioToAudioPipeline(AudioLDMPipeline):
             out = wav_out[:, :n_samples]
             if output_sampling_rate is not None:
                 out, rate = resample_audio(out, rate, output_sampling_rate), int(output_sampling_rate)
+            if loudness_lufs is not None:
+                out, loud = normalize_loudness(out, rate, loudness_lufs, peak_ceiling_dbfs)
             if output_type == "np":
                 out = out.float().cpu().numpy()
         if not return_dict:
             return (out,)
         if plan is not None:                            # a windowed call also hands back its plan and the blended mel [B, T, 64] (device)
-            return AudioPipelineOutput(audios=out, sampling_rate=rate, plan=plan, mel=None if mel_out is None else mel_out[..., 0])
-        return AudioPipelineOutput(audios=out, sampling_rate=rate)
+            return AudioPipelineOutput(audios=out, sampling_rate=rate, plan=plan, mel=None if mel_out is None else mel_out[..., 0],
+                                       loudness=loud)
+        return AudioPipelineOutput(audios=out, sampling_rate=rate, loudness=loud)

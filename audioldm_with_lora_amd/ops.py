@@ -1491,12 +1491,22 @@ def resample_poly(x, up, down, lens=None, table=None):
     K = -(-(2 * half + 1) // up)
     if tuple(table.shape) != (up, K) or table.dtype != torch.float32 or table.device != x.device or not table.is_contiguous():
         raise ValueError(f"resample_poly: table must be contiguous fp32 [{up}, {K}] on {x.device}")
+    y = _resample_poly_rows(x, up, down, _h2d(lens, x.device), table)
+    return y, ((lens.to(torch.int64) * up + down - 1) // down).to(torch.int32)
+
+
+def _resample_poly_rows(x, up, down, dev_lens, table):
+    """resample_poly's launch with the lengths already on the device (int32 [B]; the kernel cuts them to [0, T]): nothing is copied
+    from the host, so a captured graph can hold it.  x contiguous fp32 [B, T], table the checked phase table."""
+    from . import resample as R
+    B, T = x.shape
+    half = 10 * max(up, down)
+    K = -(-(2 * half + 1) // up)
     T_out = R.output_length(T, up, down)
     y = torch.empty(B, T_out, dtype=torch.float32, device=x.device)
-    dl = _h2d(lens, x.device)
-    check(_lib.load().aldm_resample_poly(_p(x), _p(dl), B, T, _p(table), up, down, K, half, _p(y), T_out, _stream()),
+    check(_lib.load().aldm_resample_poly(_p(x), _p(dev_lens), B, T, _p(table), up, down, K, half, _p(y), T_out, _stream()),
           "aldm_resample_poly")
-    return y, ((lens.to(torch.int64) * up + down - 1) // down).to(torch.int32)
+    return y
 
 
 def _h2d(t, device):
@@ -1564,6 +1574,98 @@ def clip_normalize(y, n, target):
     out = torch.empty(B, target, dtype=torch.float32, device=y.device)
     check(lib.aldm_clip_normalize(_p(y), _p(n), B, T, target, _p(ws), _p(out), _stream()), "aldm_clip_normalize")
     return out
+
+
+def _wave_rows(x, lens, what, longest=None):
+    """(B, T) of a contiguous fp32 [B, T] device tensor x, and lens as int32 [B] on x's device (checked against `longest`, default T,
+    and copied over when it is not there; the kernels cut device lengths to the row themselves)"""
+    _require_gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.numel() == 0 or not x.is_contiguous():
+        raise ValueError(f"{what}: x must be a non-empty contiguous fp32 [B, T]")
+    B, T = x.shape
+    if not (torch.is_tensor(lens) and lens.is_cuda):
+        lens = torch.as_tensor(lens).to("cpu", torch.int32).reshape(-1)
+        if lens.numel() != B or int(lens.min()) < 0 or int(lens.max()) > (T if longest is None else longest):
+            raise ValueError(f"{what}: lens must hold {B} lengths in [0, {T}], got {lens.tolist()}")
+        lens = _h2d(lens, x.device)
+    assert lens.dtype == torch.int32 and lens.numel() == B and lens.is_contiguous() and lens.device == x.device, f"{what}: lens int32 [B]"
+    return B, T, lens
+
+
+def _f64_table(t, n, device, what):
+    if not (torch.is_tensor(t) and t.dtype == torch.float64 and t.numel() == n and t.is_contiguous() and t.device == device):
+        raise ValueError(f"{what} must be a contiguous float64 tensor of {n} elements on {device}")
+
+
+def kweight_energy(x, lens, hop, coef, mpow, chunk):
+    """K-weighted energy per hop of `hop` samples (aldm_kweight_energy; loudness.py has the definition): x fp32 [B, T] whose row b holds
+    lens[b] samples -> float64 [B, T // hop], zero behind a row's complete hops.  coef float64 [10], mpow float64 [6, 2, 4, 4] on the device:
+    the two biquads and the chunk's state-transition powers (loudness.LoudnessMeter builds both)."""
+    B, T, lens = _wave_rows(x, lens, "kweight_energy")
+    hop, chunk = int(hop), int(chunk)
+    _f64_table(coef, 10, x.device, "kweight_energy: coef")
+    _f64_table(mpow, 192, x.device, "kweight_energy: mpow")
+    lib = _lib.load()
+    e = torch.empty(B, T // hop if hop > 0 else 0, dtype=torch.float64, device=x.device)
+    ws = torch.empty(max(1, lib.aldm_kweight_energy_workspace_doubles(B, T)), dtype=torch.float64, device=x.device)
+    n = float(B) * T
+    # two passes over the samples, 10 fused multiply-adds a sample each, and the squares; every sample is read twice
+    check(_launch(f"kweight_energy|B{B} T{T} H{hop}", 2.0 * (2 * 10 + 4) * n, 2 * 4.0 * n + 8.0 * e.numel() + 8.0 * ws.numel(),
+                  lambda: lib.aldm_kweight_energy(_p(x), _p(lens), B, T, hop, _p(coef), _p(mpow), chunk, _p(ws), _p(e), _stream())),
+          "aldm_kweight_energy")
+    return e
+
+
+def loudness_gate(energy, lens, T, hop):
+    """Gated BS.1770 loudness from hop energies (aldm_loudness_gate): energy float64 [B, T // hop], lens int32 [B] -> float64 [B] in
+    LUFS, -inf for a clip without a 400 ms block above -70."""
+    _require_gpu(energy)
+    T, hop = int(T), int(hop)
+    if energy.dtype != torch.float64 or energy.dim() != 2 or not energy.is_contiguous() or hop <= 0 or energy.shape[1] != T // hop:
+        raise ValueError(f"loudness_gate: energy must be a contiguous float64 [B, {T} // {hop}]")
+    B = energy.shape[0]
+    if not (torch.is_tensor(lens) and lens.is_cuda):
+        lens = _h2d(torch.as_tensor(lens).to("cpu", torch.int32).reshape(-1), energy.device)
+    assert lens.dtype == torch.int32 and lens.numel() == B and lens.is_contiguous() and lens.device == energy.device, "loudness_gate: lens int32 [B]"
+    out = torch.empty(B, dtype=torch.float64, device=energy.device)
+    n = float(energy.numel())
+    check(_launch(f"loudness_gate|B{B} hops{energy.shape[1]}", 2.0 * 8 * n, 2 * 4 * 8.0 * n + 8.0 * B,
+                  lambda: _lib.load().aldm_loudness_gate(_p(energy), _p(lens), B, T, hop, _p(out), _stream())), "aldm_loudness_gate")
+    return out
+
+
+def peak_abs(x, lens, lens_ratio=(1, 1)):
+    """max |x| over the first lens[b] samples of every row (aldm_peak_abs): x fp32 [B, T] -> fp32 [B].  lens_ratio = (up, down): lens
+    are those of the rows x was resampled FROM, and row b holds ceil(lens[b] up / down) samples (resample_poly's out_lens, worked out
+    on the device)."""
+    up, down = int(lens_ratio[0]), int(lens_ratio[1])
+    if up < 1 or down < 1:
+        raise ValueError(f"peak_abs: lens_ratio must be two positive integers, got {lens_ratio!r}")
+    B, T, lens = _wave_rows(x, lens, "peak_abs", longest=x.shape[-1] * down // up)
+    out = torch.empty(B, dtype=torch.float32, device=x.device)
+    check(_launch(f"peak_abs|B{B} T{T}", 1.0 * B * T, 4.0 * B * T + 4.0 * B,
+                  lambda: _lib.load().aldm_peak_abs(_p(x), _p(lens), B, T, up, down, _p(out), _stream())), "aldm_peak_abs")
+    return out
+
+
+def loudness_gain(x, lens, lufs, peak, target_lufs, ceiling_dbfs=None):
+    """The gain that brings rows of loudness `lufs` (float64 [B]) to target_lufs, capped so that gain * peak (fp32 [B]) stays at or
+    under ceiling_dbfs (None: no cap), applied out of place (aldm_loudness_gain) -> (y fp32 [B, T], gain fp32 [B], gain_db float64 [B]).
+    A row whose loudness is -inf keeps gain 1; y is 0 from lens[b] on."""
+    B, T, lens = _wave_rows(x, lens, "loudness_gain")
+    _f64_table(lufs, B, x.device, "loudness_gain: lufs")
+    cap = ceiling_dbfs is not None
+    if cap and not (torch.is_tensor(peak) and peak.dtype == torch.float32 and peak.numel() == B and peak.is_contiguous()
+                    and peak.device == x.device):
+        raise ValueError(f"loudness_gain: peak must be a contiguous fp32 [{B}] on {x.device}")
+    y = torch.empty_like(x)
+    gain = torch.empty(B, dtype=torch.float32, device=x.device)
+    gain_db = torch.empty(B, dtype=torch.float64, device=x.device)
+    check(_launch(f"loudness_gain|B{B} T{T}", 1.0 * B * T, 8.0 * B * T + 24.0 * B,
+                  lambda: _lib.load().aldm_loudness_gain(_p(x), _p(lens), B, T, _p(lufs), _p(peak) if cap else None, float(target_lufs),
+                                                         float(ceiling_dbfs) if cap else 0.0, int(cap), _p(gain), _p(gain_db), _p(y),
+                                                         _stream())), "aldm_loudness_gain")
+    return y, gain, gain_db
 
 
 def train_noise_fused(state, alphas_cumprod, moments=None, latents=None, scaling_factor=1.0, noise_offset=0.0, ticket=None,

@@ -16,6 +16,8 @@ import torch
 from . import ops
 from .engine import DenoiseEngine, WindowedDenoiseEngine
 from .longform import plan_for_seconds
+from .loudness import check_rate as check_loudness_rate
+from .loudness import normalize_loudness
 from .resample import ratio, resample
 from .scheduler import DDIMScheduler, _fresh_seed
 from .unet import UNet2DConditionModel
@@ -282,8 +284,12 @@ class AudioLDMPipeline:
                  negative_prompt=None, num_waveforms_per_prompt=1, eta=0.0, generator=None, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, return_dict=True, output_type="np", adapter_names=None,
                  adapter_weights=None, window_length_in_s=None, window_overlap_in_s=None, loop=False, window_prompts=None,
-                 window_prompt_embeds=None, output_sampling_rate=None, **kw):
-        """output_sampling_rate (default None: the vocoder's 16 kHz, as ever): the trimmed waveform is resampled to this rate on the
+                 window_prompt_embeds=None, output_sampling_rate=None, loudness_lufs=None, peak_ceiling_dbfs=-1.0, **kw):
+        """loudness_lufs (default None: the level the vocoder produced, as ever): every clip is brought to this BS.1770 integrated
+        loudness on the device (loudness.py), at the rate it is delivered at -- after the output_sampling_rate resampling -- with the
+        gain capped so that the oversampled peak stays at or under peak_ceiling_dbfs (None: no cap); the output carries `loudness`,
+        the dict of device tensors lufs_in / gain_db / peak_in (None without loudness_lufs).
+        output_sampling_rate (default None: the vocoder's 16 kHz, as ever): the trimmed waveform is resampled to this rate on the
         device before it leaves for the host (resample.py; ceil(n_samples up / down) samples); the output carries `sampling_rate`.
         window_length_in_s (default None: one clip of audio_length_in_s, as ever) turns on windowed denoising for clips longer
         than the UNet was trained on: overlapping windows of that length (window_overlap_in_s, default a quarter of it) along one
@@ -296,6 +302,8 @@ class AudioLDMPipeline:
         vc = self.vocoder.config
         if output_sampling_rate is not None:
             ratio(vc.sampling_rate, output_sampling_rate)           # (raises on a rate that cannot be reached, before any work)
+        if loudness_lufs is not None:
+            check_loudness_rate(vc.sampling_rate if output_sampling_rate is None else output_sampling_rate)
         if audio_length_in_s is None:
             # diffusers: unet.config.sample_size * vae_scale_factor * prod(upsample_rates) / sampling_rate
             inner = getattr(getattr(self.unet, "base_model", None), "model", self.unet)          # a PeftModel wraps the UNet
@@ -344,10 +352,13 @@ class AudioLDMPipeline:
         rate = int(vc.sampling_rate)
         if output_sampling_rate is not None:
             audio, rate = resample(audio, rate, output_sampling_rate), int(output_sampling_rate)
+        loud = None
+        if loudness_lufs is not None:
+            audio, loud = normalize_loudness(audio, rate, loudness_lufs, peak_ceiling_dbfs)
         if output_type == "np":
             audio = audio.float().cpu().numpy()
         if not return_dict:
             return (audio,)
         if plan is not None:                            # a windowed call also hands back its plan and the blended mel [B, T, 64] (device)
-            return AudioPipelineOutput(audios=audio, sampling_rate=rate, plan=plan, mel=mel[..., 0])
-        return AudioPipelineOutput(audios=audio, sampling_rate=rate)
+            return AudioPipelineOutput(audios=audio, sampling_rate=rate, plan=plan, mel=mel[..., 0], loudness=loud)
+        return AudioPipelineOutput(audios=audio, sampling_rate=rate, loudness=loud)

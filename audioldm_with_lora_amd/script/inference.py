@@ -26,6 +26,8 @@ generates what follows it up to T seconds.
 `--repaint JUMP_LENGTH,JUMP_N_SAMPLE` (with --init-audio and a --regenerate-* or --extend-to-seconds mask, with or without
 --window-seconds) inpaints with RePaint's resampling loop (RePaintScheduler) instead of the legacy blend: more UNet calls, and a
 regenerated region that agrees better with what is kept; it runs from noise (--strength 1.0).
+`--loudness -14 [--peak-ceiling -1]` brings every clip to that ITU-R BS.1770 integrated loudness on the device before it is written
+(loudness.py; after `--output-sampling-rate`, so the level and the peak ceiling hold for the file).
 """
 import argparse
 import os
@@ -97,6 +99,10 @@ def parse_args(argv=None):
                          "nothing, quirk Q5)")
     ap.add_argument("--init-audio", default=None, help="wav to start from (audio-to-audio), any rate: resampled to the model's on the device; read with scipy")
     ap.add_argument("--output-sampling-rate", type=int, default=None, metavar="R", help="write the wav files at R Hz (default: the model's 16000)")
+    ap.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                    help="bring every clip to this ITU-R BS.1770 integrated loudness on the device, at the rate it is written at (e.g. -14)")
+    ap.add_argument("--peak-ceiling", type=float, default=None, metavar="DBFS",
+                    help="with --loudness: cap the gain so that the 4x oversampled peak stays at or under this level (default -1.0)")
     ap.add_argument("--strength", type=float, default=None,
                     help="with --init-audio: how much of the schedule to run (1 = from noise; default 0.5, with --repaint 1.0)")
     ap.add_argument("--repaint", default=None, metavar="JUMP_LENGTH,JUMP_N_SAMPLE",
@@ -113,6 +119,10 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.output_sampling_rate is not None and args.output_sampling_rate <= 0:
         ap.error("--output-sampling-rate expects a positive rate in Hz")
+    if args.peak_ceiling is not None and args.loudness is None:
+        ap.error("--peak-ceiling needs --loudness")
+    if args.loudness is not None and not np.isfinite(args.loudness):
+        ap.error("--loudness expects a finite level in LUFS")
     if args.adapters and not args.lora:
         ap.error("--adapters needs --lora NAME=PATH")
     if args.init_audio is None and (args.regenerate_seconds or args.regenerate_bands):
@@ -176,6 +186,8 @@ def main(argv=None):
     generator = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
     out_rate = int(pipe.vocoder.config.sampling_rate) if args.output_sampling_rate is None else args.output_sampling_rate
     rated = {} if args.output_sampling_rate is None else {"output_sampling_rate": args.output_sampling_rate}
+    if args.loudness is not None:                       # (normalised after the resampling, at the rate the file is written at)
+        rated.update(loudness_lufs=args.loudness, peak_ceiling_dbfs=-1.0 if args.peak_ceiling is None else args.peak_ceiling)
     windowed = {}
     if args.window_seconds is not None:
         windowed = dict(window_length_in_s=args.window_seconds, window_overlap_in_s=args.window_overlap_seconds, loop=args.loop)
@@ -241,7 +253,7 @@ def read_wav(path):
 
 def _audio_to_audio(pipe, args, generator, windowed=None, **routed):
     """the clips of an --init-audio call; windowed: the window keywords of a --window-seconds call; routed: prompt= / adapter_names= of
-    an --adapters call (one clip per routing entry, all from the same recording), and output_sampling_rate="""
+    an --adapters call (one clip per routing entry, all from the same recording), output_sampling_rate= and the loudness keywords"""
     sr, wav = read_wav(args.init_audio)
     a2a = AudioLDMAudioToAudioPipeline.from_pipe(pipe)
     if args.repaint is not None:

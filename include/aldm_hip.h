@@ -776,6 +776,37 @@ int aldm_clip_normalize_parts(int T, int target);
 int aldm_clip_normalize(const float* y, const int* n, int B, int T, int target, double* workspace, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * ITU-R BS.1770-4 integrated loudness (mono, channel weight 1) and loudness normalisation (csrc/loudness.hip).  No host
+ * synchronisation and no floating-point atomics in any of them: the chain can be captured in a graph, and a row's result depends
+ * neither on B nor on the row's place in the batch.  x fp32 [B][T], lens int32 [B] on the device (cut to [0, T]), hop = fs / 10.
+ * ------------------------------------------------------------------------------------------ */
+/* The samples of a chunk: the kernels cut a clip into chunks of this many samples and hand the filter state along them. */
+int aldm_loudness_chunk(void);
+/* K-weighted energy per hop: energy float64 [B][T / hop], energy[b][j] = sum of y^2 over [j hop, (j + 1) hop) for the complete hops
+   inside lens[b], exactly 0 behind them; y = the cascade of two biquads in transposed direct form II from a zero state at sample 0,
+   state and sums in float64.  coef float64 [10] on the device = {b0, b1, b2, a1, a2} of the shelf then of the high-pass (a0 = 1);
+   mpow float64 [6][2][16] on the device: the 4x4 state transition of the cascade over `chunk` samples, to the powers 1, 2, 4 .. 32,
+   each as a double-double (the 16 leading doubles, then the 16 trailing ones; row-major; state order s1, s2 of the shelf, s1, s2 of
+   the high-pass).  chunk must be the library's chunk length, hop >= 800.
+   workspace: as many doubles as the workspace function says for (B, T); contents need not survive.  T < hop: there is no hop,
+   energy may be NULL (here and in the gate, which then answers -inf). */
+long long aldm_kweight_energy_workspace_doubles(int B, int T);
+int aldm_kweight_energy(const float* x, const int* lens, int B, int T, int hop, const double* coef, const double* mpow, int chunk,
+                        double* workspace, double* energy, void* stream);
+/* Gated loudness from the hop energies: block i = hops i .. i + 3, z_i = their sum / (4 hop), l_i = -0.691 + 10 log10 z_i; absolute
+   gate l_i > -70, relative gate 10 LU under the loudness of the absolutely gated blocks; lufs float64 [B] = -0.691 + 10 log10 of the
+   mean z of the blocks that pass both, -inf for a clip without a block above -70 (shorter than 4 hops, or silent). */
+int aldm_loudness_gate(const double* energy, const int* lens, int B, int T, int hop, double* lufs, void* stream);
+/* peak fp32 [B] = max |x[b][i]| over i < min(T, ceil(lens[b] lens_up / lens_down)) (0 for an empty row): with 1 : 1 the row's own
+   length, with up : down the length of the row the resampler made from a source row of lens[b] samples */
+int aldm_peak_abs(const float* x, const int* lens, int B, int T, int lens_up, int lens_down, float* peak, void* stream);
+/* gain[b] = 10^((target_lufs - lufs[b]) / 20), with use_ceiling at most 10^(ceiling_dbfs / 20) / peak[b], rounded towards zero to
+   fp32; a row whose lufs is not finite keeps gain 1.  gain fp32 [B], gain_db float64 [B] = 20 log10 of the fp32 gain,
+   y fp32 [B][T] = gain x below lens[b] and exactly 0 from there on (y != x). */
+int aldm_loudness_gain(const float* x, const int* lens, int B, int T, const double* lufs, const float* peak, double target_lufs,
+                       double ceiling_dbfs, int use_ceiling, float* gain, double* gain_db, float* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * What aldm_igemm would run, answered on the host (no device needed; pointer fields of the argument are only tested for null).
  * The dispatch itself reads these two answers: csrc/igemm_select.h holds the tile table and the selection.
  * ------------------------------------------------------------------------------------------ */
